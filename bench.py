@@ -26,9 +26,15 @@ Also on the JSON line:
   roofline     — dominant kernel of the timed run: algorithmic bytes (SURVEY.md section 8d) / its HIP-event time, per launch;
                  `traffic` = HBM bytes per launch of that kernel from the stored rocprofv3 PMC pass of the same command
                  (PMC_FILES below: the newest profiles/rNN_pmc_traffic.json taken from these sources), null if that file has no row for it
+  and with --full only (null otherwise; a plain run sets up, warms up, times the K steps and prints the line):
+  verify       — one more untimed traversal of the chain, the digest of every iteration's output DB against the committed digests
+  wall_to_contigs — (c2 / c3, one GPU) the fused C++ driver as its own process, fragment DB files on disk -> final DB on disk
   cpu_baseline — the CPU oracle (a port of the reference's algorithm, oracle/) on a bounded sample of the same community
                  model on this host's cores (rank 0, N = 1), plus the I/O-inclusive rate of the drop-in command line
                  (plass-hip: DB files in, DB files out) on the same sample
+
+--dump-outputs DIR writes what the last timed step computed (dump_outputs: its output DB's digest, size and a seeded sample of its
+entries, and the step's result counts) to DIR/<name>.npy in float32 / float64, after the timed steps.
 """
 import argparse
 import json
@@ -334,6 +340,43 @@ def cpu_baseline(ctx, cfg, sample_pairs, iters):
     return res
 
 
+DUMP_SEED = 0                     # --dump-outputs: the sample of an output DB's entries is drawn with this seed ...
+DUMP_SAMPLE_ENTRIES = 16384       # ... this many entries (all of a smaller DB) ...
+DUMP_MAX_RESIDUES = 8 << 20       # ... cut back to at most this many residues over all DBs dumped (32 MB of float32)
+
+
+def dump_outputs(ctx, out_dir, dbs, counts):
+    """--dump-outputs: what the last timed step handed its caller, as float .npy files under out_dir (same arguments, same files).
+    counts.npy = the step's result counts (config c2 / c3: candidate overlaps, accepted alignments, extended sequences; c5: the same three);
+    per output DB <name>: <name>_digest.npy = the order-independent digest of the WHOLE DB (plasship_seqdb_digest) as four 16-bit limbs,
+    most significant first, then its entry bytes; <name>_info.npy = entries, residues, longest entry; and a fixed seeded sample of its
+    entries in key order: <name>_keys.npy, <name>_lengths.npy (residues per entry) and <name>_residues.npy (the sampled entries' residue
+    bytes back to back)."""
+    import numpy as np
+    from plass_amd._lib import _check
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(out_dir, name + ".npy"), a)
+    save("counts", np.array(counts, dtype=np.float64))
+    for name, db in dbs.items():
+        i = db.info()
+        dg, entry_bytes = db.digest()
+        d = int(dg, 16)
+        save(name + "_digest", np.array([(d >> s) & 0xffff for s in (48, 32, 16, 0)] + [entry_bytes], dtype=np.float64))
+        save(name + "_info", np.array([i["n"], i["residues"], i["max_entry_len"]], dtype=np.float64))
+        n = i["n"]
+        data = np.empty(max(i["data_bytes"], 1), dtype=np.uint8)
+        off = np.empty(max(n, 1), dtype=np.uint64); elen = np.empty(max(n, 1), dtype=np.uint32); key = np.empty(max(n, 1), dtype=np.uint32)
+        _check(ctx.lib.plasship_seqdb_download(ctx.h, db.h, data.ctypes.data, off.ctypes.data, elen.ctypes.data, key.ctypes.data), "plasship_seqdb_download")
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE_ENTRIES), replace=False)) if n else np.zeros(0, dtype=np.int64)
+        lens = elen[idx].astype(np.int64) - 2                # (an entry is "SEQ\n\0")
+        keep = np.cumsum(lens) <= DUMP_MAX_RESIDUES // len(dbs)
+        idx, lens = idx[keep], lens[keep]
+        res = [data[int(off[j]):int(off[j]) + int(l)] for j, l in zip(idx, lens)]
+        save(name + "_keys", key[idx].astype(np.float64))
+        save(name + "_lengths", lens.astype(np.float64))
+        save(name + "_residues", (np.concatenate(res) if res else np.zeros(0, dtype=np.uint8)).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -341,15 +384,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=None, help="untimed iterations first (default: one traversal of the chain)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c3", help="c3 = BASELINE configs[2]/[3] (50 M reads, default); c2 = configs[1] (1 M reads); c5 = configs[4] (PenguiN chains, 20 M reads, one GPU)")
     ap.add_argument("--pairs", type=int, default=0, help="read pairs of the whole job (0 = the config's own; the community scales with it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed verification traversal, the CPU baseline and (c2 / c3, one GPU) the wall clock to contigs; "
+                         "without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (its output DB(s) — digest, size and a seeded sample of entries — and result counts) to DIR/<name>.npy")
     ap.add_argument("--cpu-sample-pairs", type=int, default=0, help="0 = 40000 below 8 host cores, 120000 otherwise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-wall", action="store_true", help="skip the wall-clock-to-contigs run of the fused C++ driver (DB files on disk -> final DB on disk)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the untimed traversal that digests every iteration's output DB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-wall", action="store_true", help="--full: skip the wall-clock-to-contigs run of the fused C++ driver (DB files on disk -> final DB on disk)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the untimed traversal that digests every iteration's output DB")
     ap.add_argument("--comm", choices=["auto", "native", "torch"], default="auto",
                     help="sharded run: 'native' = the library's own RCCL communicator (include/plasship_rccl.h), 'torch' = torch.distributed P2P; auto = native, torch if that fails")
     ap.add_argument("--mode", choices=["auto", "sharded", "partitions"], default="auto",
                     help="N > 1: 'sharded' = the one read set over the GPUs with RCCL all-to-all (default); 'partitions' = N independent sets of 1/N the size")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps == 0:
+        ap.error("--dump-outputs needs at least one timed step")
     if args.config == "c5":
         return main_c5(args)
 
@@ -480,6 +530,12 @@ def main():
     final_info = db.info() if steps else db0.info()
     local_overlaps = overlaps
     elapsed, overlaps = pdist.reduce_step(dist, elapsed, overlaps, device="cuda")
+    if args.dump_outputs:
+        if rank == 0:
+            _, _, k, r, a, _ = rows[-1]
+            dump_outputs(ctx, args.dump_outputs, {"seq": db}, [k.n_candidates, r.n_accepted, a.n_extended])
+        if dist is not None:
+            dist.barrier()
 
     if rank == 0:
         stats = [stage_table(k, r, a) for (_, _, k, r, a, _) in rows]
@@ -561,7 +617,7 @@ def main():
     # workload (tests/golden/c3_chain_digests.json: agreed on by the line-store, the dense-partition and the sharded path,
     # tests/test_gpu_large.py).  A 32-bit slip above 2^32 record slots can no longer print a plausible rate unnoticed.
     verify = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         vdb, digests = db0, []
         for it in range(chain):
             out, _, _, _, _ = one_iteration(ctx, vdb, it)
@@ -587,7 +643,7 @@ def main():
     # nine short `plass-hip` invocations of this leg then measure that (round 4's first evidence run: 4.8 s instead of 1.3 s;
     # tools/cli_dropin_probe.py, profiles/r04_calls/call21_cli_dropin_probe.log) ----
     cpu_line = None
-    if rank == 0 and world == 1 and comm is None and native is None and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and comm is None and native is None and not args.no_cpu_baseline:
         # (64 host cores and more: 1 M pairs through ALL iterations of the chain, about a minute; fewer: three iterations of a smaller sample)
         cpu_line = cpu_baseline(ctx, args.config, args.cpu_sample_pairs, chain if len(os.sched_getaffinity(0)) >= 32 else min(chain, 3))
     # ---- wall clock to final contigs (the metric's second half): the fragment DB goes to disk, then the fused C++ driver
@@ -599,7 +655,7 @@ def main():
     # just ended, not of the path.  The second run starts after PLASS_BENCH_SCRUB_WAIT seconds (default 20) of an idle GPU: `seconds` is
     # that run, the first one is kept as `seconds_behind_a_job_that_just_freed_the_hbm`.
     wall = None
-    if rank == 0 and world == 1 and mode == "single" and args.config in ("c2", "c3") and not args.no_wall:
+    if args.full and rank == 0 and world == 1 and mode == "single" and args.config in ("c2", "c3") and not args.no_wall:
         import shutil
         wall = {"seconds": None}
         tdir = tempfile.mkdtemp(prefix="plass_wall_", dir=os.environ.get("PLASS_BENCH_TMPDIR"))
@@ -748,11 +804,15 @@ def main_c5(args):
     rows, overlaps = run(steps, True)
     ctx.sync(); torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:                                    # the last step's outputs: the extended ORFs and their twins, or the non-circular contigs
+        _, _, k, r, a, _, kind = rows[-1]
+        dump_outputs(ctx, args.dump_outputs, {"nucl": st["nu"], "aa": st["aa"]} if kind == "guided" else {"seq": st["db"]},
+                     [k.n_candidates, r.n_accepted, a.n_extended])
     # ---- untimed verification: one more traversal, digest of every step's output DB(s) against the committed digests of this workload
     # (tests/golden/c5_chain_digests.json — written down from the GPU path's output in round 4; round 5: identical to the unmodified reference's
     # run of the same 20 M reads, profiles/r05_headline_pin_reference.txt) ----
     verify = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         digests = []
         run(chain, False, digests)
         verify = {"step_digests": digests, "reference": None, "match": None}
@@ -802,7 +862,7 @@ def main_c5(args):
     nu0.free(); aa0.free(); reads.free()
     ctx.close()
     line["verify"] = verify
-    line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_c5(args.cpu_sample_pairs)
+    line["cpu_baseline"] = cpu_baseline_c5(args.cpu_sample_pairs) if args.full and not args.no_cpu_baseline else None
     import ctypes
     sys.stderr.flush(); ctypes.CDLL(None).fflush(None)
     print(json.dumps(line), flush=True)
