@@ -356,6 +356,32 @@ int plasship_orfhdr_write(plasship_ctx *ctx, const plasship_orfhdr *h, const cha
 int plasship_orfhdr_count(const plasship_orfhdr *h, size_t *n);
 void plasship_orfhdr_free(plasship_ctx *ctx, plasship_orfhdr *h);
 
+/* ---- mergereads  (replaces int mergereads(int, const char**, const Command&), src/assembler/mergereads.cpp:15-129: FLASH's combine_reads
+ *      per pair, lib/flash/combine_reads.cpp; the first step of every paired-end run, data/assemble.sh:27-38).  Positional args
+ *      <r1> <r2> [<r1b> <r2b> ...] <o:readDB>; file pairs are processed in sequence with continuing keys, a pair of files stops at the
+ *      shorter one.  `reads` = the read DB (dbtype 1, keys 0..n-1 in input order: a merged pair gives one entry, an unmerged pair mate 1
+ *      and the reverse-complemented mate 2), resident on the device; `headers` = <readDB>_h (dbtype 12 = DBTYPE_GENERIC_DB, entries
+ *      "name\n\0" with the kseq name of mate 1, or of mate 1 and mate 2), a sequence DB handle that plasship_seqdb_write writes as it is.
+ *      Input: FASTQ, plain or .gz (by file name), four-line records.  PLASSHIP_ERR_UNSUPPORTED before anything is computed for what the
+ *      reference reads but this path does not: "stdin", .bz2, FASTA, multi-line or malformed records, an empty sequence, a quality byte
+ *      >= 128, parameters other than the reference's.  par may be NULL (the reference's values). ---------------------------------- */
+typedef struct plasship_merge_params {
+    int32_t min_overlap;          /* 15   (mergereads.cpp:20)                                                             */
+    int32_t max_overlap;          /* 65   (mergereads.cpp:19)                                                             */
+    float max_mismatch_density;   /* 0.10 (mergereads.cpp:21)                                                             */
+    int32_t cap_mismatch_quals;   /* 0    (only changes the merged qualities, which are not written)                      */
+    int32_t allow_outies;         /* 0                                                                                    */
+} plasship_merge_params;
+typedef struct plasship_merge_stats {
+    uint64_t pairs, combined, not_combined;
+    uint64_t long_pairs;          /* pairs with a mate longer than 512 bases (the wave-per-pair kernel)                   */
+    float ms_parse;               /* host: reading / decompressing, validating and packing the FASTQ, building the header DB */
+    float ms_upload;              /* host -> device copies of the packed batches                                          */
+    float ms_kernel;              /* HIP events around the kernels of every batch                                         */
+} plasship_merge_stats;
+int plasship_mergereads(plasship_ctx *ctx, const char *const *fastq, size_t n_files, const plasship_merge_params *par,
+                        plasship_seqdb **reads, plasship_seqdb **headers, plasship_merge_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,16 @@ class SynthStats(C.Structure):
                 ("ms_kernel", C.c_float)]
 
 
+class _MergeParams(C.Structure):
+    _fields_ = [("min_overlap", C.c_int32), ("max_overlap", C.c_int32), ("max_mismatch_density", C.c_float),
+                ("cap_mismatch_quals", C.c_int32), ("allow_outies", C.c_int32)]
+
+
+class MergeStats(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("combined", C.c_uint64), ("not_combined", C.c_uint64), ("long_pairs", C.c_uint64),
+                ("ms_parse", C.c_float), ("ms_upload", C.c_float), ("ms_kernel", C.c_float)]
+
+
 class AlnRecord(C.Structure):
     _fields_ = [("query_key", C.c_uint32), ("target_key", C.c_uint32), ("bit_score", C.c_int32), ("raw_score", C.c_int32),
                 ("seq_id", C.c_float), ("q_start", C.c_int32), ("q_end", C.c_int32), ("q_len", C.c_int32),
@@ -150,6 +160,7 @@ SYMBOLS = [
     ("plasship_orfhdr_write", C.c_int, [P, P, C.c_char_p]),
     ("plasship_orfhdr_count", C.c_int, [P, C.POINTER(C.c_size_t)]),
     ("plasship_orfhdr_free", None, [P, P]),
+    ("plasship_mergereads", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_MergeParams), C.POINTER(P), C.POINTER(P), C.POINTER(MergeStats)]),
 ]
 # include/plasship_rccl.h (native RCCL communicator of a sharded run)
 RCCL_SYMBOLS = [
@@ -290,6 +301,19 @@ class SynthParams:
     def _c(self):
         return _SynthParams(self.n_pairs, self.seed, self.n_genomes, self.genome_min_len, self.genome_max_len, self.abundance_sigma,
                             self.insert_mean, self.insert_sd, self.insert_min, self.read_len, self.error_rate)
+
+
+@dataclass
+class MergeParams:
+    """the FLASH parameters of the reference's mergereads (src/assembler/mergereads.cpp:19-23); only these values are implemented"""
+    min_overlap: int = 15
+    max_overlap: int = 65
+    max_mismatch_density: float = 0.10
+    cap_mismatch_quals: bool = False
+    allow_outies: bool = False
+
+    def _c(self):
+        return _MergeParams(self.min_overlap, self.max_overlap, self.max_mismatch_density, int(self.cap_mismatch_quals), int(self.allow_outies))
 
 
 class Context:
@@ -445,6 +469,14 @@ class Context:
         aa, _ = self.translatenucs(nucl, hdr, add_orf_stop=True)
         hdr.free()
         return nucl, aa
+
+    def mergereads(self, paths, par=None):
+        """paired-end FASTQ files [r1, r2, r1b, r2b, ...] (plain or .gz) -> (read DB, header DB, MergeStats); reference module mergereads"""
+        paths = [os.fsencode(str(p)) for p in paths]
+        arr = (C.c_char_p * len(paths))(*paths)
+        h = P(); hh = P(); st = MergeStats(); cp = (par or MergeParams())._c()
+        _check(self.lib.plasship_mergereads(self.h, arr, len(paths), C.byref(cp), C.byref(h), C.byref(hh), C.byref(st)), "plasship_mergereads")
+        return SeqDB(self, h), SeqDB(self, hh), st
 
     def synth_read_pairs(self, par):
         """synthetic read pairs generated in HBM (include/plasship_synth.h) -> nucleotide read DB"""

@@ -116,6 +116,7 @@ static const std::map<std::string, std::set<std::string>> &moduleFlags() {
                                "--cov-mode", "--max-seq-len", "--keep-target", "--hash-shift", "--ignore-multi-kmer", "--rescore-mode", "--min-aln-len", "--seq-id-mode"};
         m["nuclassemble-chain"] = m["assemble-chain"]; m["nuclassemble-chain"].insert("--chop-cycle");
         m["guidedassemble-chain"] = m["assemble-chain"];
+        m["mergereads"] = {};       // the reference's onlythreads set (plass.cpp:47, Parameters.cpp:301-303): --threads, -v
         for (auto &kv : m) kv.second.insert(common.begin(), common.end());
     }
     return m;
@@ -138,9 +139,11 @@ int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stdout, "usage: plass-hip <kmermatcher|rescorediagonal|assembleresults|nuclassembleresults|guidedassembleresults|proteinaln2nucl|findassemblystart|"
                         "cyclecheck|extractorfs|translatenucs|concatdbs> <dbs…> [flags]\n"
-                        "       plass-hip assemble-chain <i:fragmentDB|readDB> <o:assemblyDB> [--num-iterations 12] [--from-reads 1] [--write-intermediate DIR]\n"
-                        "       plass-hip nuclassemble-chain <i:nuclDB> <o:assemblyDB> [--num-iterations 8]        (writes <o>_cycle_<i> for circular contigs)\n"
-                        "       plass-hip guidedassemble-chain <i:readDB> <o:nuclAssemblyDB> <o:aaAssemblyDB> [--num-iterations 5]\n");
+                        "       plass-hip mergereads <i:r1.fastq[.gz]> <i:r2.fastq[.gz]> [<r1b> <r2b> …] <o:readDB>      (writes <o> and <o>_h)\n"
+                        "       plass-hip assemble-chain <i:fragmentDB|readDB | r1.fastq r2.fastq …> <o:assemblyDB> [--num-iterations 12] [--from-reads 1] [--write-intermediate DIR]\n"
+                        "       plass-hip nuclassemble-chain <i:nuclDB | r1.fastq r2.fastq …> <o:assemblyDB> [--num-iterations 8]        (writes <o>_cycle_<i> for circular contigs)\n"
+                        "       plass-hip guidedassemble-chain <i:readDB | r1.fastq r2.fastq …> <o:nuclAssemblyDB> <o:aaAssemblyDB> [--num-iterations 5]\n"
+                        "       (FASTQ pairs: merged on the GPU first, as the workflows' mergereads step, data/assemble.sh:27-38)\n");
         return EXIT_FAILURE;
     }
     const std::string mod = argv[1];
@@ -271,6 +274,22 @@ int main(int argc, char **argv) {
     if (mod == "proteinaln2nucl" && pos.size() == 6 && (pos[0] == pos[1]) != (pos[2] == pos[3])) { fprintf(stdout, "Either query database == target database for nucleotide and amino acid or != for both\n"); return EXIT_FAILURE; }
     if (mod == "proteinaln2nucl" && pos.size() == 6 && pos[0] != pos[1])
         return unsupported("plass-hip proteinaln2nucl: separate query and target DBs are not part of the GPU path (the assembly workflows use one DB)\n");
+    // mergereads (and the chains started from FASTQ pairs): the inputs KSeqFactory reads without this path's parser (KSeqWrapper.cpp:160-195)
+    // are refused by name here; what only the contents show (FASTA, multi-line records, quality bytes >= 128) comes back from the library as
+    // PLASSHIP_ERR_UNSUPPORTED before anything is written
+    const size_t nChainOut = mod == "guidedassemble-chain" ? 2 : 1;
+    std::vector<std::string> fastqIn;
+    if (mod == "mergereads") {
+        if (pos.size() < 3 || (pos.size() - 1) % 2) { fprintf(stdout, "mergereads <i:fastqFile1[.gz]> <i:fastqFile2[.gz]> ... <o:sequenceDB>\n"); return EXIT_FAILURE; }
+        fastqIn.assign(pos.begin(), pos.end() - 1);
+    } else if (chain && pos.size() > nChainOut + 1) {
+        if ((pos.size() - nChainOut) % 2) { fprintf(stdout, "%s: one DB or pairs of FASTQ files before the output\n", mod.c_str()); return EXIT_FAILURE; }
+        fastqIn.assign(pos.begin(), pos.end() - nChainOut);
+    }
+    for (const std::string &q : fastqIn) {
+        if (q == "stdin") return unsupported("plass-hip %s: reading stdin is left to the reference\n", mod.c_str());
+        if (q.size() >= 4 && q.compare(q.size() - 4, 4, ".bz2") == 0) return unsupported("plass-hip %s: bzip2 input (%s) is left to the reference\n", mod.c_str(), q.c_str());
+    }
     if (getenv("PLASSHIP_CLI_DRYRUN") && atoi(getenv("PLASSHIP_CLI_DRYRUN")) != 0) {
         fprintf(stdout, "plass-hip dry run: %s accepted (%zu positional arguments, %zu flags); nothing read or computed\n", mod.c_str(), pos.size(), f.seen.size());
         return EXIT_DRYRUN_ACCEPTED;
@@ -413,12 +432,23 @@ int main(int argc, char **argv) {
             if (KW(plasship_orfhdr_write(ctx, o, pos[2].c_str()))) return fail("concatdbs");
             plasship_orfhdr_free(ctx, o); plasship_orfhdr_free(ctx, b); plasship_orfhdr_free(ctx, a);
         } else { fprintf(stdout, "plass-hip concatdbs: cannot read the database type of %s\n", pos[0].c_str()); return EXIT_FAILURE; }      // (other types were refused above)
+    } else if (mod == "mergereads") {
+        // writes <out> and <out>_h like the reference (mergereads.cpp:28-31)
+        std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
+        plasship_seqdb *r = nullptr, *h = nullptr;
+        plasship_merge_stats st; memset(&st, 0, sizeof(st));
+        if (K(plasship_mergereads(ctx, files.data(), files.size(), nullptr, &r, &h, &st))) return fail("mergereads");
+        fprintf(stdout, "pairs: %llu combined: %llu not combined: %llu | parse %.3f s upload %.3f s kernels %.3f ms\n", (unsigned long long) st.pairs,
+                (unsigned long long) st.combined, (unsigned long long) st.not_combined, st.ms_parse * 1e-3, st.ms_upload * 1e-3, st.ms_kernel);
+        if (KW(plasship_seqdb_write(ctx, r, pos.back().c_str())) || KW(plasship_seqdb_write(ctx, h, (pos.back() + "_h").c_str()))) return fail("mergereads");
+        plasship_seqdb_free(ctx, h); plasship_seqdb_free(ctx, r);
     } else if (chain) {
         // ---- fused drivers: the iteration loop of a workflow script with every DB of the loop resident in HBM; only the first DB is
         //      read from disk and only the last one written (plus, with --write-intermediate DIR, every iteration's assembly by a host
         //      thread on a second context while the next iteration runs, with the workflow's .done sentinels) ----
         const bool prot = mod == "assemble-chain", nuc = mod == "nuclassemble-chain", gd = mod == "guidedassemble-chain";
-        if (pos.size() != (gd ? 3u : 2u)) { fprintf(stdout, "%s: wrong number of databases\n", mod.c_str()); return EXIT_FAILURE; }
+        if (pos.size() != (gd ? 3u : 2u) && fastqIn.empty()) { fprintf(stdout, "%s: wrong number of databases\n", mod.c_str()); return EXIT_FAILURE; }
+        const std::vector<std::string> outs(pos.end() - nChainOut, pos.end());
         if (f.numIterations < 1) { fprintf(stdout, "--num-iterations must be at least 1\n"); return EXIT_FAILURE; }
         plasship_ctx *wctx = nullptr; std::thread writer; int writerRc = 0; std::string writerErr;
         // every exit path below joins the writer first (a joinable std::thread that goes out of scope terminates the process, and an
@@ -438,7 +468,13 @@ int main(int argc, char **argv) {
         // a multi-GB input: the library takes its device arena (seconds of hipMalloc) while this thread reads and parses the DB files
         { struct stat stIn; if (stat(pos[0].c_str(), &stIn) == 0 && stIn.st_size >= ((off_t) 1 << 30)) (void) plasship_ctx_reserve_async(ctx); }
         plasship_seqdb *in = nullptr;
-        if (K(plasship_seqdb_read(ctx, pos[0].c_str(), &in))) return fail(mod.c_str());
+        if (!fastqIn.empty()) {         // the workflows' mergereads step (data/assemble.sh:27-38): the merged reads stay in HBM, the header DB is not needed
+            std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
+            plasship_seqdb *h = nullptr; plasship_merge_stats ms;
+            if (K(plasship_mergereads(ctx, files.data(), files.size(), nullptr, &in, &h, &ms))) return fail(mod.c_str());
+            plasship_seqdb_free(ctx, h);
+            fprintf(stdout, "mergereads: %llu pairs, %llu combined\n", (unsigned long long) ms.pairs, (unsigned long long) ms.combined);
+        } else if (K(plasship_seqdb_read(ctx, pos[0].c_str(), &in))) return fail(mod.c_str());
         const double tRead = now();
         int dbtype = -1; plasship_seqdb_info(in, nullptr, nullptr, nullptr, &dbtype, nullptr);
         auto orfPar = [&](bool start) {       // the two extractorfs passes (Assembler.cpp:116-130, GuidedNuclassembler.cpp:133-145)
@@ -505,7 +541,7 @@ int main(int argc, char **argv) {
             if (nuc) {     // data/nuclassemble.sh:19-61,132: circular contigs leave the loop, the rest goes on
                 plasship_seqdb *cyc = nullptr, *rest = nullptr; plasship_cyclecheck_params cp; cp.max_seq_len = f.maxSeqLen; cp.chop_cycle = f.chopCycle; plasship_cyclecheck_stats cs;
                 if (K(plasship_cyclecheck(ctx, db, &cp, &cyc, &rest, &cs))) return fail(mod.c_str());
-                if (cs.n_cyclic && KW(plasship_seqdb_write(ctx, cyc, (pos[1] + "_cycle_" + std::to_string(it)).c_str()))) return fail(mod.c_str());
+                if (cs.n_cyclic && KW(plasship_seqdb_write(ctx, cyc, (outs[0] + "_cycle_" + std::to_string(it)).c_str()))) return fail(mod.c_str());
                 plasship_seqdb_free(ctx, cyc); plasship_seqdb_free(ctx, db); db = rest;
             }
             fprintf(stdout, "iteration %d: candidates %llu verified %llu extended %llu (%.3f s since the DB was read)\n", it, (unsigned long long) ks.n_candidates, (unsigned long long) rs.n_accepted, (unsigned long long) as.n_extended, now() - tPrep);
@@ -513,7 +549,7 @@ int main(int argc, char **argv) {
         }
         const double tLoop = now();
         if (joinWriter()) { fprintf(stdout, "%s: writing an intermediate DB failed: %s\n", mod.c_str(), writerErr.c_str()); return EXIT_FAILURE; }
-        if (KW(plasship_seqdb_write(ctx, db, pos[1].c_str())) || (gd && KW(plasship_seqdb_write(ctx, aa, pos[2].c_str())))) return fail(mod.c_str());
+        if (KW(plasship_seqdb_write(ctx, db, outs[0].c_str())) || (gd && KW(plasship_seqdb_write(ctx, aa, outs[1].c_str())))) return fail(mod.c_str());
         const double tEnd = now();
         fprintf(stdout, "chain: %d iterations, %llu candidate overlaps | read %.3fs preprocessing %.3fs iterations %.3fs (kernels %.3fs) write %.3fs\n", f.numIterations, overlaps,
                 tRead - t0, tPrep - tRead, tLoop - tPrep, kernelMs * 1e-3, tEnd - tLoop);
