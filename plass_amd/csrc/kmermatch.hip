@@ -218,6 +218,31 @@ struct LinesOut { void *triples = nullptr; uint64_t nTriples = 0, Nk = 0, Nm = 0
 
 constexpr uint64_t HALO_SLACK = 1u << 16;
 
+// PLASSHIP_DEBUG_AGGHIST=1 (debug only, off by default): per rep sort, a histogram of the sort buckets by record slots (lines * RPL: an
+// upper bound of the records, padding slots included) and by distinct (rep, target, diagonal) keys, on stderr.  It waits for the stream.
+static bool aggHistOn() { return getenv("PLASSHIP_DEBUG_AGGHIST") != nullptr; }
+static int aggHistRecord(hipStream_t st, const uint32_t *dLineCnt, const uint32_t *dUnique, uint32_t nSort) {
+    static int call = 0;
+    std::vector<uint32_t> lc(nSort), uq(nSort);
+    PH_COPY_SYNC(st, lc.data(), dLineCnt, (size_t) nSort * 4, hipMemcpyDeviceToHost);
+    PH_COPY_SYNC(st, uq.data(), dUnique, (size_t) nSort * 4, hipMemcpyDeviceToHost);
+    constexpr int NB = 10;                         // bins: 0, <= 64, <= 128, ..., <= 8192, > 8192
+    auto bin = [](uint64_t v) { if (!v) return 0; int k = 1; uint64_t e = 64; while (k < NB - 1 && v > e) { e <<= 1; k++; } return k; };
+    uint64_t hr[NB] = {}, hd[NB] = {}, sr = 0, sd = 0, mr = 0, md = 0, big = 0;
+    for (uint32_t b = 0; b < nSort; b++) {
+        const uint64_t r = (uint64_t) lc[b] * RPL; hr[bin(r)]++; sr += r; mr = std::max(mr, r);
+        if (uq[b] == AGG_NEEDS_SCRATCH) { big++; continue; }     // (pass 2 rewrites these; only left so if it did not run)
+        hd[bin(uq[b])]++; sd += uq[b]; md = std::max<uint64_t>(md, uq[b]);
+    }
+    std::string s = "aggHist call " + std::to_string(call++) + " buckets " + std::to_string(nSort) + " | bins 0,<=64,<=128,...,<=8192,>8192 | slots";
+    for (int k = 0; k < NB; k++) s += " " + std::to_string(hr[k]);
+    s += " (mean " + std::to_string(nSort ? sr / nSort : 0) + ", max " + std::to_string(mr) + ") | distinct";
+    for (int k = 0; k < NB; k++) s += " " + std::to_string(hd[k]);
+    s += " (mean " + std::to_string(nSort ? sd / nSort : 0) + ", max " + std::to_string(md) + ", scratch " + std::to_string(big) + ")";
+    fprintf(stderr, "%s\n", s.c_str());
+    return PLASSHIP_OK;
+}
+
 // ---- sort #2 over the line store: range partition of `in` (the level-1 pieces `hp` with `outLine` output lines in total) by ranges of
 // the bit-reversed (rep - repBase), aggregation + sort per bucket, then every representative's triples to their place in
 // representative order.  TRIPLES: `in` holds weighted triples (owner side of a sharded run), else grouped records.
@@ -308,11 +333,36 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
         dScanTmp3.alloc(scanTmp3Bytes) != hipSuccess || dSparse.alloc(sortCap * RPL * sizeof(OutT)) != hipSuccess) {
         setError("kmermatch: out of device memory for the rep sort"); return PLASSHIP_ERR_DEVICE;
     }
-    // pass 1: every bucket aggregated in LDS (no scratch); pass 2: the few buckets with more distinct triples than LDS holds
+    // every representative's number of triples (the wave kernel stores those of its buckets, repRunsKernel adds the rest)
+    DevBuf dRepCnt, dRepStartLocal, dScanTmp4;
+    DevBuf &dRepStart = dRepStartOut ? *dRepStartOut : dRepStartLocal;
+    const size_t scanTmp4Bytes = exclusiveScanTmpBytes((size_t) nReps + 2);
+    if (dRepCnt.alloc(((size_t) nReps + 1) * 4) != hipSuccess || dRepStart.alloc(((size_t) nReps + 2) * 8) != hipSuccess ||
+        dScanTmp4.alloc(scanTmp4Bytes) != hipSuccess) { setError("kmermatch: out of device memory for the rep sort"); return PLASSHIP_ERR_DEVICE; }
+    PH_CHECK(hipMemsetAsync(dRepCnt.p, 0, ((size_t) nReps + 1) * 4, st));
+    // pass 1: every bucket aggregated in LDS (no scratch); pass 2: the few buckets with more distinct triples than LDS holds.
+    // PLASSHIP_TUNE_AGGWAVE: unset / 1 = one wavefront per bucket (aggSortWaveKernel), the block kernel only on the buckets that kernel
+    // leaves over (more than its caps: hot representatives, contig-heavy late iterations); 2 = the block kernel on every bucket.
+    // PLASSHIP_TUNE_AGGWAVE_CAP=n shrinks the wave caps to n distinct keys and 16 n record slots (tests: many buckets take the fall-back).
+    const bool aggWave = tuneInt("AGGWAVE", 1) != 2;
     const AggLines aggLn{sortList, dSortBeg.as<uint32_t>(), dSortCnt.as<uint32_t>()};
     const unsigned aggGrid = std::min<uint32_t>(nSort, (uint32_t) numCU * (uint32_t) tuneInt("AGGSORT", 16));
+    DevBuf dOver;                                             // [0]: buckets over the wave caps, [1 ..]: their list
+    const uint32_t *ovList = nullptr, *ovCount = nullptr;
+    if (aggWave) {
+        if (dOver.alloc(((size_t) nSort + 1) * 4) != hipSuccess) { setError("kmermatch: out of device memory for the rep sort"); return PLASSHIP_ERR_DEVICE; }
+        PH_CHECK(hipMemsetAsync(dOver.p, 0, 4, st));
+        const uint32_t capT = (uint32_t) tuneInt("AGGWAVE_CAP", (int) AW_CAP);
+        AggWaveArgs wa; wa.capKeys = std::min<uint32_t>(capT, AW_CAP); wa.capRecs = std::min<uint32_t>(AW_RECS, wa.capKeys * 16u);
+        wa.ovCount = dOver.as<uint32_t>(); wa.ovList = wa.ovCount + 1; wa.repCnt = dRepCnt.as<uint32_t>();
+        ovCount = wa.ovCount; ovList = wa.ovList;
+        constexpr int WPB = AggWaveGeo<NUCL>::WPB;
+        const unsigned wGrid = std::min<uint32_t>((nSort + WPB - 1) / WPB, (uint32_t) numCU * (uint32_t) tuneInt("AGGWAVE_GRID", (int) AggWaveGeo<NUCL>::PER_CU));
+        hipLaunchKernelGGL((aggSortWaveKernel<NUCL, LONG, TRIPLES, ORDOUT>), dim3(wGrid), dim3(WPB * 64), 0, st, sortRecs, dSparse.p, nSort, dUnique.as<uint32_t>(),
+                           repBits - sBits, idBits, (uint64_t) repBase, aggLn, repBits, wa);
+    }
     hipLaunchKernelGGL((aggSortKernel<NUCL, LONG, true, TRIPLES, ORDOUT>), dim3(aggGrid), dim3(LS_BLOCK), 0, st, sortRecs, dSparse.p, (const uint64_t *) nullptr, nSort,
-                       (unsigned long long *) nullptr, (const uint64_t *) nullptr, dUnique.as<uint32_t>(), repBits - sBits, idBits, (uint64_t) repBase, aggLn, repBits);
+                       (unsigned long long *) nullptr, (const uint64_t *) nullptr, dUnique.as<uint32_t>(), repBits - sBits, idBits, (uint64_t) repBase, aggLn, repBits, ovList, ovCount);
     hipLaunchKernelGGL(bigNeedKernel, dim3(gridFor(nSort, 256, 1024)), dim3(256), 0, st, (const uint32_t *) dSortCnt.as<uint32_t>(), (const uint32_t *) dUnique.as<uint32_t>(), nSort, dBigNeed.as<uint64_t>(), NUCL ? 3u : 2u);
     if (exclusiveScanU64(st, dBigNeed.as<uint64_t>(), dBigOff.as<uint64_t>(), nSort, dScanTmp3.p, scanTmp3Bytes)) { setError("kmermatch: scan failed"); return PLASSHIP_ERR_DEVICE; }
     uint64_t bigTot = 0;
@@ -321,20 +371,17 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
     if (bigTot) {
         if (dBigScratch.alloc(bigTot * 8) != hipSuccess) { setError("kmermatch: out of device memory for the rep sort"); return PLASSHIP_ERR_DEVICE; }
         hipLaunchKernelGGL((aggSortKernel<NUCL, LONG, true, TRIPLES, ORDOUT>), dim3(aggGrid), dim3(LS_BLOCK), 0, st, sortRecs, dSparse.p, (const uint64_t *) nullptr, nSort,
-                           dBigScratch.as<unsigned long long>(), (const uint64_t *) dBigOff.as<uint64_t>(), dUnique.as<uint32_t>(), repBits - sBits, idBits, (uint64_t) repBase, aggLn, repBits);
+                           dBigScratch.as<unsigned long long>(), (const uint64_t *) dBigOff.as<uint64_t>(), dUnique.as<uint32_t>(), repBits - sBits, idBits, (uint64_t) repBase, aggLn, repBits,
+                           ovList, ovCount);
     }
+    if (aggHistOn()) { const int hrc = aggHistRecord(st, dSortCnt.as<uint32_t>(), dUnique.as<uint32_t>(), nSort); if (hrc) return hrc; }
     // every bucket now holds its representatives' triples, each representative's contiguous and in (target, diagonal) order, but
     // the buckets are ranges of the bit-reversed id: count the triples per representative, prefix-sum over the ids, and move every
     // triple to its place in id order — the (rep, target, diagonal)-sorted array the run reduction walks
-    DevBuf dRepCnt, dRepStartLocal, dScanTmp4;
-    DevBuf &dRepStart = dRepStartOut ? *dRepStartOut : dRepStartLocal;
-    const size_t scanTmp4Bytes = exclusiveScanTmpBytes((size_t) nReps + 2);
-    if (dRepCnt.alloc(((size_t) nReps + 1) * 4) != hipSuccess || dRepStart.alloc(((size_t) nReps + 2) * 8) != hipSuccess ||
-        dScanTmp4.alloc(scanTmp4Bytes) != hipSuccess) { setError("kmermatch: out of device memory for the rep sort"); return PLASSHIP_ERR_DEVICE; }
-    PH_CHECK(hipMemsetAsync(dRepCnt.p, 0, ((size_t) nReps + 1) * 4, st));
+    // (with the wave kernel only the buckets of its overflow list are left to count)
     const unsigned runGrid = std::min<uint32_t>((nSort + 3) / 4, (uint32_t) numCU * 8);
     hipLaunchKernelGGL(repRunsKernel<OutT>, dim3(runGrid), dim3(256), 0, st, (const OutT *) dSparse.p, (const uint32_t *) dSortBeg.as<uint32_t>(),
-                       (const uint32_t *) dUnique.as<uint32_t>(), nSort, repBase, dRepCnt.as<uint32_t>());
+                       (const uint32_t *) dUnique.as<uint32_t>(), nSort, repBase, dRepCnt.as<uint32_t>(), ovList, ovCount);
     if (exclusiveScanU32(st, dRepCnt.as<uint32_t>(), dRepStart.as<uint64_t>(), nReps, dScanTmp4.p, scanTmp4Bytes)) { setError("kmermatch: scan failed"); return PLASSHIP_ERR_DEVICE; }
     nTriples = 0;
     PH_COPY_SYNC(st, &nTriples, dRepStart.as<uint64_t>() + nReps, 8, hipMemcpyDeviceToHost);

@@ -1,7 +1,7 @@
 // plasship: kmermatcher on gfx950, stages K6-K8: sort #2 as aggregation, run reduction, the stale-record scan.  Product code; part of kmermatch.hip's translation unit (included there, inside
 // namespace plasship, after common.hpp / device_utils.hpp / linepart.hpp) — split out by stage in round 4, see kmermatch.hip for the
 // reference lines the stage reproduces and DESIGN.md section 4 for the kernels' bounds.
-// Kernels: aggSortKernel, repRunsKernel / placeRunsKernel, reduceRunsKernel, rankLinesKernel and helpers.
+// Kernels: aggSortWaveKernel / aggSortKernel, repRunsKernel / placeRunsKernel, reduceRunsKernel, rankLinesKernel and helpers.
 #pragma once
 
 // =====================================================================================================
@@ -36,7 +36,8 @@ __device__ __forceinline__ bool isSentinel(const TripleX &t) { return t.rep == 0
 template <bool NUCL, bool LONG, bool LINES, bool TRIPLES = false, bool ORDOUT = false>
 __global__ __launch_bounds__(LS_BLOCK) void aggSortKernel(const void *arr, void *outTriples, const uint64_t *__restrict__ bucketStart, uint32_t nBuckets,
                                                           unsigned long long *bigScratch, const uint64_t *__restrict__ bigOff,
-                                                          uint32_t *__restrict__ uniqueCount, int localBits, int idBits, uint64_t repBase, AggLines ln, int scrambleBits) {
+                                                          uint32_t *__restrict__ uniqueCount, int localBits, int idBits, uint64_t repBase, AggLines ln, int scrambleBits,
+                                                          const uint32_t *__restrict__ bList = nullptr, const uint32_t *__restrict__ bListN = nullptr) {
     static_assert(!ORDOUT || NUCL, "only nucleotide triples carry a strand");
     typedef typename std::conditional<TRIPLES, typename std::conditional<NUCL, TripleX, Triple>::type, Rec<LONG>>::type R;
     typedef typename std::conditional<ORDOUT, TripleX, Triple>::type O;
@@ -52,7 +53,10 @@ __global__ __launch_bounds__(LS_BLOCK) void aggSortKernel(const void *arr, void 
     const R *g = reinterpret_cast<const R *>(arr);
     O *out = reinterpret_cast<O *>(outTriples);
     constexpr int DB = DiagPack<LONG>::BITS;
-    for (uint32_t b = blockIdx.x; b < nBuckets; b += gridDim.x) {
+    // bList != nullptr: only the buckets bList[0 .. *bListN) (those aggSortWaveKernel left over)
+    const uint32_t nB = bList ? *bListN : nBuckets;
+    for (uint32_t q = blockIdx.x; q < nB; q += gridDim.x) {
+        const uint32_t b = bList ? bList[q] : q;
         // cnt record positions; LINES: positions in the bucket's line list, padding sentinels are skipped when read
         const uint64_t s0 = LINES ? (uint64_t) ln.lineBeg[b] * RPL : bucketStart[b];        // where the bucket's triples are written
         const uint64_t cnt = LINES ? (uint64_t) ln.lineCnt[b] * RPL : bucketStart[b + 1] - s0;
@@ -250,14 +254,242 @@ __global__ __launch_bounds__(LS_BLOCK) void aggSortKernel(const void *arr, void 
     }
 }
 
+// ---- the same per bucket with ONE wavefront (the common case; the block kernel above takes what does not fit) ----
+// A bucket of a few hundred records holds a few hundred distinct triples: a 256-thread workgroup per bucket paid ~40-50 barriers for it
+// (bitonic stages over LDS) with most of its lanes idle.  Here every wavefront owns an LDS hash table and works through buckets of its
+// own with no workgroup barrier: aggregate with LDS atomics, compact the distinct keys with ballot / mbcnt, sort them in registers
+// (AW_CAP / 64 per lane, a cross-lane bitonic network: DPP, ds_swizzle, bpermute), look every key's count (and rank word) up again in
+// the table, write the triples in the sparse layout and count each representative's run (every representative lies in exactly one
+// bucket: its run head stores the count, no atomic, no second pass over the triples).  A bucket with more than capRecs record slots or
+// more than capKeys distinct keys goes to the overflow list (one atomic per such bucket) for aggSortKernel's list mode.
+constexpr uint32_t AW_CAP = 512;             // distinct keys a wavefront sorts (AW_CAP / 64 registers per lane)
+constexpr uint32_t AW_RECS = 8192;           // record slots (lines * RPL) of a bucket the wavefront aggregates
+constexpr int AW_LOADS = 4;                  // records per lane in flight
+template <bool NUCL> struct AggWaveGeo {     // LDS per wavefront: HT slots of key / count (/ rank word) + AW_CAP list entries
+    static constexpr uint32_t HT = 2 * AW_CAP;
+    static constexpr int WPB = NUCL ? 2 : 4;  // 48 KB (nucleotides) / 64 KB per workgroup
+    static constexpr uint32_t LDS = WPB * (HT * (NUCL ? 20u : 12u) + AW_CAP * 8u);
+    static constexpr uint32_t PER_CU = (160u * 1024u) / LDS;   // resident workgroups per CU (the grid is persistent: that many per CU)
+};
+struct AggWaveArgs { uint32_t capKeys, capRecs; uint32_t *ovList, *ovCount; uint32_t *repCnt; };
+
+__device__ __forceinline__ void waveFence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+template <int J> __device__ __forceinline__ unsigned long long xorLane64(unsigned long long v) {
+    if constexpr (J == 1) return dppMov64<0xB1>(v);                       // quad_perm [1,0,3,2]
+    else if constexpr (J == 2) return dppMov64<0x4E>(v);                  // quad_perm [2,3,0,1]
+    else if constexpr (J < 32) {                                          // ds_swizzle bit mode: and 0x1F, xor J
+        const uint32_t lo = (uint32_t) __builtin_amdgcn_ds_swizzle((int) (uint32_t) v, 0x1F | (J << 10));
+        const uint32_t hi = (uint32_t) __builtin_amdgcn_ds_swizzle((int) (uint32_t) (v >> 32), 0x1F | (J << 10));
+        return ((unsigned long long) hi << 32) | lo;
+    } else return __shfl_xor(v, J, 64);
+}
+// bitonic sort of the 64 * EB keys k[0 .. EB) ascending; element index = e * 64 + lane
+template <int EB, int E> __device__ __forceinline__ void waveBitonic(unsigned long long (&k)[E]) {
+    const int lane = laneId();
+#pragma unroll
+    for (int kk = 2; kk <= 64 * EB; kk <<= 1) {
+#pragma unroll
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            if (j >= 64) {
+                const int je = j >> 6;
+#pragma unroll
+                for (int e = 0; e < EB; e++)
+                    if ((e & je) == 0) {
+                        const bool up = ((e << 6) & kk) == 0;
+                        const unsigned long long x = k[e], y = k[e | je];
+                        const bool sw = (x > y) == up;
+                        k[e] = sw ? y : x; k[e | je] = sw ? x : y;
+                    }
+            } else {
+#pragma unroll
+                for (int e = 0; e < EB; e++) {
+                    unsigned long long y;
+                    switch (j) { case 1: y = xorLane64<1>(k[e]); break; case 2: y = xorLane64<2>(k[e]); break; case 4: y = xorLane64<4>(k[e]); break;
+                                 case 8: y = xorLane64<8>(k[e]); break; case 16: y = xorLane64<16>(k[e]); break; default: y = xorLane64<32>(k[e]); }
+                    const bool up = ((((e << 6) | lane) & kk) == 0), low = (lane & j) == 0;
+                    const unsigned long long mn = k[e] < y ? k[e] : y, mx = k[e] < y ? y : k[e];
+                    k[e] = (low == up) ? mn : mx;
+                }
+            }
+        }
+    }
+}
+
+template <bool NUCL, bool LONG, bool TRIPLES = false, bool ORDOUT = false>
+__global__ __launch_bounds__(AggWaveGeo<NUCL>::WPB * 64) void aggSortWaveKernel(const void *arr, void *outTriples, uint32_t nBuckets, uint32_t *__restrict__ uniqueCount,
+                                                                                 int localBits, int idBits, uint64_t repBase, AggLines ln, int scrambleBits, AggWaveArgs wa) {
+    static_assert(!ORDOUT || NUCL, "only nucleotide triples carry a strand");
+    typedef typename std::conditional<TRIPLES, typename std::conditional<NUCL, TripleX, Triple>::type, Rec<LONG>>::type R;
+    typedef typename std::conditional<ORDOUT, TripleX, Triple>::type O;
+    constexpr uint32_t HT = AggWaveGeo<NUCL>::HT;
+    constexpr int WPB = AggWaveGeo<NUCL>::WPB, E = AW_CAP / 64;
+    constexpr int DB = DiagPack<LONG>::BITS;
+    __shared__ unsigned long long sKey[WPB][HT];
+    __shared__ uint32_t sVal[WPB][HT];
+    __shared__ unsigned long long sOrd[NUCL ? WPB : 1][NUCL ? HT : 1];
+    __shared__ unsigned long long sList[WPB][AW_CAP];
+    const int wv = (int) (threadIdx.x >> 6), lane = laneId();
+    unsigned long long *hKey = sKey[wv], *hOrd = sOrd[NUCL ? wv : 0], *lKey = sList[wv];
+    uint32_t *hVal = sVal[wv];
+    const R *g = reinterpret_cast<const R *>(arr);
+    O *out = reinterpret_cast<O *>(outTriples);
+    for (uint32_t i = lane; i < HT; i += 64) { hKey[i] = ~0ULL; hVal[i] = 0; if (NUCL) hOrd[i] = 0; }
+    waveFence();
+    const uint32_t nW = gridDim.x * WPB;
+    // a software pipeline over the wavefront's buckets b, b + nW, ...: the NEXT bucket's line list (begin, count and the entries of
+    // lines lane and lane + 64; lines beyond 128 are read from the list directly) is requested when a bucket starts, the next bucket's
+    // first AW_LOADS * 64 records when this bucket's records are in the table (they arrive while it is sorted), and inside a bucket
+    // the next batch of records before the current one is inserted
+    struct Lines { uint32_t lb, lc, le0, le1; };
+    auto fetchLines = [&](uint32_t bb) {
+        Lines L; L.lb = ln.lineBeg[bb]; L.lc = ln.lineCnt[bb];
+        L.le0 = (uint32_t) lane < L.lc ? ln.list[L.lb + lane] : 0u;
+        L.le1 = (uint32_t) lane + 64 < L.lc ? ln.list[L.lb + 64 + lane] : 0u;
+        return L;
+    };
+    auto loadBatch = [&](const Lines &L, uint32_t i0, R (&r)[AW_LOADS]) {
+#pragma unroll
+        for (int u = 0; u < AW_LOADS; u++) {
+            const uint32_t i = i0 + (uint32_t) (u * 64 + lane), line = i / RPL;
+            const uint32_t a0 = (uint32_t) __shfl((int) L.le0, (int) (line & 63), 64), a1 = (uint32_t) __shfl((int) L.le1, (int) (line & 63), 64);
+            if (i < L.lc * RPL) { const uint32_t le = line < 64 ? a0 : line < 128 ? a1 : ln.list[L.lb + line]; r[u] = g[(uint64_t) le * RPL + (i % RPL)]; }
+        }
+    };
+    uint32_t b = blockIdx.x * WPB + (uint32_t) wv;
+    Lines cur = {0u, 0u, 0u, 0u};
+    R r[AW_LOADS];
+    if (b < nBuckets) { cur = fetchLines(b); loadBatch(cur, 0, r); }
+    for (; b < nBuckets; b += nW) {
+        const uint32_t lb = (uint32_t) __builtin_amdgcn_readfirstlane((int) cur.lb), lc = (uint32_t) __builtin_amdgcn_readfirstlane((int) cur.lc);
+        cur.lb = lb; cur.lc = lc;
+        const bool more = b + nW < nBuckets;
+        Lines nxt = {0u, 0u, 0u, 0u};
+        if (more) nxt = fetchLines(b + nW);
+        const uint32_t cnt = lc * RPL;
+        const uint64_t s0 = (uint64_t) lb * RPL;
+        const uint64_t bucketBase = (uint64_t) b << localBits;
+        auto packRec = [&](const R &r, uint32_t &val, unsigned long long &ord) {          // as aggSortKernel's
+            uint64_t rep, target; int64_t diag; ord = 0;
+            if constexpr (TRIPLES) { rep = r.rep; target = r.target; diag = r.diag; val = r.cnt & 0x7FFFFFFFu; if constexpr (NUCL) ord = r.ord; }
+            else { rep = (uint32_t) r.kmer; target = r.id; diag = r.pos; val = 1u; if constexpr (NUCL) ord = ordWordOf(r); }
+            rep -= repBase;
+            if (scrambleBits) rep = scrambleRep(rep, scrambleBits);
+            return (unsigned long long) (((((rep - bucketBase) << idBits) | target) << DB) | (uint64_t) (diag + DiagPack<LONG>::BIAS));
+        };
+        // aggregate, one insert round of 64 records at a time; U = distinct keys so far (wave-uniform)
+        bool over = cnt > wa.capRecs;
+        uint32_t U = 0;
+        for (uint32_t i0 = 0; i0 < cnt && !over; i0 += 64 * AW_LOADS) {
+            const bool pre = i0 + 64 * AW_LOADS < cnt;
+            R rn[AW_LOADS];
+            if (pre) loadBatch(cur, i0 + 64 * AW_LOADS, rn);
+#pragma unroll
+            for (int u = 0; u < AW_LOADS; u++) {
+                bool fresh = false;
+                if (i0 + (uint32_t) (u * 64 + lane) < cnt && !isSentinel(r[u])) {
+                    uint32_t v; unsigned long long od; const unsigned long long key = packRec(r[u], v, od);
+                    uint32_t slot = (uint32_t) ((key * 0x9E3779B97F4A7C15ULL) >> 40) & (HT - 1);
+                    for (;;) {                     // at most capKeys + 64 < HT keys are in the table: a free slot exists
+                        const unsigned long long prev = atomicCAS(&hKey[slot], ~0ULL, key);
+                        if (prev == ~0ULL) { fresh = true; break; }
+                        if (prev == key) break;
+                        slot = (slot + 1) & (HT - 1);
+                    }
+                    atomicAdd(&hVal[slot], v);
+                    if (NUCL) atomicMax(&hOrd[slot], od);
+                }
+                U += (uint32_t) __popcll(__ballot(fresh));
+                if (U > wa.capKeys) { over = true; break; }
+            }
+            if (pre) {
+#pragma unroll
+                for (int u = 0; u < AW_LOADS; u++) r[u] = rn[u];
+            }
+        }
+        if (more) { cur = nxt; loadBatch(cur, 0, r); }
+        waveFence();
+        if (over) {
+            if (U) { for (uint32_t i = lane; i < HT; i += 64) { hKey[i] = ~0ULL; hVal[i] = 0; if (NUCL) hOrd[i] = 0; } waveFence(); }
+            if (lane == 0) wa.ovList[atomicAdd(wa.ovCount, 1u)] = b;
+            continue;
+        }
+        if (U == 0) { if (lane == 0) uniqueCount[b] = 0; continue; }
+        // compact the distinct keys to the list, then into registers: element e * 64 + lane in k[e], ~0 behind the U keys
+        uint32_t n = 0;
+        for (uint32_t s = 0; s < HT; s += 64) {
+            const unsigned long long kx = hKey[s + lane];
+            const bool occ = kx != ~0ULL;
+            const unsigned long long m = __ballot(occ);
+            if (occ) lKey[n + (uint32_t) __popcll(m & ((1ULL << lane) - 1ULL))] = kx;
+            n += (uint32_t) __popcll(m);
+        }
+        waveFence();
+        unsigned long long k[E];
+#pragma unroll
+        for (int e = 0; e < E; e++) { const uint32_t i = (uint32_t) (e * 64 + lane); k[e] = i < U ? lKey[i] : ~0ULL; }
+        const uint32_t nE = (U + 63) / 64;
+        if (nE <= 1) waveBitonic<1>(k);
+        else if (nE <= 2) waveBitonic<2>(k);
+        else if (nE <= 4) waveBitonic<4>(k);
+        else waveBitonic<8>(k);
+        // run heads per representative (the key's bits above target and diagonal), then every key's count (and rank word) from the table
+        const int RS = DB + idBits;
+        unsigned long long hm[E];
+        uint64_t prevTop = __shfl(k[0] >> RS, 0, 64);
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const uint32_t i = (uint32_t) (e * 64 + lane);
+            const uint64_t rp = k[e] >> RS, up = __shfl_up(rp, 1, 64);
+            const bool head = i < U && (i == 0 || (lane ? up : prevTop) != rp);
+            hm[e] = __ballot(head);
+            prevTop = __shfl(rp, 63, 64);
+        }
+        uint32_t after[E];                     // first run head behind element group e (U if none)
+        uint32_t nh = U;
+#pragma unroll
+        for (int e = E - 1; e >= 0; e--) { after[e] = nh; if (hm[e]) nh = (uint32_t) (e * 64) + (uint32_t) (__ffsll((long long) hm[e]) - 1); }
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const uint32_t i = (uint32_t) (e * 64 + lane);
+            if ((uint32_t) (e * 64) >= U) break;
+            if (i < U) {
+                const unsigned long long key = k[e];
+                uint32_t slot = (uint32_t) ((key * 0x9E3779B97F4A7C15ULL) >> 40) & (HT - 1);
+                while (hKey[slot] != key) slot = (slot + 1) & (HT - 1);
+                uint32_t val = hVal[slot]; unsigned long long od = 0;
+                if (NUCL) { od = hOrd[slot]; val |= (uint32_t) (od & 1ULL) << 31; hOrd[slot] = 0; }
+                hKey[slot] = ~0ULL; hVal[slot] = 0;   // (slots are cleared behind the lookups: a probe runs on until it meets its key)
+                O t;
+                t.diag = (int32_t) ((int64_t) (key & ((1ULL << DB) - 1)) - DiagPack<LONG>::BIAS);
+                const uint64_t k2 = key >> DB;
+                t.target = (uint32_t) (k2 & ((1ULL << idBits) - 1));
+                const uint64_t rp = (k2 >> idBits) + bucketBase;
+                t.rep = (uint32_t) ((scrambleBits ? scrambleRep(rp, scrambleBits) : rp) + repBase);
+                t.cnt = val;
+                if constexpr (ORDOUT) t.ord = od;
+                out[s0 + i] = t;
+                if ((hm[e] >> lane) & 1ULL) {
+                    const unsigned long long later = lane == 63 ? 0ULL : (hm[e] & ~((2ULL << lane) - 1ULL));
+                    const uint32_t end = later ? (uint32_t) (e * 64) + (uint32_t) (__ffsll((long long) later) - 1) : after[e];
+                    wa.repCnt[t.rep - (uint32_t) repBase] = end - i;
+                }
+            }
+        }
+        if (lane == 0) uniqueCount[b] = U;
+        waveFence();
+    }
+}
+
 // line-store path: the triples of bucket b lie at in[lineBeg[b] * RPL ...] (unique[b] of them), grouped by representative.  Every
 // representative occurs in exactly one bucket: the number of its triples and the position of the first go to cnt[rep - repBase] /
 // pos[rep - repBase] (cnt is zeroed beforehand).  One wavefront per bucket; a representative's triples are counted 64 at a time
 // (a long contig is the representative of 10^5..10^6 triples: neither a serial walk per run nor one atomic per triple would do).
 template <class T>
 __global__ __launch_bounds__(256) void repRunsKernel(const T *__restrict__ in, const uint32_t *__restrict__ lineBeg, const uint32_t *__restrict__ unique, uint32_t nBuckets,
-                                                     uint32_t repBase, uint32_t *__restrict__ cnt) {
-    for (uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6); b < nBuckets; b += gridDim.x * 4) {
+                                                     uint32_t repBase, uint32_t *__restrict__ cnt, const uint32_t *__restrict__ bList, const uint32_t *__restrict__ bListN) {
+    const uint32_t nB = bList ? *bListN : nBuckets;         // bList != nullptr: only the buckets bList[0 .. *bListN)
+    for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < nB; q += gridDim.x * 4) {
+        const uint32_t b = bList ? bList[q] : q;
         const uint64_t s0 = (uint64_t) lineBeg[b] * RPL; const uint32_t n = unique[b];
         for (uint32_t i0 = 0; i0 < n; i0 += 64) {
             const uint32_t i = i0 + laneId();
