@@ -11,8 +11,8 @@
 //       seqId has 3 truncated decimals ("1.00" for 1.0), alnLength = max(|qE-qS|,|tE-tS|)+1, score = bit score
 //
 // Kernel design: the queue of a query lives in registers, one alignment per lane — 16, 32 or 64 lanes per query by queue size
-// (assembleGroupKernel<16/32/64>; work lists by prefix sums after an exact pre-screen), an HBM-resident queue above 64 alignments
-// (assembleBigKernel, one wavefront per query).  A ROUND of the reference's pop loop is computed from the queued set: the comparator
+// (assembleGroupKernel<16/32/64>; work lists by prefix sums after an exact pre-screen), a compacted queue in LDS for 65..256 alignments
+// (assembleQueueKernel<128/256>, one wavefront per query) and an HBM-resident queue above that (assembleBigKernel).  A ROUND of the reference's pop loop is computed from the queued set: the comparator
 // is a strict total order, so std::priority_queue's pop order is "max of what is in the queue", the best right-extendable and the
 // best left-extendable hit (two arg-max reductions on a packed priority) are the round's two extensions, and every other hit is
 // dropped or deferred by the geometry tests with the final offsets, in parallel; deferred hits are re-scored by their own lane
@@ -53,6 +53,10 @@ struct AsmArgs {
     uint32_t ownLaneMin;                        // wide register queues: at least this many deferred hits of a round are re-scored each by its own lane, fewer one after the other by the whole group
     unsigned long long *stats;                  // [0] extended, [1] rescored hits, [2] rescored overlap residues
     uint32_t *bigList; uint32_t nBig;   // queries with more than 64 alignments (HBM-resident queue)
+    const uint32_t *bigCount;           // assembleBigKernel: number of queries on bigList in device memory (the on-chip queue kernel's overflow), or nullptr: nBig
+    uint32_t *overList; uint32_t *overCount;    // assembleQueueKernel: queries of more alignments than its cap, handed to assembleBigKernel
+    uint32_t queueCap;                          // assembleQueueKernel: run-time cap (PLASSHIP_TUNE_ASMQ_CAP), at most the kernel's CAP
+    uint32_t *dbgRounds; uint32_t *dbgCycles;   // PLASSHIP_DEBUG_ASMHIST: [n] rounds (| 1 << 31 if extended) and clock ticks of each big query, else nullptr
     uint32_t *midList; uint32_t nMid;   // 33..64 alignments: one wavefront per query
     uint32_t *mid32List; uint32_t nMid32;   // 17..32 alignments: half a wavefront per query
     uint32_t *smallList; uint32_t nSmall;                         // <= 16 alignments: 16 lanes per query
@@ -205,12 +209,14 @@ __device__ __forceinline__ void waveMemSync() {   // make this wave's global sto
 // Four wavefronts per workgroup share the 15 KB score table (one wavefront per workgroup let LDS cap the CU at 10 wavefronts); a
 // wavefront works on its own queries and orders its own memory operations with fences — there is no workgroup barrier in the loop.
 __global__ __launch_bounds__(256) void assembleBigKernel(AsmArgs a) {
+    const uint32_t nBig = a.bigCount ? *a.bigCount : a.nBig;
+    if (blockIdx.x * 4 >= nBig) return;                // (a list counted on the device: the grid is sized for all queries of more than 64 alignments)
     __shared__ signed char smat[123 * 123 + 7];
     stageScoreTable(smat, a.mat, 256);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     unsigned long long nExt = 0, nResc = 0, nRescRes = 0, nAln = 0, nQRes = 0;
-    for (uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6); w < a.nBig; w += gridDim.x * 4) {
+    for (uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6); w < nBig; w += gridDim.x * 4) {
         const uint32_t id = a.bigList[w];
         const uint64_t h0 = a.qoff[id], h1 = a.qoff[id + 1];
         const uint32_t h = (uint32_t) (h1 - h0);
@@ -221,6 +227,7 @@ __global__ __launch_bounds__(256) void assembleBigKernel(AsmArgs a) {
         const char *orig = a.s.data + seqOff(a.s, id);
         unsigned querySeqLen = seqLen(a.s, id);
         nAln += h; nQRes += querySeqLen;
+        const uint64_t t0 = a.dbgRounds ? (uint64_t) clock64() : 0; uint32_t rounds = 0;
         // ---- queue fill (assembleresult.cpp:161-189) ----
         for (uint32_t i = lane; i < h; i += 64) {
             const AlnRec r = a.recs[h0 + i];
@@ -250,6 +257,7 @@ __global__ __launch_bounds__(256) void assembleBigKernel(AsmArgs a) {
         while (inQueue > 0) {
             unsigned leftOff = 0, rightOff = 0;
             bool brokeOut = false;
+            rounds++;
             // ---- one round as a function of the set of queued hits (see assembleGroupKernel): best right-extendable and
             //      best left-extendable hit, then every popped hit classified with the final offsets ----
             unsigned long long bestR = 0, bestL = 0; uint32_t idxR = 0xFFFFFFFFu, idxL = 0xFFFFFFFFu;
@@ -378,7 +386,229 @@ __global__ __launch_bounds__(256) void assembleBigKernel(AsmArgs a) {
             if (lane == 0) { atomicOr(&a.flags[id], 0x20u); a.newLen[id] = (uint32_t) curLen; a.newStart[id] = aoff + curStart; }
             nExt++;
         }
+        if (a.dbgRounds && lane == 0) { a.dbgRounds[id] = rounds | (couldExtend ? 0x80000000u : 0u); a.dbgCycles[id] = (uint32_t) min<uint64_t>((uint64_t) clock64() - t0, 0xFFFFFFFFull); }
         waveMemSync();
+    }
+    nResc = waveReduceSumU64(nResc); nRescRes = waveReduceSumU64(nRescRes);        // counted per lane (every lane re-scores its own hits)
+    if (lane == 0) {
+        if (nExt) atomicAdd(&a.stats[0], nExt); if (nResc) atomicAdd(&a.stats[1], nResc); if (nRescRes) atomicAdd(&a.stats[2], nRescRes);
+        if (nAln) { atomicAdd(&a.stats[9], nAln); atomicAdd(&a.stats[10], nQRes); atomicAdd(&a.stats[11], nRescRes); }
+    }
+}
+
+// The queue of a query with 65..CAP alignments in LDS, one wavefront per query as in assembleBigKernel and the same rounds, but the queue is
+// filled once and kept COMPACTED: the records that were never queued are left out on the fill, every round keeps only its deferred hits
+// (ballot + prefix count, in place), and the re-scoring keeps only the hits that stay above the identity threshold, so that a round reads
+// what is still queued and nothing else.  The target's (offset, length) word is gathered once on the fill (for the hits that can take one of
+// the two branches: nobody else reads it).  The self hit stays queued like in assembleBigKernel.  The only global traffic of a round is the
+// extension's target bytes and the residues the deferred hits are re-scored against.  A query of more alignments goes onto overList
+// (assembleBigKernel runs that list after this kernel).  Wave-private LDS, no workgroup barrier in the loop.
+constexpr uint32_t ASMQ_CAP1 = 128, ASMQ_CAP = 256;       // queue capacities of the two assembleQueueKernel launches
+template <int CAP> struct QueueLds {     // structure of arrays: a sweep reads one word per lane and field
+    unsigned long long key[CAP];         // (score ^ sign bit) << 32 | alnLength: the comparator without its target-id tie-break
+    uint64_t offLen[CAP];                // the target's offset << 24 | length (SeqView::offLen)
+    uint32_t target[CAP], qLen[CAP], dbLen[CAP];
+    int32_t qStart[CAP], qEnd[CAP], dbStart[CAP], dbEnd[CAP];
+};
+struct QItem { unsigned long long key; uint64_t offLen; uint32_t target, qLen, dbLen; int32_t qStart, qEnd, dbStart, dbEnd; };
+template <int CAP> __device__ __forceinline__ QItem qLoad(const QueueLds<CAP> &q, uint32_t i) {
+    QItem x;
+    x.key = q.key[i]; x.offLen = q.offLen[i]; x.target = q.target[i]; x.qLen = q.qLen[i]; x.dbLen = q.dbLen[i];
+    x.qStart = q.qStart[i]; x.qEnd = q.qEnd[i]; x.dbStart = q.dbStart[i]; x.dbEnd = q.dbEnd[i];
+    return x;
+}
+template <int CAP> __device__ __forceinline__ void qStore(QueueLds<CAP> &q, uint32_t i, const QItem &x) {
+    q.key[i] = x.key; q.offLen[i] = x.offLen; q.target[i] = x.target; q.qLen[i] = x.qLen; q.dbLen[i] = x.dbLen;
+    q.qStart[i] = x.qStart; q.qEnd[i] = x.qEnd; q.dbStart[i] = x.dbStart; q.dbEnd[i] = x.dbEnd;
+}
+// the lanes with `keep` set store their items to base, base + 1, ... in lane order; returns the number kept.  In place: a chunk's items are
+// all in registers before any of them is stored, and a kept item never moves up.
+template <int CAP> __device__ __forceinline__ uint32_t qCompact(QueueLds<CAP> &q, uint32_t base, bool keep, const QItem &x) {
+    const unsigned long long m = __ballot(keep);
+    if (keep) qStore(q, base + (uint32_t) __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u)), x);
+    return (uint32_t) __popcll(m);
+}
+// orders this wave's LDS accesses across its lanes (the compiler keeps them in program order; the LDS serves a wave's accesses in order)
+__device__ __forceinline__ void queueFence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+__device__ __forceinline__ unsigned long long queueKey(int score, uint32_t alnLength) {
+    return ((unsigned long long) ((uint32_t) score ^ 0x80000000u) << 32) | (unsigned long long) alnLength;
+}
+
+template <int CAP, int WPE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void assembleQueueKernel(AsmArgs a) {
+    const uint32_t nBig = a.bigCount ? *a.bigCount : a.nBig;
+    if (blockIdx.x * 4 >= nBig) return;                // (a list counted on the device: the grid is sized for all queries of more than 64 alignments)
+    __shared__ signed char smat[123 * 123 + 7];
+    __shared__ QueueLds<CAP> queues[4];
+    stageScoreTable(smat, a.mat, 256);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    QueueLds<CAP> &q = queues[threadIdx.x >> 6];
+    unsigned long long nExt = 0, nResc = 0, nRescRes = 0, nAln = 0, nQRes = 0;
+    for (uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6); w < nBig; w += gridDim.x * 4) {
+        const uint32_t id = a.bigList[w];
+        const uint64_t h0 = a.qoff[id], h1 = a.qoff[id + 1];
+        const uint32_t h = (uint32_t) (h1 - h0);
+        if (h == 0) continue;
+        if (h > CAP || h > a.queueCap) {
+            if (lane == 0) a.overList[atomicAdd(a.overCount, 1u)] = id;
+            continue;
+        }
+        const uint64_t aoff = a.arenaOff[id];
+        if (a.arenaOff[id + 1] == aoff) continue;          // no non-self hit: can never be extended
+        const uint64_t qOffLen = a.s.offLen[id];
+        const char *orig = a.s.data + (qOffLen >> 24);
+        unsigned querySeqLen = (unsigned) ((uint32_t) qOffLen & 0xFFFFFFu);
+        nAln += h; nQRes += querySeqLen;
+        const uint64_t t0 = a.dbgRounds ? (uint64_t) clock64() : 0; uint32_t rounds = 0;
+        // ---- queue fill (assembleresult.cpp:161-189), same arithmetic as assembleBigKernel ----
+        uint32_t n = 0;
+        for (uint32_t b = 0; b < h; b += 64) {
+            const uint32_t i = b + (uint32_t) lane;
+            QItem x; bool keep = false;
+            if (i < h) {
+                const AlnRec r = a.recs[h0 + i];
+                x.target = r.target;
+                const int aq = (r.qStart == -1) ? 0 : r.qStart, ad = (r.dbStart == -1) ? 0 : r.dbStart;
+                const uint32_t alnLength = (uint32_t) (max(abs(r.qEnd - aq), abs(r.dbEnd - ad)) + 1);
+                const int rawScore = (int) (fma((double) r.bitScore, a.ln2, a.logK) / a.lambda + 0.5);
+                const float scorePerCol = (float) rawScore / (float) ((double) alnLength + 0.5);
+                x.key = queueKey((int) (scorePerCol * 100), alnLength);
+                x.qStart = r.qStart; x.qEnd = r.qEnd; x.qLen = (uint32_t) r.qLen; x.dbStart = r.dbStart; x.dbEnd = r.dbEnd; x.dbLen = (uint32_t) r.dbLen;
+                keep = r.accepted != 0;                                                     // a hole of a sparse list was never queued
+                const bool branchType = ((x.dbStart == 0 && x.dbEnd != (int) x.dbLen - 1) || (x.qStart == 0 && x.qEnd != (int) x.qLen - 1)) && !(x.dbStart == 0 && x.qStart == 0);
+                x.offLen = (keep && branchType && x.target != id) ? a.s.offLen[x.target] : 0;
+            }
+            n += qCompact(q, n, keep, x);
+        }
+        queueFence();
+        char *buf = a.arena + aoff;
+        uint64_t curStart = a.leftCap[id];
+        copyBytesG<64>(buf + curStart, orig, querySeqLen, lane);
+        uint64_t curLen = querySeqLen;
+        bool couldExtend = false;
+        while (n > 0) {
+            unsigned leftOff = 0, rightOff = 0;
+            bool brokeOut = false;
+            rounds++;
+            // ---- best right-extendable and best left-extendable hit (assembleBigKernel) ----
+            unsigned long long bestR = 0, bestL = 0; uint32_t idxR = 0xFFFFFFFFu, idxL = 0xFFFFFFFFu, tgtR = 0xFFFFFFFFu, tgtL = 0xFFFFFFFFu;
+            for (uint32_t i = lane; i < n; i += 64) {
+                const QItem x = qLoad(q, i);
+                const bool notBoth = !(x.dbStart == 0 && x.qStart == 0);
+                const bool rightStart = x.dbStart == 0 && (x.dbEnd != (int) x.dbLen - 1);
+                const bool leftStart = x.qStart == 0 && (x.qEnd != (int) x.qLen - 1);
+                if (!((rightStart || leftStart) && notBoth) || x.target == id) continue;
+                const unsigned tLen = (uint32_t) x.offLen & 0xFFFFFFu;
+                if (x.dbStart == 0) {
+                    const unsigned fragR = tLen - ((unsigned) x.dbEnd + 1);
+                    if (fragR > 0 && (unsigned) x.qEnd == (querySeqLen - 1) && (x.key > bestR || (x.key == bestR && x.target < tgtR))) { bestR = x.key; idxR = i; tgtR = x.target; }
+                } else if (x.qStart == 0) {
+                    if (x.dbStart > 0 && (unsigned) x.dbEnd == (tLen - 1) && (x.key > bestL || (x.key == bestL && x.target < tgtL))) { bestL = x.key; idxL = i; tgtL = x.target; }
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long okR = __shfl_xor(bestR, o, 64), okL = __shfl_xor(bestL, o, 64);
+                const uint32_t oiR = __shfl_xor(idxR, o, 64), oiL = __shfl_xor(idxL, o, 64), otR = __shfl_xor(tgtR, o, 64), otL = __shfl_xor(tgtL, o, 64);
+                if (oiR != 0xFFFFFFFFu && (idxR == 0xFFFFFFFFu || okR > bestR || (okR == bestR && otR < tgtR))) { bestR = okR; idxR = oiR; tgtR = otR; }
+                if (oiL != 0xFFFFFFFFu && (idxL == 0xFFFFFFFFu || okL > bestL || (okL == bestL && otL < tgtL))) { bestL = okL; idxL = oiL; tgtL = otL; }
+            }
+            const bool haveR = idxR != 0xFFFFFFFFu, haveL = idxL != 0xFFFFFFFFu;
+            const bool rFirst = haveR && (!haveL || bestR > bestL || (bestR == bestL && tgtR < tgtL));
+            auto extendRight = [&]() {
+                const uint64_t ol = q.offLen[idxR];
+                const unsigned tLen = (uint32_t) ol & 0xFFFFFFu, dbEnd = (unsigned) q.dbEnd[idxR], fragLen = tLen - (dbEnd + 1);
+                copyBytesG<64>(buf + curStart + curLen, a.s.data + (ol >> 24) + dbEnd + 1, fragLen, lane);
+                curLen += fragLen; rightOff += fragLen;
+                if (lane == 0) atomicOr(&a.flags[tgtR], 0x80u);
+            };
+            if (rFirst) extendRight();
+            if (haveL) {
+                const unsigned fragLen = (unsigned) q.dbStart[idxL];
+                if (curLen + fragLen >= a.maxSeqLen) brokeOut = true;
+                else {
+                    curStart -= fragLen;
+                    copyBytesG<64>(buf + curStart, a.s.data + (q.offLen[idxL] >> 24), fragLen, lane);
+                    curLen += fragLen; leftOff += fragLen;
+                    if (lane == 0) atomicOr(&a.flags[tgtL], 0x80u);
+                }
+            }
+            if (haveR && !rFirst && !brokeOut) extendRight();
+            if (leftOff > 0 || rightOff > 0) couldExtend = true;
+            queueFence();
+            if (brokeOut) {                                        // hits ranked below the left hit were never popped: they stay queued, the loop ends
+                uint32_t still = 0;
+                for (uint32_t i = lane; i < n; i += 64) {
+                    const unsigned long long key = q.key[i];
+                    still += (key < bestL || (key == bestL && q.target[i] > tgtL)) ? 1u : 0u;
+                }
+                if (waveReduceSum((int) still) > 0) break;
+            }
+            // ---- every queued hit was popped: used, dropped or deferred; the deferred ones are kept, compacted ----
+            uint32_t nd = 0;
+            for (uint32_t b = 0; b < n; b += 64) {
+                const uint32_t i = b + (uint32_t) lane;
+                QItem x; bool deferred = false;
+                if (i < n) {
+                    x = qLoad(q, i);
+                    const bool used = (i == idxR && (rFirst || !brokeOut)) || i == idxL;
+                    const bool notBoth = !(x.dbStart == 0 && x.qStart == 0);
+                    const bool rightStart = x.dbStart == 0 && (x.dbEnd != (int) x.dbLen - 1);
+                    const bool leftStart = x.qStart == 0 && (x.qEnd != (int) x.qLen - 1);
+                    if (!used && (rightStart || leftStart) && notBoth && x.target != id) {
+                        const unsigned tLen = (uint32_t) x.offLen & 0xFFFFFFu;
+                        if (x.dbStart == 0) deferred = (tLen - ((unsigned) x.dbEnd + 1)) > rightOff && (unsigned) x.qEnd == (querySeqLen - 1) && rightOff > 0;
+                        else if (x.qStart == 0) deferred = x.dbStart > (int) leftOff && (unsigned) x.dbEnd == (tLen - 1) && leftOff > 0;
+                    }
+                }
+                nd += qCompact(q, nd, deferred, x);
+            }
+            queueFence();
+            // ---- re-score the deferred hits on the extended query (assembleresult.cpp:288-313), every lane its own hit; the survivors
+            //      are the next round's queue ----
+            querySeqLen = (unsigned) curLen;
+            const char *qs = buf + curStart;
+            if (nd) waveMemSync();                                 // the extension bytes other lanes stored are read back below
+            uint32_t nn = 0;
+            for (uint32_t b = 0; b < nd; b += 64) {
+                const uint32_t i = b + (uint32_t) lane;
+                QItem x; bool keep = false;
+                if (i < nd) {
+                    x = qLoad(q, i);
+                    const char *tSeq = a.s.data + (x.offLen >> 24);
+                    const unsigned tLen = (uint32_t) x.offLen & 0xFFFFFFu;
+                    const int diag = (int) ((unsigned) x.qStart + leftOff) - x.dbStart;
+                    const unsigned dist = (unsigned) abs(diag);
+                    unsigned qo = 0, to = 0, len = 0; bool hit = true;
+                    if (diag >= 0 && dist < querySeqLen) { qo = dist; to = 0; len = min(tLen, querySeqLen - dist); }
+                    else if (diag < 0 && dist < tLen) { qo = 0; to = dist; len = min(tLen - dist, querySeqLen); }
+                    else hit = false;
+                    unsigned first = 0, last = 0; int sc = 0, ids = 0; int startPos = -1, endPos = -1;
+                    if (hit && len > 0) { scoreColumnsSerial(qs + qo, tSeq + to, len, smat, first, last, sc, ids); startPos = (int) first; endPos = (int) last; }
+                    const unsigned score = (unsigned) max(sc, 0);
+                    nResc++; nRescRes += hit ? len : 0;
+                    // updateAlignment
+                    int qS, qE, dS, dE;
+                    if (diag >= 0) { qS = startPos + (int) dist; qE = endPos + (int) dist; dS = startPos; dE = endPos; }
+                    else { qS = startPos; qE = endPos; dS = startPos + (int) dist; dE = endPos + (int) dist; }
+                    const float seqId = (float) ids / ((float) qE - (float) qS);
+                    const uint32_t alnLength = hit ? len : 0u;
+                    const float spc = (float) score / (float) ((double) alnLength + 0.5);
+                    x.key = queueKey((int) (spc * 100), alnLength); x.qLen = querySeqLen; x.dbLen = tLen;
+                    x.qStart = qS; x.qEnd = qE; x.dbStart = dS; x.dbEnd = dE;
+                    keep = seqId >= a.seqIdThr;
+                }
+                nn += qCompact(q, nn, keep, x);
+            }
+            queueFence();
+            n = nn;
+        }
+        if (couldExtend) {
+            if (lane == 0) { atomicOr(&a.flags[id], 0x20u); a.newLen[id] = (uint32_t) curLen; a.newStart[id] = aoff + curStart; }
+            nExt++;
+        }
+        if (a.dbgRounds && lane == 0) { a.dbgRounds[id] = rounds | (couldExtend ? 0x80000000u : 0u); a.dbgCycles[id] = (uint32_t) min<uint64_t>((uint64_t) clock64() - t0, 0xFFFFFFFFull); }
     }
     nResc = waveReduceSumU64(nResc); nRescRes = waveReduceSumU64(nRescRes);        // counted per lane (every lane re-scores its own hits)
     if (lane == 0) {
@@ -1769,6 +1999,41 @@ static int mergeExtended(plasship_ctx *ctx, uint32_t N, bool guided, int keepTar
     return PLASSHIP_OK;
 }
 
+// PLASSHIP_DEBUG_ASMHIST=1 (debug only, off by default): per assembleresults call, the queries of more than 64 alignments by queue size h
+// (queries, extended, rounds, share of the kernels' clock ticks) and by rounds per query, on stderr.  It waits for the stream.
+static bool asmHistOn() { return getenv("PLASSHIP_DEBUG_ASMHIST") != nullptr; }
+static int asmHistRecord(hipStream_t st, uint32_t N, const uint64_t *dQoff, const uint32_t *dBigList, uint32_t nBig, const uint32_t *dRounds, const uint32_t *dCycles,
+                         uint32_t cap) {
+    static int call = 0;
+    std::vector<uint32_t> ids(nBig), rounds(N), cycles(N);
+    std::vector<uint64_t> qoff((size_t) N + 1);
+    if (nBig) PH_COPY_SYNC(st, ids.data(), dBigList, (size_t) nBig * 4, hipMemcpyDeviceToHost);
+    PH_COPY_SYNC(st, qoff.data(), dQoff, ((size_t) N + 1) * 8, hipMemcpyDeviceToHost);
+    PH_COPY_SYNC(st, rounds.data(), dRounds, (size_t) N * 4, hipMemcpyDeviceToHost);
+    PH_COPY_SYNC(st, cycles.data(), dCycles, (size_t) N * 4, hipMemcpyDeviceToHost);
+    constexpr int NH = 5, NR = 8;                  // h: <= 128, <= 256, <= 512, <= 1024, more; rounds: 0, 1, 2, <= 4, ..., <= 32, more
+    uint64_t hq[NH] = {}, hx[NH] = {}, hr[NH] = {}, hc[NH] = {}, hm[NH] = {}, rq[NR] = {}, ct = 0, over = 0, maxH = 0;
+    for (uint32_t w = 0; w < nBig; w++) {
+        const uint32_t id = ids[w], h = (uint32_t) (qoff[id + 1] - qoff[id]), r = rounds[id] & 0x7FFFFFFFu;
+        int b = 0; while (b < NH - 1 && h > (128u << b)) b++;
+        int k = 0; if (r) { k = 1; uint32_t e = 1; while (k < NR - 1 && r > e) { e <<= 1; k++; } }
+        hq[b]++; hx[b] += rounds[id] >> 31; hr[b] += r; hm[b] = std::max<uint64_t>(hm[b], r); hc[b] += cycles[id]; ct += cycles[id];
+        rq[k]++; over += h > cap; maxH = std::max<uint64_t>(maxH, h);
+    }
+    std::string s = "asmHist call " + std::to_string(call++) + " big queries " + std::to_string(nBig) + " (max h " + std::to_string(maxH) + ", over cap " +
+                    std::to_string(cap) + ": " + std::to_string(over) + ") | h bins <=128,<=256,<=512,<=1024,more: queries/extended/mean rounds/max rounds/% ticks";
+    for (int b = 0; b < NH; b++) {
+        char t[96];
+        snprintf(t, sizeof(t), " [%llu %llu %.2f %llu %.1f%%]", (unsigned long long) hq[b], (unsigned long long) hx[b], hq[b] ? (double) hr[b] / hq[b] : 0.0,
+                 (unsigned long long) hm[b], ct ? 100.0 * hc[b] / ct : 0.0);
+        s += t;
+    }
+    s += " | rounds 0,1,2,<=4,<=8,<=16,<=32,more:";
+    for (int k = 0; k < NR; k++) s += " " + std::to_string(rq[k]);
+    fprintf(stderr, "%s\n", s.c_str());
+    return PLASSHIP_OK;
+}
+
 // aaDb == nullptr: assembleresults (protein DB) / nuclassembleresults (nucleotide DB); aaDb != nullptr: guidedassembleresults
 static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_seqdb *aaDb, const plasship_alns *al,
                         const plasship_assemble_params *par, plasship_seqdb **out, plasship_seqdb **outAa, plasship_assemble_stats *stats) {
@@ -1951,8 +2216,36 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     }
     PH_CHECK(hipEventRecord(ctx->ev[5], st));
     PH_CHECK(hipEventRecord(ctx->ev[6], st));
-    if (a.nBig) hipLaunchKernelGGL(assembleBigKernel, dim3(std::min<uint32_t>((a.nBig + 3) / 4, (uint32_t) ctx->numCU * (uint32_t) tuneInt("ASMBIG", 4))), dim3(256), 0, st, a);
+    DevBuf dDbgRounds, dDbgCycles;
+    const bool hist = asmHistOn() && a.nBig;
+    if (hist) {
+        if (dDbgRounds.alloc(((size_t) N + 1) * 4) != hipSuccess || dDbgCycles.alloc(((size_t) N + 1) * 4) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        PH_CHECK(hipMemsetAsync(dDbgRounds.p, 0, ((size_t) N + 1) * 4, st));
+        PH_CHECK(hipMemsetAsync(dDbgCycles.p, 0, ((size_t) N + 1) * 4, st));
+        a.dbgRounds = dDbgRounds.as<uint32_t>(); a.dbgCycles = dDbgCycles.as<uint32_t>();
+    }
+    // more than 64 alignments: the on-chip queue kernel up to its cap, assembleBigKernel (HBM-resident queue) for the queries above it, which the
+    // first kernel lists on the device (PLASSHIP_TUNE_ASMQ=2: assembleBigKernel for all of them; PLASSHIP_TUNE_ASMQ_CAP=n: a smaller cap)
+    const bool onChip = tuneInt("ASMQ", 1) != 2;
+    const uint32_t qCap = (uint32_t) std::max(0, std::min(tuneInt("ASMQ_CAP", (int) ASMQ_CAP), (int) ASMQ_CAP));
+    const dim3 gBig(std::min<uint32_t>((a.nBig + 3) / 4, (uint32_t) ctx->numCU * (uint32_t) tuneInt("ASMBIG", 4)));
+    DevBuf dOverList[2], dOverCount;
+    if (a.nBig && onChip) {
+        if (dOverList[0].alloc(((size_t) a.nBig + 1) * 4) != hipSuccess || dOverList[1].alloc(((size_t) a.nBig + 1) * 4) != hipSuccess || dOverCount.alloc(8) != hipSuccess) {
+            setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE;
+        }
+        PH_CHECK(hipMemsetAsync(dOverCount.p, 0, 8, st));
+        // up to 128 alignments (4 wavefronts per SIMD: 37 KB of LDS per workgroup), then the rest up to 256 (2 per SIMD: 59 KB), then the HBM-resident queue;
+        // each launch lists the queries above its cap for the next one.  The grid is what the CUs hold at once.
+        AsmArgs q1 = a; q1.overList = dOverList[0].as<uint32_t>(); q1.overCount = dOverCount.as<uint32_t>(); q1.queueCap = qCap;
+        hipLaunchKernelGGL((assembleQueueKernel<ASMQ_CAP1, 4>), dim3(std::min<uint32_t>((a.nBig + 3) / 4, (uint32_t) ctx->numCU * 4u)), dim3(256), 0, st, q1);
+        AsmArgs q2 = q1; q2.bigList = dOverList[0].as<uint32_t>(); q2.bigCount = dOverCount.as<uint32_t>(); q2.overList = dOverList[1].as<uint32_t>(); q2.overCount = dOverCount.as<uint32_t>() + 1;
+        hipLaunchKernelGGL((assembleQueueKernel<ASMQ_CAP, 2>), dim3(std::min<uint32_t>((a.nBig + 3) / 4, (uint32_t) ctx->numCU * 2u)), dim3(256), 0, st, q2);
+        AsmArgs o = a; o.bigList = dOverList[1].as<uint32_t>(); o.bigCount = dOverCount.as<uint32_t>() + 1;
+        hipLaunchKernelGGL(assembleBigKernel, gBig, dim3(256), 0, st, o);
+    } else if (a.nBig) hipLaunchKernelGGL(assembleBigKernel, gBig, dim3(256), 0, st, a);
     PH_CHECK(hipEventRecord(ctx->ev[7], st));
+    if (hist) { const int rcH = asmHistRecord(st, N, a.qoff, a.bigList, a.nBig, a.dbgRounds, a.dbgCycles, onChip ? qCap : 64); if (rcH) return rcH; }
     }
     PH_TRACE(st, "assemble: extension kernels");
     // ---- output DB(s): extended queries + carried-over sequences, in key order ----
