@@ -382,6 +382,41 @@ typedef struct plasship_merge_stats {
 int plasship_mergereads(plasship_ctx *ctx, const char *const *fastq, size_t n_files, const plasship_merge_params *par,
                         plasship_seqdb **reads, plasship_seqdb **headers, plasship_merge_stats *stats);
 
+/* ---- the workflows' tail: the contigs worth reporting, as a FASTA file
+ *      plasship_select_contigs replaces the `_only_assembled` index filters and createsubdb of data/assemble.sh:170-189 (with
+ *      --filter-proteins 0) and data/nuclassemble.sh:151-169 (FASTA mode); plasship_fasta_write replaces createhdb
+ *      (src/util/createhdb.cpp:45-58) and convert2fasta (lib/mmseqs/src/util/convert2fasta.cpp:41-56).  "Entry length" = sequence + "\n\0".
+ *        protein:    S1 = keys in `result` and `source` whose entry in `result` is longer; S2 = keys k of `result` whose entry on data-file line
+ *                    k — id k, the canonical layout — is "*", 'A'..'Z'*, "*" (assemble.sh:176 compares a line number with a key); S1 | S2.
+ *        nucleotide: only_extended: the keys of S1, else every key; then entry length > min_contig_len + 1.
+ *      `source` is the DB the chain started from (plass: aa_6f_start_long, the fragments before findassemblystart; penguin: the reads); only
+ *      its keys and lengths are read.  `cycles` (may be NULL) only counts the selected circular contigs here.  The result is an INDEX over
+ *      `result`'s bytes (no copy): free it before `result`.  It is an ordinary DB handle (write, download, fasta_write).
+ *      plasship_fasta_write: per entry in key order ">" <rank> " len:" <sequence length> [" cycle:" <0|1>] "\n" <sequence> "\n", the cycle
+ *      field when `cycles` is given (1 for the keys in it); an empty DB gives an empty file.  Written to "<path>.tmp.<pid>", renamed at the end.
+ *      ------------------------------------------------------------------------------------------------------------------------------- */
+#define PLASSHIP_SELECT_PROTEIN 0
+#define PLASSHIP_SELECT_NUCLEOTIDE 1
+typedef struct plasship_select_params {
+    int32_t mode;                 /* PLASSHIP_SELECT_PROTEIN | PLASSHIP_SELECT_NUCLEOTIDE                                              */
+    int32_t only_extended;        /* nucleotide: --contig-output-mode 1 (the default) keeps the extended contigs only, 0 keeps all      */
+    int64_t min_contig_len;       /* nucleotide: --min-contig-len (1000)                                                               */
+} plasship_select_params;
+typedef struct plasship_select_stats {
+    uint64_t n_selected;
+    uint64_t n_s1_only, n_s2_only, n_both;   /* protein: how the selected keys qualified (nucleotide: the extended ones count as S1)     */
+    uint64_t n_cycle;                        /* selected keys that are in `cycles`                                                      */
+    float ms_kernel;
+} plasship_select_stats;
+int plasship_select_contigs(plasship_ctx *ctx, const plasship_seqdb *result, const plasship_seqdb *source, const plasship_seqdb *cycles,
+                            const plasship_select_params *par, plasship_seqdb **out, plasship_select_stats *stats);
+typedef struct plasship_fasta_stats {
+    uint64_t n_entries, bytes, n_chunks;
+    float ms_kernel;              /* the size pass and the formatting of every chunk (HIP events)                                   */
+    float ms_total;               /* the whole call, file written and renamed                                                       */
+} plasship_fasta_stats;
+int plasship_fasta_write(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_seqdb *cycles, const char *path, plasship_fasta_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,19 @@ class MergeStats(C.Structure):
                 ("ms_parse", C.c_float), ("ms_upload", C.c_float), ("ms_kernel", C.c_float)]
 
 
+class _SelectParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("only_extended", C.c_int32), ("min_contig_len", C.c_int64)]
+
+
+class SelectStats(C.Structure):
+    _fields_ = [("n_selected", C.c_uint64), ("n_s1_only", C.c_uint64), ("n_s2_only", C.c_uint64), ("n_both", C.c_uint64),
+                ("n_cycle", C.c_uint64), ("ms_kernel", C.c_float)]
+
+
+class FastaStats(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("bytes", C.c_uint64), ("n_chunks", C.c_uint64), ("ms_kernel", C.c_float), ("ms_total", C.c_float)]
+
+
 class AlnRecord(C.Structure):
     _fields_ = [("query_key", C.c_uint32), ("target_key", C.c_uint32), ("bit_score", C.c_int32), ("raw_score", C.c_int32),
                 ("seq_id", C.c_float), ("q_start", C.c_int32), ("q_end", C.c_int32), ("q_len", C.c_int32),
@@ -161,6 +174,8 @@ SYMBOLS = [
     ("plasship_orfhdr_count", C.c_int, [P, C.POINTER(C.c_size_t)]),
     ("plasship_orfhdr_free", None, [P, P]),
     ("plasship_mergereads", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_MergeParams), C.POINTER(P), C.POINTER(P), C.POINTER(MergeStats)]),
+    ("plasship_select_contigs", C.c_int, [P, P, P, P, C.POINTER(_SelectParams), C.POINTER(P), C.POINTER(SelectStats)]),
+    ("plasship_fasta_write", C.c_int, [P, P, P, C.c_char_p, C.POINTER(FastaStats)]),
 ]
 # include/plasship_rccl.h (native RCCL communicator of a sharded run)
 RCCL_SYMBOLS = [
@@ -477,6 +492,23 @@ class Context:
         h = P(); hh = P(); st = MergeStats(); cp = (par or MergeParams())._c()
         _check(self.lib.plasship_mergereads(self.h, arr, len(paths), C.byref(cp), C.byref(h), C.byref(hh), C.byref(st)), "plasship_mergereads")
         return SeqDB(self, h), SeqDB(self, hh), st
+
+    def select_contigs(self, result, source, mode, cycles=None, only_extended=True, min_contig_len=1000):
+        """the workflows' `_only_assembled` selection (data/assemble.sh:170-189 with --filter-proteins 0, data/nuclassemble.sh:151-169)
+        -> (subset DB indexing `result`'s bytes, SelectStats); mode "protein" or "nucleotide"; free the subset before `result`"""
+        if mode not in ("protein", "nucleotide"):
+            raise ValueError("mode must be 'protein' or 'nucleotide'")
+        cp = _SelectParams(0 if mode == "protein" else 1, 1 if only_extended else 0, int(min_contig_len))
+        h = P(); st = SelectStats()
+        _check(self.lib.plasship_select_contigs(self.h, result.h, source.h, cycles.h if cycles is not None else None, C.byref(cp), C.byref(h), C.byref(st)),
+               "plasship_select_contigs")
+        return SeqDB(self, h), st
+
+    def write_fasta(self, db, path, cycles=None):
+        """createhdb + convert2fasta of `db` into the file `path` (with a " cycle:<0|1>" field when `cycles` is given) -> FastaStats"""
+        st = FastaStats()
+        _check(self.lib.plasship_fasta_write(self.h, db.h, cycles.h if cycles is not None else None, os.fsencode(str(path)), C.byref(st)), "plasship_fasta_write")
+        return st
 
     def synth_read_pairs(self, par):
         """synthetic read pairs generated in HBM (include/plasship_synth.h) -> nucleotide read DB"""

@@ -60,6 +60,9 @@ struct Flags {
     int orfMin = 30, orfMax = 32734, orfGaps = INT_MAX, contigStart = 2, contigEnd = 2, orfStart = 1, fwdFrames = 7, revFrames = 7;
     int translationTable = 1, translate = 0, allStarts = 0, addOrfStop = 0, preserveKeys = 0, takeLarger = 0;
     int numIterations = 0, fromReads = 0; std::string writeIntermediate; float seqIdThrNucl = 0.99f;
+    // the workflows' tail (--fasta-out): Assembler.cpp / Nuclassembler.cpp defaults (--filter-proteins 1, --min-contig-len 1000,
+    // --contig-output-mode 1)
+    std::string fastaOut; int filterProteins = 1, minContigLen = 1000, contigOutputMode = 1;
     std::set<std::string> seen;
 };
 
@@ -114,8 +117,9 @@ static const std::map<std::string, std::set<std::string>> &moduleFlags() {
         // guidedNuclAssemble.sh:77-126 with the DBs chained in HBM); flags = the workflow's own, defaults = the workflow's
         m["assemble-chain"] = {"--num-iterations", "--write-intermediate", "--from-reads", "-k", "--alph-size", "--kmer-per-seq", "--kmer-per-seq-scale", "--min-seq-id", "-e", "-c",
                                "--cov-mode", "--max-seq-len", "--keep-target", "--hash-shift", "--ignore-multi-kmer", "--rescore-mode", "--min-aln-len", "--seq-id-mode"};
-        m["nuclassemble-chain"] = m["assemble-chain"]; m["nuclassemble-chain"].insert("--chop-cycle");
         m["guidedassemble-chain"] = m["assemble-chain"];
+        m["nuclassemble-chain"] = m["assemble-chain"]; m["nuclassemble-chain"].insert({"--chop-cycle", "--fasta-out", "--min-contig-len", "--contig-output-mode"});
+        m["assemble-chain"].insert({"--fasta-out", "--filter-proteins", "--protein-filter-threshold"});
         m["mergereads"] = {};       // the reference's onlythreads set (plass.cpp:47, Parameters.cpp:301-303): --threads, -v
         for (auto &kv : m) kv.second.insert(common.begin(), common.end());
     }
@@ -142,6 +146,8 @@ int main(int argc, char **argv) {
                         "       plass-hip mergereads <i:r1.fastq[.gz]> <i:r2.fastq[.gz]> [<r1b> <r2b> …] <o:readDB>      (writes <o> and <o>_h)\n"
                         "       plass-hip assemble-chain <i:fragmentDB|readDB | r1.fastq r2.fastq …> <o:assemblyDB> [--num-iterations 12] [--from-reads 1] [--write-intermediate DIR]\n"
                         "       plass-hip nuclassemble-chain <i:nuclDB | r1.fastq r2.fastq …> <o:assemblyDB> [--num-iterations 8]        (writes <o>_cycle_<i> for circular contigs)\n"
+                        "       (assemble-chain --filter-proteins 0 / nuclassemble-chain [--min-contig-len 1000] [--contig-output-mode 1]: --fasta-out FILE writes the\n"
+                        "        selected contigs as FASTA, the workflows' tail, data/assemble.sh:159-201, data/nuclassemble.sh:138-207)\n"
                         "       plass-hip guidedassemble-chain <i:readDB | r1.fastq r2.fastq …> <o:nuclAssemblyDB> <o:aaAssemblyDB> [--num-iterations 5]\n"
                         "       (FASTQ pairs: merged on the GPU first, as the workflows' mergereads step, data/assemble.sh:27-38)\n");
         return EXIT_FAILURE;
@@ -183,6 +189,11 @@ int main(int argc, char **argv) {
         if (a == "-k") f.k = atoi(v.c_str());
         else if (a == "--num-iterations") { std::string t2; f.numIterations = atoi((multiParam(v, mod == "assemble-chain" || mod == "guidedassemble-chain" ? "aa" : "nucl", t2) ? t2 : v).c_str()); }
         else if (a == "--write-intermediate") f.writeIntermediate = v;
+        else if (a == "--fasta-out") f.fastaOut = v;
+        else if (a == "--filter-proteins") f.filterProteins = atoi(v.c_str());
+        else if (a == "--protein-filter-threshold") { /* filternoncoding's threshold: only read by the step --filter-proteins 1 runs */ }
+        else if (a == "--min-contig-len") f.minContigLen = atoi(v.c_str());
+        else if (a == "--contig-output-mode") f.contigOutputMode = atoi(v.c_str());
         else if (a == "--from-reads") f.fromReads = atoi(v.c_str());
         else if (a == "--alph-size") { if (multiParam(v, "aa", t)) f.alph = atoi(t.c_str()); }
         else if (a == "--kmer-per-seq") f.kps = atoi(v.c_str());
@@ -289,6 +300,15 @@ int main(int argc, char **argv) {
     for (const std::string &q : fastqIn) {
         if (q == "stdin") return unsupported("plass-hip %s: reading stdin is left to the reference\n", mod.c_str());
         if (q.size() >= 4 && q.compare(q.size() - 4, 4, ".bz2") == 0) return unsupported("plass-hip %s: bzip2 input (%s) is left to the reference\n", mod.c_str(), q.c_str());
+    }
+    // --fasta-out: the workflows' tail on the device (data/assemble.sh:159-201, nuclassemble.sh:138-207).  With --filter-proteins 1 (plass
+    // assemble's default) the tail selects from filternoncoding's output, a network with the reference's weights: not on this path.
+    if (!f.fastaOut.empty()) {
+        if (mod == "assemble-chain" && f.filterProteins != 0)
+            return unsupported("plass-hip assemble-chain: --fasta-out selects from filternoncoding's output with --filter-proteins 1; filternoncoding is outside the GPU path (pass --filter-proteins 0)\n");
+        if (mod == "nuclassemble-chain" && f.contigOutputMode != 0 && f.contigOutputMode != 1) { fprintf(stdout, "--contig-output-mode must be 0 or 1\n"); return EXIT_FAILURE; }
+        struct stat stF;
+        if (stat(f.fastaOut.c_str(), &stF) == 0) { fprintf(stdout, "%s exists already!\n", f.fastaOut.c_str()); return EXIT_FAILURE; }     // data/assemble.sh:23, nuclassemble.sh:69
     }
     if (getenv("PLASSHIP_CLI_DRYRUN") && atoi(getenv("PLASSHIP_CLI_DRYRUN")) != 0) {
         fprintf(stdout, "plass-hip dry run: %s accepted (%zu positional arguments, %zu flags); nothing read or computed\n", mod.c_str(), pos.size(), f.seen.size());
@@ -504,6 +524,10 @@ int main(int argc, char **argv) {
             fprintf(stdout, "%s: wrong input DB type %d\n", mod.c_str(), dbtype); return EXIT_FAILURE;
         }
         const double tPrep = now();
+        // the tail (--fasta-out) needs SOURCE — the DB the loop starts from (the reads; the fragments before findassemblystart: kept below) — and
+        // every iteration's circular contigs
+        const bool wantFasta = !f.fastaOut.empty();
+        plasship_seqdb *source = (wantFasta && nuc) ? db : nullptr, *cycAll = nullptr;
         plasship_rescore_params rp; memset(&rp, 0, sizeof(rp));
         rp.rescore_mode = f.rescoreMode; rp.eval_thr = f.evalThr; rp.seq_id_thr = f.seqIdThr; rp.cov_mode = f.covMode; rp.cov_thr = f.covThr; rp.min_aln_len = f.minAlnLen;
         rp.seq_id_mode = f.seqIdMode; rp.add_backtrace = gd ? 1 : 0;
@@ -523,7 +547,9 @@ int main(int argc, char **argv) {
             if (prot && it == 0) {         // data/assemble.sh:110-141: findassemblystart, then k-mer matching and re-scoring again on the corrected sequences
                 plasship_seqdb *corr = nullptr; plasship_findstart_stats fs;
                 if (K(plasship_find_assembly_start(ctx, db, al, &corr, &fs))) return fail(mod.c_str());
-                plasship_alns_free(ctx, al); plasship_cands_free(ctx, c); plasship_seqdb_free(ctx, db); db = corr; q = db;
+                plasship_alns_free(ctx, al); plasship_cands_free(ctx, c);
+                if (wantFasta) source = db; else plasship_seqdb_free(ctx, db);      // SOURCE of the tail: aa_6f_start_long, before the correction
+                db = corr; q = db;
                 if (K(plasship_kmermatch(ctx, q, &kp, &c, &ks)) || K(plasship_rescore(ctx, q, q, c, &rp, &al, &rs))) return fail(mod.c_str());
             }
             overlaps += ks.n_candidates; kernelMs += ks.ms_extract + ks.ms_sort1 + ks.ms_group + ks.ms_sort2 + ks.ms_reduce + rs.ms_kernel;
@@ -536,13 +562,19 @@ int main(int argc, char **argv) {
             kernelMs += as.ms_kernel;
             plasship_alns_free(ctx, al); plasship_cands_free(ctx, c);
             if (joinWriter()) { fprintf(stdout, "%s: writing an intermediate DB failed: %s\n", mod.c_str(), writerErr.c_str()); return EXIT_FAILURE; }   // the writer read `db`
-            plasship_seqdb_free(ctx, db); if (gd) plasship_seqdb_free(ctx, aa);
+            if (db != source) plasship_seqdb_free(ctx, db);
+            if (gd) plasship_seqdb_free(ctx, aa);
             db = next; aa = nextAa;
             if (nuc) {     // data/nuclassemble.sh:19-61,132: circular contigs leave the loop, the rest goes on
                 plasship_seqdb *cyc = nullptr, *rest = nullptr; plasship_cyclecheck_params cp; cp.max_seq_len = f.maxSeqLen; cp.chop_cycle = f.chopCycle; plasship_cyclecheck_stats cs;
                 if (K(plasship_cyclecheck(ctx, db, &cp, &cyc, &rest, &cs))) return fail(mod.c_str());
                 if (cs.n_cyclic && KW(plasship_seqdb_write(ctx, cyc, (outs[0] + "_cycle_" + std::to_string(it)).c_str()))) return fail(mod.c_str());
-                plasship_seqdb_free(ctx, cyc); plasship_seqdb_free(ctx, db); db = rest;
+                if (wantFasta && cs.n_cyclic) {       // PREV_CYCLE_ALL: every iteration's circular contigs (nuclassemble.sh:35-41, concatdbs --preserve-keys)
+                    if (!cycAll) { cycAll = cyc; cyc = nullptr; }
+                    else { plasship_seqdb *u = nullptr; if (K(plasship_seqdb_concat_keys(ctx, cycAll, cyc, 1, &u))) return fail(mod.c_str()); plasship_seqdb_free(ctx, cycAll); cycAll = u; }
+                }
+                if (cyc) plasship_seqdb_free(ctx, cyc);
+                plasship_seqdb_free(ctx, db); db = rest;
             }
             fprintf(stdout, "iteration %d: candidates %llu verified %llu extended %llu (%.3f s since the DB was read)\n", it, (unsigned long long) ks.n_candidates, (unsigned long long) rs.n_accepted, (unsigned long long) as.n_extended, now() - tPrep);
             if (it + 1 < f.numIterations) writeAsync(db, (gd ? "assembly_nucl_" : "assembly_") + std::to_string(it));
@@ -550,6 +582,23 @@ int main(int argc, char **argv) {
         const double tLoop = now();
         if (joinWriter()) { fprintf(stdout, "%s: writing an intermediate DB failed: %s\n", mod.c_str(), writerErr.c_str()); return EXIT_FAILURE; }
         if (KW(plasship_seqdb_write(ctx, db, outs[0].c_str())) || (gd && KW(plasship_seqdb_write(ctx, aa, outs[1].c_str())))) return fail(mod.c_str());
+        if (wantFasta) {
+            // RESULT: the last assembly, or (nucleotide, circular contigs found) the non-circular rest + every circular contig (nuclassemble.sh:140-148)
+            plasship_seqdb *result = db, *merged = nullptr, *sel = nullptr;
+            if (cycAll) { if (K(plasship_seqdb_concat_keys(ctx, db, cycAll, 1, &merged))) return fail(mod.c_str()); result = merged; }
+            plasship_select_params sp; memset(&sp, 0, sizeof(sp));
+            sp.mode = nuc ? PLASSHIP_SELECT_NUCLEOTIDE : PLASSHIP_SELECT_PROTEIN; sp.only_extended = f.contigOutputMode == 1; sp.min_contig_len = f.minContigLen;
+            plasship_select_stats ss; plasship_fasta_stats fs;
+            if (!source) { fprintf(stdout, "%s: --fasta-out needs the fragment DB before findassemblystart\n", mod.c_str()); return EXIT_FAILURE; }
+            if (K(plasship_select_contigs(ctx, result, source, cycAll, &sp, &sel, &ss))) return fail(mod.c_str());
+            size_t nResult = 0; plasship_seqdb_info(result, &nResult, nullptr, nullptr, nullptr, nullptr);
+            if (KW(plasship_fasta_write(ctx, sel, cycAll, f.fastaOut.c_str(), &fs))) return fail(mod.c_str());
+            fprintf(stdout, "fasta: %llu of %zu contigs selected (S1 only %llu, S2 only %llu, both %llu, circular %llu), %llu bytes | select %.3f ms, format %.3f ms, file %.3f s\n",
+                    (unsigned long long) ss.n_selected, nResult, (unsigned long long) ss.n_s1_only, (unsigned long long) ss.n_s2_only,
+                    (unsigned long long) ss.n_both, (unsigned long long) ss.n_cycle, (unsigned long long) fs.bytes, ss.ms_kernel, fs.ms_kernel, fs.ms_total * 1e-3);
+            plasship_seqdb_free(ctx, sel); if (merged) plasship_seqdb_free(ctx, merged); if (cycAll) plasship_seqdb_free(ctx, cycAll);
+            plasship_seqdb_free(ctx, source);
+        }
         const double tEnd = now();
         fprintf(stdout, "chain: %d iterations, %llu candidate overlaps | read %.3fs preprocessing %.3fs iterations %.3fs (kernels %.3fs) write %.3fs\n", f.numIterations, overlaps,
                 tRead - t0, tPrep - tRead, tLoop - tPrep, kernelMs * 1e-3, tEnd - tLoop);

@@ -198,7 +198,9 @@ struct plasship_seqdb {
     std::shared_ptr<plasship::SeqHeap> heap;
     bool contiguous = true;
     uint64_t buildAppendedBytes = 0, buildCopiedBytes = 0;  // how buildOutputDB made this DB: bytes appended to the shared heap / bytes of a full copy
-    const char *dataPtr() const { return heap ? heap->buf.as<char>() : d_data.as<char>(); }
+    // a subset (plasship_select_contigs) of a DB without a heap indexes that DB's own buffer, which must outlive it
+    const char *borrowedData = nullptr;
+    const char *dataPtr() const { return heap ? heap->buf.as<char>() : borrowedData ? borrowedData : d_data.as<char>(); }
     // rank of every entry in DATA FILE order (empty: the file lay in key order, rank == id).  Only DBs read from files written by
     // several threads have one; concatdbs renumbers its second DB by it (DBConcat.cpp:46-47,113-118 opens it LINEAR_ACCCESS).
     plasship::DevBuf d_fileRank;
