@@ -417,6 +417,28 @@ typedef struct plasship_fasta_stats {
 } plasship_fasta_stats;
 int plasship_fasta_write(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_seqdb *cycles, const char *path, plasship_fasta_stats *stats);
 
+/* ---- the workflows' --db-mode end: the selected contigs as a DB of their own
+ *      plasship_subdb_write replaces `createsubdb <list> <RESULT> <out> --subdb-mode 0` (data/nuclassemble.sh:170-172;
+ *      lib/mmseqs/src/util/createsubdb.cpp:41-92), the `assembly_cycle.index` filter behind it (nuclassemble.sh:173-175) and the two moves
+ *      of db-mode (nuclassemble.sh:200-206): `penguin nuclassemble --db-mode 1`, and through it the end of `penguin guided_nuclassemble`
+ *      (data/guidedNuclAssemble.sh:167-170; GuidedNuclassembler.cpp:167-174 passes --db-mode 1).
+ *      `db` is a subset made by plasship_select_contigs (any DB handle will do).  Its entries are gathered on the device, back to back in the
+ *      handle's order — key order, the order of the `_only_assembled_filtered.index` list — and written as <path>, <path>.index and
+ *      <path>.dbtype: keys kept, offsets running, lengths the entry lengths.  No header DB and no FASTA file are written, as in db-mode.
+ *      `cycles` (may be NULL) = every circular contig the chain found (PREV_CYCLE_ALL): then <path>_cycle.index holds the lines of
+ *      <path>.index whose key is in it (the file exists whenever `cycles` is given, with or without lines).
+ *      The guided chain's `_only_assembled` rule (data/guidedNuclAssemble.sh:136-139: keys in both RESULT and SOURCE with `$3 > $6`, no length
+ *      threshold) needs no mode of its own: it is PLASSHIP_SELECT_NUCLEOTIDE with only_extended = 1 and min_contig_len = 0 (every entry
+ *      length is >= 2 > 0 + 1).
+ *      ------------------------------------------------------------------------------------------------------------------------------- */
+typedef struct plasship_subdb_stats {
+    uint64_t n_entries, bytes;    /* of the DB written                                                                              */
+    uint64_t n_cycle;             /* lines of <path>_cycle.index                                                                    */
+    float ms_kernel;              /* the prefix sum and the gather (HIP events)                                                     */
+    float ms_total;               /* the whole call, files written and renamed                                                      */
+} plasship_subdb_stats;
+int plasship_subdb_write(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_seqdb *cycles, const char *path, plasship_subdb_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,10 @@ class FastaStats(C.Structure):
     _fields_ = [("n_entries", C.c_uint64), ("bytes", C.c_uint64), ("n_chunks", C.c_uint64), ("ms_kernel", C.c_float), ("ms_total", C.c_float)]
 
 
+class SubdbStats(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("bytes", C.c_uint64), ("n_cycle", C.c_uint64), ("ms_kernel", C.c_float), ("ms_total", C.c_float)]
+
+
 class AlnRecord(C.Structure):
     _fields_ = [("query_key", C.c_uint32), ("target_key", C.c_uint32), ("bit_score", C.c_int32), ("raw_score", C.c_int32),
                 ("seq_id", C.c_float), ("q_start", C.c_int32), ("q_end", C.c_int32), ("q_len", C.c_int32),
@@ -176,6 +180,7 @@ SYMBOLS = [
     ("plasship_mergereads", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_MergeParams), C.POINTER(P), C.POINTER(P), C.POINTER(MergeStats)]),
     ("plasship_select_contigs", C.c_int, [P, P, P, P, C.POINTER(_SelectParams), C.POINTER(P), C.POINTER(SelectStats)]),
     ("plasship_fasta_write", C.c_int, [P, P, P, C.c_char_p, C.POINTER(FastaStats)]),
+    ("plasship_subdb_write", C.c_int, [P, P, P, C.c_char_p, C.POINTER(SubdbStats)]),
 ]
 # include/plasship_rccl.h (native RCCL communicator of a sharded run)
 RCCL_SYMBOLS = [
@@ -509,6 +514,63 @@ class Context:
         st = FastaStats()
         _check(self.lib.plasship_fasta_write(self.h, db.h, cycles.h if cycles is not None else None, os.fsencode(str(path)), C.byref(st)), "plasship_fasta_write")
         return st
+
+    def write_subdb(self, db, path, cycles=None):
+        """`createsubdb --subdb-mode 0` of a selection (data/nuclassemble.sh:170-176, 200-207): its entries gathered on the device and written
+        as `path`, `path`.index, `path`.dbtype, plus `path`_cycle.index (the index lines of the keys in `cycles`) when `cycles` is given
+        -> SubdbStats"""
+        st = SubdbStats()
+        _check(self.lib.plasship_subdb_write(self.h, db.h, cycles.h if cycles is not None else None, os.fsencode(str(path)), C.byref(st)), "plasship_subdb_write")
+        return st
+
+    def nuclassemble_db(self, db, path, num_iterations=8, k=22, min_seq_id=0.99, min_aln_len=0, max_seq_len=200000, chop_cycle=True,
+                        only_extended=True, min_contig_len=1000):
+        """`penguin nuclassemble --db-mode 1` on a resident nucleotide DB (data/nuclassemble.sh:95-207): the loop with cyclecheck after every
+        iteration, RESULT = the rest + every circular contig, the `_only_assembled` and --min-contig-len selection against `db`, written with
+        write_subdb -> (SelectStats, SubdbStats).  `db` stays the caller's."""
+        km = KmermatchParams(k=k, kmer_per_seq_scale=0.1, include_only_extendable=True)
+        rs = RescoreParams(min_seq_id=min_seq_id, min_aln_len=min_aln_len)
+        asp = AssembleParams(min_seq_id=min_seq_id, max_seq_len=max_seq_len)
+        cur, cyc_all = db, None
+        for _ in range(num_iterations):
+            c, _s = self.kmermatcher(cur, km)
+            a, _s = self.rescorediagonal(cur, cur, c, rs)
+            nxt, _s = self.assembleresults(cur, a, asp)
+            a.free(); c.free()
+            if cur is not db:
+                cur.free()
+            cyc, cur, cs = self.cyclecheck(nxt, max_seq_len=max_seq_len, chop_cycle=chop_cycle, with_rest=True)
+            nxt.free()
+            if cs.n_cyclic and cyc_all is None:
+                cyc_all, cyc = cyc, None
+            elif cs.n_cyclic:
+                u = self.concatdbs(cyc_all, cyc, preserve_keys=True)
+                cyc_all.free(); cyc_all = u
+            if cyc is not None:
+                cyc.free()
+        result = self.concatdbs(cur, cyc_all, preserve_keys=True) if cyc_all is not None else cur
+        sel, ss = self.select_contigs(result, db, "nucleotide", cycles=cyc_all, only_extended=only_extended, min_contig_len=min_contig_len)
+        ds = self.write_subdb(sel, path, cycles=cyc_all)
+        sel.free()
+        if result is not cur:
+            result.free()
+        if cur is not db:
+            cur.free()
+        if cyc_all is not None:
+            cyc_all.free()
+        return ss, ds
+
+    def guided_tail(self, nucl_result, nucl_source, reads, path, **nucl_par):
+        """what `penguin guided_nuclassemble` does behind its guided loop, up to linclust (data/guidedNuclAssemble.sh:135-170): the extended
+        ORFs of `nucl_result` (keys of `nucl_source` = nucl_6f_start_long whose entry grew, `$3 > $6`) concatenated with `reads`, then
+        nuclassemble_db(merged, path, **nucl_par) -> (SelectStats, SubdbStats).  The three DBs stay the caller's."""
+        only, _s = self.select_contigs(nucl_result, nucl_source, "nucleotide", only_extended=True, min_contig_len=0)
+        merged = self.concatdbs(only, reads)
+        only.free()
+        try:
+            return self.nuclassemble_db(merged, path, **nucl_par)
+        finally:
+            merged.free()
 
     def synth_read_pairs(self, par):
         """synthetic read pairs generated in HBM (include/plasship_synth.h) -> nucleotide read DB"""

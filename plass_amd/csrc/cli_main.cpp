@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <set>
 #include <string>
@@ -63,6 +64,9 @@ struct Flags {
     // the workflows' tail (--fasta-out): Assembler.cpp / Nuclassembler.cpp defaults (--filter-proteins 1, --min-contig-len 1000,
     // --contig-output-mode 1)
     std::string fastaOut; int filterProteins = 1, minContigLen = 1000, contigOutputMode = 1;
+    // the workflows' --db-mode end (nuclassemble.sh:200-207): nuclassemble-chain --db-mode 1 --db-out DB, and the nested nuclassemble of
+    // guidedassemble-chain --nuclassembly-out DB with the nucleotide halves of the multi-parameters (GuidedNuclassembler.cpp:10-14,167-174)
+    std::string dbOut, nuclAssemblyOut; int dbMode = 0, numIterationsNucl = 5, kNucl = 22, minAlnLenNucl = 0;
     std::set<std::string> seen;
 };
 
@@ -93,6 +97,107 @@ static int fail(const char *what) {
 }
 static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// ---- the iteration loop of a workflow script (data/assemble.sh:85-156, nuclassemble.sh:95-137, guidedNuclAssemble.sh:77-126) with every DB of
+//      the loop resident in HBM.  One function for the three drivers and for the nuclassemble that guidedassemble-chain --nuclassembly-out
+//      runs on the merged DB (guidedNuclAssemble.sh:167-170). ----
+enum ChainKind { CHAIN_PROTEIN, CHAIN_NUCL, CHAIN_GUIDED };
+struct ChainLoop {
+    plasship_ctx *ctx = nullptr; const char *name = ""; ChainKind kind = CHAIN_PROTEIN;
+    int numIterations = 1, k = 0, alph = 13, kps = 60, ignoreMulti = 1, covMode = 0, hashShift = 67, gapOpenNucl = 5, gapExtendNucl = 2, chopCycle = 1;
+    float kpsScale = 0.0f, covThr = 0.0f; unsigned long long maxSeqLen = 65535;
+    plasship_rescore_params rp; plasship_assemble_params ap;
+    bool keepForTail = false;            // keep SOURCE and every iteration's circular contigs: a tail follows
+    std::string cyclePrefix;             // nucleotide: circular contigs of iteration i are written to <cyclePrefix><i> ("": they are not)
+    std::string intermediateName;        // --write-intermediate: "assembly_" / "assembly_nucl_" ("": nothing is written)
+    std::function<int()> joinWriter; std::function<void(const plasship_seqdb *, const std::string &)> writeAsync;
+    // in: the DB(s) the loop starts from; out: the last iteration's
+    plasship_seqdb *db = nullptr, *aa = nullptr;
+    plasship_seqdb *source = nullptr, *cycAll = nullptr;       // keepForTail: SOURCE of the tail, PREV_CYCLE_ALL (nullptr: no circular contig)
+    unsigned long long overlaps = 0; double kernelMs = 0, tStart = 0;
+};
+static int runChainLoop(ChainLoop &L) {
+    plasship_ctx *ctx = L.ctx;
+    const bool prot = L.kind == CHAIN_PROTEIN, nuc = L.kind == CHAIN_NUCL, gd = L.kind == CHAIN_GUIDED;
+    plasship_seqdb *&db = L.db, *&aa = L.aa, *&source = L.source, *&cycAll = L.cycAll;
+    // SOURCE is the DB the loop starts from (the reads; the guided chain's nucl_6f_start_long; the fragments before findassemblystart: kept below)
+    if (L.keepForTail && !prot) source = db;
+    int hashShift = L.hashShift;
+    for (int it = 0; it < L.numIterations; it++) {
+        plasship_kmermatch_params kp; memset(&kp, 0, sizeof(kp));
+        kp.kmer_size = L.k; kp.alphabet_size = L.alph; kp.kmers_per_seq = L.kps; kp.kmers_per_seq_scale = L.kpsScale; kp.ignore_multi_kmer = L.ignoreMulti;
+        kp.cov_mode = L.covMode; kp.cov_thr = L.covThr;
+        // plass assemble: --hash-shift grows with every second iteration, iteration 0 keeps non-extendable matches (Assembler.cpp:99-110)
+        if (prot) { hashShift += it % 2; kp.hash_shift = hashShift; kp.include_only_extendable = it > 0; } else { kp.hash_shift = L.hashShift; kp.include_only_extendable = 1; }
+        plasship_seqdb *q = gd ? aa : db;
+        plasship_cands *c = nullptr; plasship_alns *al = nullptr; plasship_kmermatch_stats ks; plasship_rescore_stats rs; plasship_assemble_stats as;
+        if (K(plasship_kmermatch(ctx, q, &kp, &c, &ks)) || K(plasship_rescore(ctx, q, q, c, &L.rp, &al, &rs))) return fail(L.name);
+        if (prot && it == 0) {         // data/assemble.sh:110-141: findassemblystart, then k-mer matching and re-scoring again on the corrected sequences
+            plasship_seqdb *corr = nullptr; plasship_findstart_stats fs;
+            if (K(plasship_find_assembly_start(ctx, db, al, &corr, &fs))) return fail(L.name);
+            plasship_alns_free(ctx, al); plasship_cands_free(ctx, c);
+            if (L.keepForTail) source = db; else plasship_seqdb_free(ctx, db);      // SOURCE of the tail: aa_6f_start_long, before the correction
+            db = corr; q = db;
+            if (K(plasship_kmermatch(ctx, q, &kp, &c, &ks)) || K(plasship_rescore(ctx, q, q, c, &L.rp, &al, &rs))) return fail(L.name);
+        }
+        L.overlaps += ks.n_candidates; L.kernelMs += ks.ms_extract + ks.ms_sort1 + ks.ms_group + ks.ms_sort2 + ks.ms_reduce + rs.ms_kernel;
+        plasship_seqdb *next = nullptr, *nextAa = nullptr;
+        if (gd) {
+            plasship_alns *na = nullptr; plasship_aln2nucl_params np; np.gap_open = L.gapOpenNucl; np.gap_extend = L.gapExtendNucl; plasship_aln2nucl_stats ns;
+            if (K(plasship_aln2nucl(ctx, db, db, aa, aa, al, &np, &na, &ns)) || K(plasship_guided_assemble(ctx, db, aa, na, &L.ap, &next, &nextAa, &as))) return fail(L.name);
+            plasship_alns_free(ctx, na);
+        } else if (K(plasship_assemble(ctx, db, al, &L.ap, &next, &as))) return fail(L.name);
+        L.kernelMs += as.ms_kernel;
+        plasship_alns_free(ctx, al); plasship_cands_free(ctx, c);
+        if (L.joinWriter && L.joinWriter()) return EXIT_FAILURE;   // the writer read `db` (the caller's joinWriter prints the message)
+        if (db != source) plasship_seqdb_free(ctx, db);
+        if (gd) plasship_seqdb_free(ctx, aa);
+        db = next; aa = nextAa;
+        if (nuc) {     // data/nuclassemble.sh:19-61,132: circular contigs leave the loop, the rest goes on
+            plasship_seqdb *cyc = nullptr, *rest = nullptr; plasship_cyclecheck_params cp; cp.max_seq_len = L.maxSeqLen; cp.chop_cycle = L.chopCycle; plasship_cyclecheck_stats cs;
+            if (K(plasship_cyclecheck(ctx, db, &cp, &cyc, &rest, &cs))) return fail(L.name);
+            if (cs.n_cyclic && !L.cyclePrefix.empty() && KW(plasship_seqdb_write(ctx, cyc, (L.cyclePrefix + std::to_string(it)).c_str()))) return fail(L.name);
+            if (L.keepForTail && cs.n_cyclic) {       // PREV_CYCLE_ALL: every iteration's circular contigs (nuclassemble.sh:35-41, concatdbs --preserve-keys)
+                if (!cycAll) { cycAll = cyc; cyc = nullptr; }
+                else { plasship_seqdb *u = nullptr; if (K(plasship_seqdb_concat_keys(ctx, cycAll, cyc, 1, &u))) return fail(L.name); plasship_seqdb_free(ctx, cycAll); cycAll = u; }
+            }
+            if (cyc) plasship_seqdb_free(ctx, cyc);
+            plasship_seqdb_free(ctx, db); db = rest;
+        }
+        fprintf(stdout, "iteration %d: candidates %llu verified %llu extended %llu (%.3f s since the DB was read)\n", it, (unsigned long long) ks.n_candidates, (unsigned long long) rs.n_accepted, (unsigned long long) as.n_extended, now() - L.tStart);
+        if (it + 1 < L.numIterations && L.writeAsync && !L.intermediateName.empty()) L.writeAsync(db, L.intermediateName + std::to_string(it));
+    }
+    return EXIT_SUCCESS;
+}
+// ---- the workflows' tail on the last DB of a loop (data/assemble.sh:159-201, nuclassemble.sh:138-207): RESULT, the `_only_assembled` selection,
+//      then FASTA (fastaOut) or, in db-mode, the DB of the selected contigs and its cycle index (dbOut).  Frees source and cycAll. ----
+static int chainTail(plasship_ctx *ctx, const char *name, bool nuc, plasship_seqdb *db, plasship_seqdb *source, plasship_seqdb *cycAll,
+                     int contigOutputMode, int minContigLen, const std::string &fastaOut, const std::string &dbOut) {
+    // RESULT: the last assembly, or (nucleotide, circular contigs found) the non-circular rest + every circular contig (nuclassemble.sh:140-148)
+    plasship_seqdb *result = db, *merged = nullptr, *sel = nullptr;
+    if (cycAll) { if (K(plasship_seqdb_concat_keys(ctx, db, cycAll, 1, &merged))) return fail(name); result = merged; }
+    plasship_select_params sp; memset(&sp, 0, sizeof(sp));
+    sp.mode = nuc ? PLASSHIP_SELECT_NUCLEOTIDE : PLASSHIP_SELECT_PROTEIN; sp.only_extended = contigOutputMode == 1; sp.min_contig_len = minContigLen;
+    plasship_select_stats ss;
+    if (!source) { fprintf(stdout, "%s: the tail needs the fragment DB before findassemblystart\n", name); return EXIT_FAILURE; }
+    if (K(plasship_select_contigs(ctx, result, source, cycAll, &sp, &sel, &ss))) return fail(name);
+    size_t nResult = 0; plasship_seqdb_info(result, &nResult, nullptr, nullptr, nullptr, nullptr);
+    if (!fastaOut.empty()) {
+        plasship_fasta_stats fs;
+        if (KW(plasship_fasta_write(ctx, sel, cycAll, fastaOut.c_str(), &fs))) return fail(name);
+        fprintf(stdout, "fasta: %llu of %zu contigs selected (S1 only %llu, S2 only %llu, both %llu, circular %llu), %llu bytes | select %.3f ms, format %.3f ms, file %.3f s\n",
+                (unsigned long long) ss.n_selected, nResult, (unsigned long long) ss.n_s1_only, (unsigned long long) ss.n_s2_only,
+                (unsigned long long) ss.n_both, (unsigned long long) ss.n_cycle, (unsigned long long) fs.bytes, ss.ms_kernel, fs.ms_kernel, fs.ms_total * 1e-3);
+    } else {
+        plasship_subdb_stats ds;
+        if (KW(plasship_subdb_write(ctx, sel, cycAll, dbOut.c_str(), &ds))) return fail(name);
+        fprintf(stdout, "db-mode: %llu of %zu contigs selected (circular %llu), %llu bytes | select %.3f ms, gather %.3f ms, files %.3f s\n",
+                (unsigned long long) ss.n_selected, nResult, (unsigned long long) ds.n_cycle, (unsigned long long) ds.bytes, ss.ms_kernel, ds.ms_kernel, ds.ms_total * 1e-3);
+    }
+    plasship_seqdb_free(ctx, sel); if (merged) plasship_seqdb_free(ctx, merged); if (cycAll) plasship_seqdb_free(ctx, cycAll);
+    plasship_seqdb_free(ctx, source);
+    return EXIT_SUCCESS;
+}
+
 // which flags a module owns (its parameter vector in the reference)
 static const std::map<std::string, std::set<std::string>> &moduleFlags() {
     static const std::set<std::string> common = {"--threads", "-v", "--compressed"};
@@ -118,7 +223,9 @@ static const std::map<std::string, std::set<std::string>> &moduleFlags() {
         m["assemble-chain"] = {"--num-iterations", "--write-intermediate", "--from-reads", "-k", "--alph-size", "--kmer-per-seq", "--kmer-per-seq-scale", "--min-seq-id", "-e", "-c",
                                "--cov-mode", "--max-seq-len", "--keep-target", "--hash-shift", "--ignore-multi-kmer", "--rescore-mode", "--min-aln-len", "--seq-id-mode"};
         m["guidedassemble-chain"] = m["assemble-chain"];
-        m["nuclassemble-chain"] = m["assemble-chain"]; m["nuclassemble-chain"].insert({"--chop-cycle", "--fasta-out", "--min-contig-len", "--contig-output-mode"});
+        // (--nuclassembly-out DB: the nuclassemble of data/guidedNuclAssemble.sh:135-170 behind the guided loop, with the nucleotide workflow's own flags)
+        m["guidedassemble-chain"].insert({"--nuclassembly-out", "--chop-cycle", "--min-contig-len", "--contig-output-mode"});
+        m["nuclassemble-chain"] = m["assemble-chain"]; m["nuclassemble-chain"].insert({"--chop-cycle", "--fasta-out", "--min-contig-len", "--contig-output-mode", "--db-mode", "--db-out"});
         m["assemble-chain"].insert({"--fasta-out", "--filter-proteins", "--protein-filter-threshold"});
         m["mergereads"] = {};       // the reference's onlythreads set (plass.cpp:47, Parameters.cpp:301-303): --threads, -v
         for (auto &kv : m) kv.second.insert(common.begin(), common.end());
@@ -129,7 +236,7 @@ static const std::map<std::string, std::set<std::string>> &moduleFlags() {
 static const std::set<std::string> &boolFlags() {
     static const std::set<std::string> b = {"-a", "--add-self-matches", "--wrapped-scoring", "--filter-hits", "--include-only-extendable", "--ignore-multi-kmer",
                                             "--keep-target", "--chop-cycle", "--adjust-kmer-len", "--use-all-table-starts", "--add-orf-stop", "--preserve-keys",
-                                            "--take-larger-entry"};
+                                            "--take-larger-entry", "--db-mode"};
     return b;
 }
 static bool parseBool(const std::string &v, bool &ok) {                 // Parameters::parseBool: TRUE/1 | FALSE/0
@@ -148,7 +255,9 @@ int main(int argc, char **argv) {
                         "       plass-hip nuclassemble-chain <i:nuclDB | r1.fastq r2.fastq …> <o:assemblyDB> [--num-iterations 8]        (writes <o>_cycle_<i> for circular contigs)\n"
                         "       (assemble-chain --filter-proteins 0 / nuclassemble-chain [--min-contig-len 1000] [--contig-output-mode 1]: --fasta-out FILE writes the\n"
                         "        selected contigs as FASTA, the workflows' tail, data/assemble.sh:159-201, data/nuclassemble.sh:138-207)\n"
-                        "       plass-hip guidedassemble-chain <i:readDB | r1.fastq r2.fastq …> <o:nuclAssemblyDB> <o:aaAssemblyDB> [--num-iterations 5]\n"
+                        "       (nuclassemble-chain --db-mode 1 --db-out DB: the selected contigs as DB, DB.index, DB.dbtype and DB_cycle.index instead, nuclassemble.sh:200-207)\n"
+                        "       plass-hip guidedassemble-chain <i:readDB | r1.fastq r2.fastq …> <o:nuclAssemblyDB> <o:aaAssemblyDB> [--num-iterations aa:5,nucl:5]\n"
+                        "       (--nuclassembly-out DB: goes on with data/guidedNuclAssemble.sh:135-170 — the extended ORFs + the reads through nuclassemble --db-mode 1)\n"
                         "       (FASTQ pairs: merged on the GPU first, as the workflows' mergereads step, data/assemble.sh:27-38)\n");
         return EXIT_FAILURE;
     }
@@ -166,7 +275,7 @@ int main(int argc, char **argv) {
         f.alph = 13; f.kps = 60; f.ignoreMulti = 1; f.covThr = 0.0f; f.covMode = 0; f.evalThr = 1e-5; f.rescoreMode = 3; f.keepTarget = 1; f.hashShift = 67;
         if (mod == "assemble-chain") { f.k = 14; f.scaleAA = 0.0f; f.seqIdThr = 0.9f; f.maxSeqLen = 65535; f.numIterations = 12; }
         else if (mod == "nuclassemble-chain") { f.k = 22; f.scaleNucl = 0.1f; f.seqIdThr = 0.99f; f.maxSeqLen = 200000; f.numIterations = 8; f.onlyExt = 1; f.chopCycle = 1; }
-        else { f.k = 14; f.scaleAA = 0.1f; f.seqIdThr = 0.97f; f.maxSeqLen = 200000; f.numIterations = 5; f.onlyExt = 1; f.covMode = 1; f.addBt = 1; }
+        else { f.k = 14; f.scaleAA = 0.1f; f.scaleNucl = 0.1f; f.seqIdThr = 0.97f; f.maxSeqLen = 200000; f.numIterations = 5; f.onlyExt = 1; f.covMode = 1; f.addBt = 1; }
     }
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
@@ -186,8 +295,17 @@ int main(int argc, char **argv) {
             if (!ok) { fprintf(stdout, "Error in argument %s\n", a.c_str()); return false; }
             field = b ? 1 : 0; return true;
         };
-        if (a == "-k") f.k = atoi(v.c_str());
-        else if (a == "--num-iterations") { std::string t2; f.numIterations = atoi((multiParam(v, mod == "assemble-chain" || mod == "guidedassemble-chain" ? "aa" : "nucl", t2) ? t2 : v).c_str()); }
+        if (a == "-k") {       // (guided chain: a MultiParam, one value sets both halves — lib/mmseqs/src/commons/MultiParam.cpp:23-39)
+            if (mod == "guidedassemble-chain") { if (multiParam(v, "aa", t)) f.k = atoi(t.c_str()); if (multiParam(v, "nucl", t)) f.kNucl = atoi(t.c_str()); }
+            else f.k = atoi(v.c_str());
+        }
+        else if (a == "--num-iterations") {
+            std::string t2; f.numIterations = atoi((multiParam(v, mod == "assemble-chain" || mod == "guidedassemble-chain" ? "aa" : "nucl", t2) ? t2 : v).c_str());
+            if (multiParam(v, "nucl", t2)) f.numIterationsNucl = atoi(t2.c_str());
+        }
+        else if (a == "--nuclassembly-out") f.nuclAssemblyOut = v;
+        else if (a == "--db-out") f.dbOut = v;
+        else if (a == "--db-mode") { if (!setBool(f.dbMode)) return EXIT_FAILURE; }
         else if (a == "--write-intermediate") f.writeIntermediate = v;
         else if (a == "--fasta-out") f.fastaOut = v;
         else if (a == "--filter-proteins") f.filterProteins = atoi(v.c_str());
@@ -211,7 +329,10 @@ int main(int argc, char **argv) {
             else if (mod == "assemble-chain") { if (multiParam(v, "aa", t)) f.seqIdThr = strtof(t.c_str(), nullptr); }
             else f.seqIdThr = strtof(v.c_str(), nullptr);
         }
-        else if (a == "--min-aln-len") f.minAlnLen = atoi(v.c_str());
+        else if (a == "--min-aln-len") {
+            if (mod == "guidedassemble-chain") { if (multiParam(v, "aa", t)) f.minAlnLen = atoi(t.c_str()); if (multiParam(v, "nucl", t)) f.minAlnLenNucl = atoi(t.c_str()); }
+            else f.minAlnLen = atoi(v.c_str());
+        }
         else if (a == "--seq-id-mode") f.seqIdMode = atoi(v.c_str());
         else if (a == "-a") { if (!setBool(f.addBt)) return EXIT_FAILURE; }
         else if (a == "--add-self-matches") { if (!setBool(f.addSelf)) return EXIT_FAILURE; }
@@ -310,6 +431,19 @@ int main(int argc, char **argv) {
         struct stat stF;
         if (stat(f.fastaOut.c_str(), &stF) == 0) { fprintf(stdout, "%s exists already!\n", f.fastaOut.c_str()); return EXIT_FAILURE; }     // data/assemble.sh:23, nuclassemble.sh:69
     }
+    // --db-mode 1 --db-out DB (nuclassemble-chain) and --nuclassembly-out DB (guidedassemble-chain): the same tail ending in createsubdb's DB
+    // instead of the FASTA file (nuclassemble.sh:200-207; the guided workflow runs its nuclassemble with --db-mode 1, GuidedNuclassembler.cpp:173)
+    if (mod == "nuclassemble-chain" && (f.dbMode || !f.dbOut.empty())) {
+        if (f.dbMode && !f.fastaOut.empty()) { fprintf(stdout, "nuclassemble-chain: --db-mode 1 writes a DB (--db-out), not a FASTA file: --fasta-out cannot be combined with it\n"); return EXIT_FAILURE; }
+        if (!f.dbMode || f.dbOut.empty()) { fprintf(stdout, "nuclassemble-chain: --db-mode 1 and --db-out DB go together\n"); return EXIT_FAILURE; }
+    }
+    for (const std::string *o : {&f.dbOut, &f.nuclAssemblyOut}) {
+        if (o->empty()) continue;
+        if (f.contigOutputMode != 0 && f.contigOutputMode != 1) { fprintf(stdout, "--contig-output-mode must be 0 or 1\n"); return EXIT_FAILURE; }
+        struct stat stO;
+        if (stat(o->c_str(), &stO) == 0) { fprintf(stdout, "%s exists already!\n", o->c_str()); return EXIT_FAILURE; }     // nuclassemble.sh:69, guidedNuclAssemble.sh:24
+    }
+    if (!f.nuclAssemblyOut.empty() && f.numIterationsNucl < 1) { fprintf(stdout, "--num-iterations must be at least 1 (nucl)\n"); return EXIT_FAILURE; }
     if (getenv("PLASSHIP_CLI_DRYRUN") && atoi(getenv("PLASSHIP_CLI_DRYRUN")) != 0) {
         fprintf(stdout, "plass-hip dry run: %s accepted (%zu positional arguments, %zu flags); nothing read or computed\n", mod.c_str(), pos.size(), f.seen.size());
         return EXIT_DRYRUN_ACCEPTED;
@@ -519,89 +653,78 @@ int main(int argc, char **argv) {
                 if (K(plasship_translate_nucs(ctx, ol, hl, &tp, &al, &ost)) || K(plasship_translate_nucs(ctx, os, hs, &tp, &as, &ost)) || K(plasship_seqdb_concat(ctx, al, as, &db))) return fail(mod.c_str());
                 plasship_seqdb_free(ctx, al); plasship_seqdb_free(ctx, as);
             }
-            plasship_orfhdr_free(ctx, hl); plasship_orfhdr_free(ctx, hs); plasship_seqdb_free(ctx, ol); plasship_seqdb_free(ctx, os); plasship_seqdb_free(ctx, in);
+            plasship_orfhdr_free(ctx, hl); plasship_orfhdr_free(ctx, hs); plasship_seqdb_free(ctx, ol); plasship_seqdb_free(ctx, os);
+            if (!(gd && !f.nuclAssemblyOut.empty())) { plasship_seqdb_free(ctx, in); in = nullptr; }      // (the guided tail concatenates the reads: guidedNuclAssemble.sh:161-165)
         } else if ((prot && dbtype != PLASSHIP_DBTYPE_AMINO_ACIDS) || (nuc && dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES)) {
             fprintf(stdout, "%s: wrong input DB type %d\n", mod.c_str(), dbtype); return EXIT_FAILURE;
         }
         const double tPrep = now();
-        // the tail (--fasta-out) needs SOURCE — the DB the loop starts from (the reads; the fragments before findassemblystart: kept below) — and
-        // every iteration's circular contigs
-        const bool wantFasta = !f.fastaOut.empty();
-        plasship_seqdb *source = (wantFasta && nuc) ? db : nullptr, *cycAll = nullptr;
-        plasship_rescore_params rp; memset(&rp, 0, sizeof(rp));
-        rp.rescore_mode = f.rescoreMode; rp.eval_thr = f.evalThr; rp.seq_id_thr = f.seqIdThr; rp.cov_mode = f.covMode; rp.cov_thr = f.covThr; rp.min_aln_len = f.minAlnLen;
-        rp.seq_id_mode = f.seqIdMode; rp.add_backtrace = gd ? 1 : 0;
-        plasship_assemble_params ap; memset(&ap, 0, sizeof(ap));
-        ap.seq_id_thr = gd ? f.seqIdThrNucl : f.seqIdThr; ap.max_seq_len = f.maxSeqLen; ap.keep_target = f.keepTarget; ap.rescore_mode = f.rescoreMode;
-        unsigned long long overlaps = 0; double kernelMs = 0;
-        int hashShift = f.hashShift;
-        for (int it = 0; it < f.numIterations; it++) {
-            plasship_kmermatch_params kp; memset(&kp, 0, sizeof(kp));
-            kp.kmer_size = f.k; kp.alphabet_size = f.alph; kp.kmers_per_seq = f.kps; kp.kmers_per_seq_scale = nuc ? f.scaleNucl : f.scaleAA; kp.ignore_multi_kmer = f.ignoreMulti;
-            kp.cov_mode = f.covMode; kp.cov_thr = f.covThr;
-            // plass assemble: --hash-shift grows with every second iteration, iteration 0 keeps non-extendable matches (Assembler.cpp:99-110)
-            if (prot) { hashShift += it % 2; kp.hash_shift = hashShift; kp.include_only_extendable = it > 0; } else { kp.hash_shift = f.hashShift; kp.include_only_extendable = 1; }
-            plasship_seqdb *q = gd ? aa : db;
-            plasship_cands *c = nullptr; plasship_alns *al = nullptr; plasship_kmermatch_stats ks; plasship_rescore_stats rs; plasship_assemble_stats as;
-            if (K(plasship_kmermatch(ctx, q, &kp, &c, &ks)) || K(plasship_rescore(ctx, q, q, c, &rp, &al, &rs))) return fail(mod.c_str());
-            if (prot && it == 0) {         // data/assemble.sh:110-141: findassemblystart, then k-mer matching and re-scoring again on the corrected sequences
-                plasship_seqdb *corr = nullptr; plasship_findstart_stats fs;
-                if (K(plasship_find_assembly_start(ctx, db, al, &corr, &fs))) return fail(mod.c_str());
-                plasship_alns_free(ctx, al); plasship_cands_free(ctx, c);
-                if (wantFasta) source = db; else plasship_seqdb_free(ctx, db);      // SOURCE of the tail: aa_6f_start_long, before the correction
-                db = corr; q = db;
-                if (K(plasship_kmermatch(ctx, q, &kp, &c, &ks)) || K(plasship_rescore(ctx, q, q, c, &rp, &al, &rs))) return fail(mod.c_str());
-            }
-            overlaps += ks.n_candidates; kernelMs += ks.ms_extract + ks.ms_sort1 + ks.ms_group + ks.ms_sort2 + ks.ms_reduce + rs.ms_kernel;
-            plasship_seqdb *next = nullptr, *nextAa = nullptr;
-            if (gd) {
-                plasship_alns *na = nullptr; plasship_aln2nucl_params np; np.gap_open = f.gapOpenNucl; np.gap_extend = f.gapExtendNucl; plasship_aln2nucl_stats ns;
-                if (K(plasship_aln2nucl(ctx, db, db, aa, aa, al, &np, &na, &ns)) || K(plasship_guided_assemble(ctx, db, aa, na, &ap, &next, &nextAa, &as))) return fail(mod.c_str());
-                plasship_alns_free(ctx, na);
-            } else if (K(plasship_assemble(ctx, db, al, &ap, &next, &as))) return fail(mod.c_str());
-            kernelMs += as.ms_kernel;
-            plasship_alns_free(ctx, al); plasship_cands_free(ctx, c);
-            if (joinWriter()) { fprintf(stdout, "%s: writing an intermediate DB failed: %s\n", mod.c_str(), writerErr.c_str()); return EXIT_FAILURE; }   // the writer read `db`
-            if (db != source) plasship_seqdb_free(ctx, db);
-            if (gd) plasship_seqdb_free(ctx, aa);
-            db = next; aa = nextAa;
-            if (nuc) {     // data/nuclassemble.sh:19-61,132: circular contigs leave the loop, the rest goes on
-                plasship_seqdb *cyc = nullptr, *rest = nullptr; plasship_cyclecheck_params cp; cp.max_seq_len = f.maxSeqLen; cp.chop_cycle = f.chopCycle; plasship_cyclecheck_stats cs;
-                if (K(plasship_cyclecheck(ctx, db, &cp, &cyc, &rest, &cs))) return fail(mod.c_str());
-                if (cs.n_cyclic && KW(plasship_seqdb_write(ctx, cyc, (outs[0] + "_cycle_" + std::to_string(it)).c_str()))) return fail(mod.c_str());
-                if (wantFasta && cs.n_cyclic) {       // PREV_CYCLE_ALL: every iteration's circular contigs (nuclassemble.sh:35-41, concatdbs --preserve-keys)
-                    if (!cycAll) { cycAll = cyc; cyc = nullptr; }
-                    else { plasship_seqdb *u = nullptr; if (K(plasship_seqdb_concat_keys(ctx, cycAll, cyc, 1, &u))) return fail(mod.c_str()); plasship_seqdb_free(ctx, cycAll); cycAll = u; }
-                }
-                if (cyc) plasship_seqdb_free(ctx, cyc);
-                plasship_seqdb_free(ctx, db); db = rest;
-            }
-            fprintf(stdout, "iteration %d: candidates %llu verified %llu extended %llu (%.3f s since the DB was read)\n", it, (unsigned long long) ks.n_candidates, (unsigned long long) rs.n_accepted, (unsigned long long) as.n_extended, now() - tPrep);
-            if (it + 1 < f.numIterations) writeAsync(db, (gd ? "assembly_nucl_" : "assembly_") + std::to_string(it));
-        }
+        // a tail (--fasta-out; --db-mode 1 --db-out; --nuclassembly-out) needs SOURCE — the DB the loop starts from — and, on nucleotides,
+        // every iteration's circular contigs: the loop keeps both
+        const bool wantFasta = !f.fastaOut.empty(), wantDb = nuc && f.dbMode, wantNuclAsm = gd && !f.nuclAssemblyOut.empty();
+        ChainLoop L;
+        L.ctx = ctx; L.name = mod.c_str(); L.kind = prot ? CHAIN_PROTEIN : nuc ? CHAIN_NUCL : CHAIN_GUIDED;
+        L.numIterations = f.numIterations; L.k = f.k; L.alph = f.alph; L.kps = f.kps; L.kpsScale = nuc ? f.scaleNucl : f.scaleAA; L.ignoreMulti = f.ignoreMulti;
+        L.covMode = f.covMode; L.covThr = f.covThr; L.hashShift = f.hashShift; L.gapOpenNucl = f.gapOpenNucl; L.gapExtendNucl = f.gapExtendNucl;
+        L.chopCycle = f.chopCycle; L.maxSeqLen = f.maxSeqLen;
+        memset(&L.rp, 0, sizeof(L.rp));
+        L.rp.rescore_mode = f.rescoreMode; L.rp.eval_thr = f.evalThr; L.rp.seq_id_thr = f.seqIdThr; L.rp.cov_mode = f.covMode; L.rp.cov_thr = f.covThr; L.rp.min_aln_len = f.minAlnLen;
+        L.rp.seq_id_mode = f.seqIdMode; L.rp.add_backtrace = gd ? 1 : 0;
+        memset(&L.ap, 0, sizeof(L.ap));
+        L.ap.seq_id_thr = gd ? f.seqIdThrNucl : f.seqIdThr; L.ap.max_seq_len = f.maxSeqLen; L.ap.keep_target = f.keepTarget; L.ap.rescore_mode = f.rescoreMode;
+        L.keepForTail = wantFasta || wantDb || wantNuclAsm;
+        if (nuc) L.cyclePrefix = outs[0] + "_cycle_";
+        L.intermediateName = gd ? "assembly_nucl_" : "assembly_";
+        L.joinWriter = [&]() { if (joinWriter()) { fprintf(stdout, "%s: writing an intermediate DB failed: %s\n", mod.c_str(), writerErr.c_str()); return 1; } return 0; };
+        L.writeAsync = writeAsync;
+        L.db = db; L.aa = aa; L.tStart = tPrep;
+        if (const int rcL = runChainLoop(L)) return rcL;
+        db = L.db; aa = L.aa;
         const double tLoop = now();
-        if (joinWriter()) { fprintf(stdout, "%s: writing an intermediate DB failed: %s\n", mod.c_str(), writerErr.c_str()); return EXIT_FAILURE; }
+        if (L.joinWriter()) return EXIT_FAILURE;
         if (KW(plasship_seqdb_write(ctx, db, outs[0].c_str())) || (gd && KW(plasship_seqdb_write(ctx, aa, outs[1].c_str())))) return fail(mod.c_str());
-        if (wantFasta) {
-            // RESULT: the last assembly, or (nucleotide, circular contigs found) the non-circular rest + every circular contig (nuclassemble.sh:140-148)
-            plasship_seqdb *result = db, *merged = nullptr, *sel = nullptr;
-            if (cycAll) { if (K(plasship_seqdb_concat_keys(ctx, db, cycAll, 1, &merged))) return fail(mod.c_str()); result = merged; }
+        if (wantFasta || wantDb) {
+            if (const int rcT = chainTail(ctx, mod.c_str(), nuc, db, L.source, L.cycAll, f.contigOutputMode, f.minContigLen, f.fastaOut, f.dbOut)) return rcT;
+        }
+        double tTail = 0;
+        if (wantNuclAsm) {
+            // ---- data/guidedNuclAssemble.sh:135-170 on the handles of the loop above ----
+            const double tt0 = now();
+            // `_only_assembled` (guidedNuclAssemble.sh:136-139): the entries of the last assembly_nucl_<i> whose key nucl_6f_start_long holds with a
+            // shorter entry, `$3 > $6`; no length threshold — the nucleotide selection with only_extended and --min-contig-len 0 (include/plasship.h)
             plasship_select_params sp; memset(&sp, 0, sizeof(sp));
-            sp.mode = nuc ? PLASSHIP_SELECT_NUCLEOTIDE : PLASSHIP_SELECT_PROTEIN; sp.only_extended = f.contigOutputMode == 1; sp.min_contig_len = f.minContigLen;
-            plasship_select_stats ss; plasship_fasta_stats fs;
-            if (!source) { fprintf(stdout, "%s: --fasta-out needs the fragment DB before findassemblystart\n", mod.c_str()); return EXIT_FAILURE; }
-            if (K(plasship_select_contigs(ctx, result, source, cycAll, &sp, &sel, &ss))) return fail(mod.c_str());
-            size_t nResult = 0; plasship_seqdb_info(result, &nResult, nullptr, nullptr, nullptr, nullptr);
-            if (KW(plasship_fasta_write(ctx, sel, cycAll, f.fastaOut.c_str(), &fs))) return fail(mod.c_str());
-            fprintf(stdout, "fasta: %llu of %zu contigs selected (S1 only %llu, S2 only %llu, both %llu, circular %llu), %llu bytes | select %.3f ms, format %.3f ms, file %.3f s\n",
-                    (unsigned long long) ss.n_selected, nResult, (unsigned long long) ss.n_s1_only, (unsigned long long) ss.n_s2_only,
-                    (unsigned long long) ss.n_both, (unsigned long long) ss.n_cycle, (unsigned long long) fs.bytes, ss.ms_kernel, fs.ms_kernel, fs.ms_total * 1e-3);
-            plasship_seqdb_free(ctx, sel); if (merged) plasship_seqdb_free(ctx, merged); if (cycAll) plasship_seqdb_free(ctx, cycAll);
-            plasship_seqdb_free(ctx, source);
+            sp.mode = PLASSHIP_SELECT_NUCLEOTIDE; sp.only_extended = 1; sp.min_contig_len = 0;
+            plasship_seqdb *only = nullptr, *mergedIn = nullptr; plasship_select_stats ss;
+            if (K(plasship_select_contigs(ctx, db, L.source, nullptr, &sp, &only, &ss))) return fail(mod.c_str());
+            // concatdbs <only_assembled> <reads> guided_assembly.merged (guidedNuclAssemble.sh:161-165): the subset's keys are kept, the reads follow
+            // from max(key) + 1 on in the order of their data file (DBConcat.cpp:63-118; 1 when nothing was selected: DBConcat.cpp:63,100)
+            if (K(plasship_seqdb_concat(ctx, only, in, &mergedIn))) return fail(mod.c_str());
+            size_t nAsm = 0, nMerged = 0; plasship_seqdb_info(db, &nAsm, nullptr, nullptr, nullptr, nullptr); plasship_seqdb_info(mergedIn, &nMerged, nullptr, nullptr, nullptr, nullptr);
+            fprintf(stdout, "guided tail: %llu of %zu extended ORFs + the reads = %zu sequences\n", (unsigned long long) ss.n_selected, nAsm, nMerged);
+            plasship_seqdb_free(ctx, only); plasship_seqdb_free(ctx, L.source); L.source = nullptr; plasship_seqdb_free(ctx, in); in = nullptr;
+            // nuclassemble <merged> <out> --db-mode 1 (guidedNuclAssemble.sh:167-170): the nucleotide halves of the multi-parameters
+            // (GuidedNuclassembler.cpp:167-172), everything else as penguin nuclassemble runs it (Nuclassembler.cpp:10-31)
+            ChainLoop N;
+            N.ctx = ctx; N.name = mod.c_str(); N.kind = CHAIN_NUCL;
+            N.numIterations = f.numIterationsNucl; N.k = f.kNucl; N.alph = f.alph; N.kps = f.kps; N.kpsScale = f.scaleNucl; N.ignoreMulti = f.ignoreMulti;
+            N.covMode = 0; N.covThr = f.covThr; N.hashShift = f.hashShift; N.chopCycle = f.chopCycle; N.maxSeqLen = f.maxSeqLen;
+            memset(&N.rp, 0, sizeof(N.rp));
+            N.rp.rescore_mode = f.rescoreMode; N.rp.eval_thr = f.evalThr; N.rp.seq_id_thr = f.seqIdThrNucl; N.rp.cov_mode = 0; N.rp.cov_thr = f.covThr; N.rp.min_aln_len = f.minAlnLenNucl;
+            N.rp.seq_id_mode = f.seqIdMode; N.rp.add_backtrace = 0;
+            N.ap = L.ap;
+            N.keepForTail = true;
+            N.db = mergedIn; N.tStart = tt0;
+            if (const int rcN = runChainLoop(N)) return rcN;
+            if (const int rcT = chainTail(ctx, mod.c_str(), true, N.db, N.source, N.cycAll, f.contigOutputMode, f.minContigLen, std::string(), f.nuclAssemblyOut)) return rcT;
+            plasship_seqdb_free(ctx, N.db);
+            L.overlaps += N.overlaps; L.kernelMs += N.kernelMs;
+            tTail = now() - tt0;
         }
         const double tEnd = now();
-        fprintf(stdout, "chain: %d iterations, %llu candidate overlaps | read %.3fs preprocessing %.3fs iterations %.3fs (kernels %.3fs) write %.3fs\n", f.numIterations, overlaps,
-                tRead - t0, tPrep - tRead, tLoop - tPrep, kernelMs * 1e-3, tEnd - tLoop);
+        fprintf(stdout, "chain: %d iterations, %llu candidate overlaps | read %.3fs preprocessing %.3fs iterations %.3fs (kernels %.3fs) write %.3fs", f.numIterations, L.overlaps,
+                tRead - t0, tPrep - tRead, tLoop - tPrep, L.kernelMs * 1e-3, tEnd - tLoop - tTail);
+        if (wantNuclAsm) fprintf(stdout, " nuclassembly (%d iterations) %.3fs", f.numIterationsNucl, tTail);
+        fprintf(stdout, "\n");
         plasship_seqdb_free(ctx, db); if (gd) plasship_seqdb_free(ctx, aa);
         if (wctx) plasship_ctx_destroy(wctx);
     }

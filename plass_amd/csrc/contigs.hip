@@ -1,7 +1,9 @@
 // The workflows' tail on the device: which contigs are reported, and the FASTA file they go out in.
 //   plasship_select_contigs  replaces the `_only_assembled` index filters + createsubdb of data/assemble.sh:170-189 (protein) and
 //                            data/nuclassemble.sh:151-169 (nucleotide);
-//   plasship_fasta_write     replaces createhdb (src/util/createhdb.cpp:45-58) + convert2fasta (lib/mmseqs/src/util/convert2fasta.cpp:41-56).
+//   plasship_fasta_write     replaces createhdb (src/util/createhdb.cpp:45-58) + convert2fasta (lib/mmseqs/src/util/convert2fasta.cpp:41-56);
+//   plasship_subdb_write     replaces createsubdb --subdb-mode 0 and the `_cycle.index` filter of the workflows' --db-mode end
+//                            (data/nuclassemble.sh:170-176,200-207; lib/mmseqs/src/util/createsubdb.cpp:41-92).
 // "Entry length" is the index length (sequence + "\n\0").  Ranks are key-order ids: the data file of the canonical layout (one file in key
 // order: what this library writes, what the reference writes with --threads 1) — the one place where the layout matters is S2 below.
 #include "common.hpp"
@@ -201,6 +203,31 @@ __global__ __launch_bounds__(256) void fastaWriteKernel(const char *data, const 
     }
 }
 
+// ---- createsubdb --subdb-mode 0 ---------------------------------------------------------------------------------------------------
+// A subset made by plasship_select_contigs is an index over its parent's bytes; the DB createsubdb writes holds the listed entries back to
+// back in list order (createsubdb.cpp:66-79).  Entry bytes ("SEQ\n\0") per entry, a prefix sum, then one wavefront per entry.
+__global__ __launch_bounds__(256) void subdbBytesKernel(const uint32_t *__restrict__ len, uint64_t n, uint64_t *__restrict__ bytes) {
+    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t) gridDim.x * 256) bytes[i] = (uint64_t) len[i] + 2;
+}
+// 16 bytes per lane and step.  Neither end of the copy is aligned (entries start anywhere in both buffers): the bytes go through
+// __builtin_memcpy, whose alignment of 1 lets the compiler pick what the target allows — global memory takes unaligned dwordx4 accesses on
+// gfx950, so this is one load and one store per lane and step.  The last 1-15 bytes of an entry are copied byte by byte: nothing is read or
+// written beyond the entry, so the kernel does not lean on the padding behind the buffers.
+__global__ __launch_bounds__(256) void subdbGatherKernel(const char *__restrict__ data, const uint64_t *__restrict__ off, const uint32_t *__restrict__ len,
+                                                         const uint64_t *__restrict__ newOff, uint64_t n, char *__restrict__ out) {
+    const uint32_t lane = (uint32_t) laneId();
+    const uint64_t wave = ((uint64_t) blockIdx.x * 256 + threadIdx.x) >> 6, nWaves = ((uint64_t) gridDim.x * 256) >> 6;
+    for (uint64_t i = wave; i < n; i += nWaves) {
+        const uint32_t el = len[i] + 2;
+        const char *from = data + off[i];
+        char *to = out + newOff[i];
+        for (uint32_t q = 16u * lane; q < el; q += 1024u) {
+            if (q + 16u <= el) { uint4 x; __builtin_memcpy(&x, from + q, 16); __builtin_memcpy(to + q, &x, 16); }
+            else for (uint32_t b = q; b < el; b++) to[b] = from[b];
+        }
+    }
+}
+
 static unsigned gridFor(uint64_t n, int numCU) { return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) numCU * 16)); }
 
 }  // namespace plasship
@@ -334,6 +361,72 @@ extern "C" int plasship_fasta_write(plasship_ctx *ctx, const plasship_seqdb *db,
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         stats->n_entries = n; stats->bytes = total; stats->n_chunks = nChunks; stats->ms_kernel = msKernel0 + msKernel; stats->ms_total = (float) ((ioNow() - t0) * 1e3);
+    }
+    return PLASSHIP_OK;
+}
+
+extern "C" int plasship_subdb_write(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_seqdb *cycles, const char *path, plasship_subdb_stats *stats) {
+    if (!ctx || !db || !path) { setError("plasship_subdb_write: bad argument"); return PLASSHIP_ERR_ARG; }
+    PH_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    const uint64_t n = db->n;
+    const double t0 = ioNow();
+    PH_CHECK(hipEventRecord(ctx->ev[0], st));
+    DevBuf dOff, dTmp, dOut;
+    const size_t tmpBytes = exclusiveScanTmpBytes((size_t) n + 2);
+    if (dOff.alloc((n + 2) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess) { setError("plasship_subdb_write: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+    if (n) hipLaunchKernelGGL(subdbBytesKernel, dim3(gridFor(n, ctx->numCU)), dim3(256), 0, st, (const uint32_t *) db->d_len.as<uint32_t>(), n, dOff.as<uint64_t>());
+    if (exclusiveScanU64(st, dOff.as<uint64_t>(), dOff.as<uint64_t>(), n, dTmp.p, tmpBytes)) { setError("plasship_subdb_write: scan failed"); return PLASSHIP_ERR_DEVICE; }
+    uint64_t total = 0;
+    PH_COPY_SYNC(st, &total, dOff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost);
+    if (dOut.alloc(total + 64) != hipSuccess) { setError("plasship_subdb_write: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+    // one wavefront per entry, four to a block
+    if (n) hipLaunchKernelGGL(subdbGatherKernel, dim3((unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 3) / 4, (uint64_t) ctx->numCU * 16))), dim3(256), 0, st, db->dataPtr(),
+                              (const uint64_t *) db->d_off.as<uint64_t>(), (const uint32_t *) db->d_len.as<uint32_t>(), (const uint64_t *) dOff.as<uint64_t>(), n, dOut.as<char>());
+    PH_CHECK(hipEventRecord(ctx->ev[1], st));
+    PH_CHECK(plasship::streamSync(st));
+    PH_CHECK(hipGetLastError());
+    float ms = 0; PH_CHECK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    // the index: keys and entry lengths in list order (a handle's order is key order, so the list is ordered and createsubdb leaves the
+    // index as written: createsubdb.cpp:57-58,88)
+    std::vector<uint32_t> key(n), elen(n), cyc;
+    if (n) {
+        int rc = stagedCopyToHost(ctx, key.data(), db->d_key.p, n * 4); if (rc) return rc;
+        rc = stagedCopyToHost(ctx, elen.data(), db->d_len.p, n * 4); if (rc) return rc;
+        for (uint64_t i = 0; i < n; i++) elen[i] += 2;
+    }
+    if (cycles && cycles->n) { cyc.resize(cycles->n); const int rc = stagedCopyToHost(ctx, cyc.data(), cycles->d_key.p, cycles->n * 4); if (rc) return rc; }
+    std::string err; DBFileWriter w;
+    if (!w.open(path, db->dbtype, err)) { setError(err); return PLASSHIP_ERR_IO; }
+    if (total) {
+        const int rc = stagedDownload(ctx, dOut.p, total, [&](const char *src, uint64_t, uint64_t nb) { w.data(src, (size_t) nb); return !w.failed; });
+        if (rc == PLASSHIP_ERR_IO) setError(std::string("error while writing ") + path);
+        if (rc) return rc;
+    }
+    w.index(key.data(), elen.data(), (size_t) n);
+    if (!w.close(err)) { setError(err); return PLASSHIP_ERR_IO; }
+    // "<path>_cycle.index": the lines of the index just written whose key is circular (nuclassemble.sh:173-175,204-206); the file exists
+    // whenever a cycle DB does, with or without lines
+    uint64_t nCyc = 0;
+    if (cycles) {
+        std::string text; char tmp[80]; uint64_t o = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            if (std::binary_search(cyc.begin(), cyc.end(), key[i])) {          // (a handle's keys are ascending)
+                char *q = fmtU32(key[i], tmp); *q++ = '\t'; q = fmtU64(o, q); *q++ = '\t'; q = fmtU64(elen[i], q); *q++ = '\n';
+                text.append(tmp, (size_t) (q - tmp)); nCyc++;
+            }
+            o += elen[i];
+        }
+        const std::string name = std::string(path) + "_cycle.index", tmpName = name + ".tmp." + std::to_string((long) getpid());
+        FILE *fp = fopen(tmpName.c_str(), "wb");
+        bool ok = fp != nullptr;
+        if (fp) { ok = fwrite(text.data(), 1, text.size(), fp) == text.size(); ok &= fclose(fp) == 0; }
+        if (ok) ok = rename(tmpName.c_str(), name.c_str()) == 0;
+        if (!ok) { unlink(tmpName.c_str()); setError("plasship_subdb_write: cannot write " + name); return PLASSHIP_ERR_IO; }
+    }
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->n_entries = n; stats->bytes = total; stats->n_cycle = nCyc; stats->ms_kernel = ms; stats->ms_total = (float) ((ioNow() - t0) * 1e3);
     }
     return PLASSHIP_OK;
 }
