@@ -1870,7 +1870,7 @@ static int buildOutputDBImpl(plasship_ctx *ctx, const plasship_seqdb *db, const 
     }
     if (append) {
         o->heap = db->heap; o->contiguous = false;
-        if (N) hipLaunchKernelGGL(appendOutKernel, dim3(std::min<uint32_t>((N + 255) / 256, (uint32_t) ctx->numCU * (uint32_t) tuneInt("WRITEOUT", 16))), dim3(256), 0, st, sv, dFlags, dNewLen, dNewStart, dArena,
+        if (N) hipLaunchKernelGGL(appendOutKernel, dim3(std::min<uint32_t>((N + 255) / 256, (uint32_t) ctx->numCU * 16u)), dim3(256), 0, st, sv, dFlags, dNewLen, dNewStart, dArena,
                                   (const uint64_t *) dAppOff.as<uint64_t>(), heapBase, (const uint32_t *) dKeep.as<uint32_t>(), (const uint64_t *) dKeepPos.as<uint64_t>(), (const uint32_t *) db->d_key.as<uint32_t>(),
                                   db->heap->buf.as<char>(), o->d_off.as<uint64_t>(), o->d_len.as<uint32_t>(), o->d_key.as<uint32_t>(), o->d_changed.as<unsigned char>());
     } else {
@@ -1894,7 +1894,7 @@ static int buildOutputDBImpl(plasship_ctx *ctx, const plasship_seqdb *db, const 
         PH_CHECK(hipMemsetAsync(dst + outBytes, 0, 64, st));
         if (N) {
             // (2 and 4 sequences in flight per lane group changed nothing — profiles/r03_ab_knobs.txt: the kernel is not bound by its chains of round trips)
-            const unsigned woGrid = std::min<uint32_t>((N + 15) / 16, (uint32_t) ctx->numCU * (uint32_t) tuneInt("WRITEOUT", 16));
+            const unsigned woGrid = std::min<uint32_t>((N + 15) / 16, (uint32_t) ctx->numCU * 16u);
             hipLaunchKernelGGL((writeOutKernel<8, 1>), dim3(woGrid), dim3(256), 0, st, sv, dFlags, dNewLen,
                                dNewStart, dArena, dOutOff.as<uint64_t>(), dKeep.as<uint32_t>(), dKeepPos.as<uint64_t>(), db->d_key.as<uint32_t>(),
                                dst, o->d_off.as<uint64_t>(), o->d_len.as<uint32_t>(), o->d_key.as<uint32_t>(), o->d_changed.as<unsigned char>());
@@ -2081,7 +2081,7 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
                                        (uint64_t) par->max_seq_len, dQSum.as<unsigned long long>(), guided ? dQSumAa.as<unsigned long long>() : (unsigned long long *) nullptr, dQCan.as<uint32_t>(),
                                        (nucl && !guided) ? 1 : 0);
     if (N) hipLaunchKernelGGL(arenaSizeKernel, dim3(std::min<uint32_t>((N + 255) / 256, 8192)), dim3(256), 0, st, sv, al->d_qoff.as<uint64_t>(), (const unsigned long long *) dQSum.as<unsigned long long>(),
-                              (const unsigned long long *) dQSumAa.as<unsigned long long>(), (const uint32_t *) dQCan.as<uint32_t>(), dLeftCap.as<uint32_t>(), dBytes.as<uint64_t>(), nucl ? 1 : 0, (uint64_t) tuneInt("NUCL_THREAD_BYTES", 1 << 30),
+                              (const unsigned long long *) dQSumAa.as<unsigned long long>(), (const uint32_t *) dQCan.as<uint32_t>(), dLeftCap.as<uint32_t>(), dBytes.as<uint64_t>(), nucl ? 1 : 0, (uint64_t) 1 << 30,
                               dTierA.as<uint64_t>(), dTierB.as<uint64_t>(),
                               guided ? aaDb->d_len.as<uint32_t>() : (const uint32_t *) nullptr, dAaLeftCap.as<uint32_t>(), guided ? dAaBytes.as<uint64_t>() : (uint64_t *) nullptr);
     if (guided && exclusiveScanU64(st, dAaBytes.as<uint64_t>(), dAaArenaOff.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
@@ -2108,7 +2108,7 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     a.s = sv; a.qoff = al->d_qoff.as<uint64_t>(); a.recs = al->d_recs.as<AlnRec>(); a.items = dItems.as<Item>(); a.arenaOff = dArenaOff.as<uint64_t>();
     a.leftCap = dLeftCap.as<uint32_t>(); a.arena = dArena.as<char>(); a.flags = dFlags.as<uint32_t>(); a.newLen = dNewLen.as<uint32_t>(); a.newStart = dNewStart.as<uint64_t>();
     a.mat = dMat.as<signed char>(); a.lambda = ev.g[0]; a.logK = ev.logK; a.ln2 = ev.ln2; a.seqIdThr = par->seq_id_thr; a.maxSeqLen = par->max_seq_len; a.rescoreMode = par->rescore_mode;
-    a.ownLaneMin = (uint32_t) tuneInt("ASM_OWN", 6);      // swept 1 / 3 / 6 / 12 / never: 30.4 / 28.4 / 27.9 / 29.9 / 40.3 ms for the two wide tiers (profiles/r05_ab_knobs.txt, call 11)
+    a.ownLaneMin = 6;      // swept 1 / 3 / 6 / 12 / never: 30.4 / 28.4 / 27.9 / 29.9 / 40.3 ms for the two wide tiers (profiles/r05_ab_knobs.txt, call 11)
     a.stats = dStats.as<unsigned long long>();
     a.smallList = dSmallList.as<uint32_t>(); a.nSmall = cnts[0];
     a.mid32List = dMid32List.as<uint32_t>(); a.nMid32 = cnts[1];
@@ -2159,17 +2159,15 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
             };
             if (pass == 0) {
                 if (cnts[0]) {
-                    a.queryList = dSmallList.as<uint32_t>(); a.nQueryList = cnts[0];
-                    if (tuneInt("NUCL_CLASSES", 1) == 1) {                    // PLASSHIP_TUNE_NUCL_CLASSES=2: id order
-                        DevBuf dCls;
-                        if (dCls.alloc(2 * NW_CLASSES * 4) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-                        PH_CHECK(hipMemsetAsync(dCls.p, 0, 2 * NW_CLASSES * 4, st));
-                        const unsigned g = std::min<uint32_t>((cnts[0] + 255) / 256, (uint32_t) ctx->numCU * 8);
-                        hipLaunchKernelGGL(nuclClassCountKernel, dim3(g), dim3(256), 0, st, (const uint32_t *) dSmallList.as<uint32_t>(), cnts[0], (const uint64_t *) dBytes.as<uint64_t>(), dCls.as<uint32_t>());
-                        hipLaunchKernelGGL(nuclClassScatterKernel, dim3(g), dim3(256), 0, st, (const uint32_t *) dSmallList.as<uint32_t>(), cnts[0], (const uint64_t *) dBytes.as<uint64_t>(), dCls.as<uint32_t>(),
-                                           dMidList.as<uint32_t>());          // (the 64-lane list is a protein tier: unused here)
-                        a.queryList = dMidList.as<uint32_t>();
-                    }
+                    // the list in work classes (nuclClassScatterKernel): the thread-per-query kernel reads the classed copy
+                    DevBuf dCls;
+                    if (dCls.alloc(2 * NW_CLASSES * 4) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+                    PH_CHECK(hipMemsetAsync(dCls.p, 0, 2 * NW_CLASSES * 4, st));
+                    const unsigned g = std::min<uint32_t>((cnts[0] + 255) / 256, (uint32_t) ctx->numCU * 8);
+                    hipLaunchKernelGGL(nuclClassCountKernel, dim3(g), dim3(256), 0, st, (const uint32_t *) dSmallList.as<uint32_t>(), cnts[0], (const uint64_t *) dBytes.as<uint64_t>(), dCls.as<uint32_t>());
+                    hipLaunchKernelGGL(nuclClassScatterKernel, dim3(g), dim3(256), 0, st, (const uint32_t *) dSmallList.as<uint32_t>(), cnts[0], (const uint64_t *) dBytes.as<uint64_t>(), dCls.as<uint32_t>(),
+                                       dMidList.as<uint32_t>());          // (the 64-lane list is a protein tier: unused here)
+                    a.queryList = dMidList.as<uint32_t>(); a.nQueryList = cnts[0];
                     const uint32_t grid = std::min<uint32_t>((cnts[0] + NT_BLOCK - 1) / NT_BLOCK, (uint32_t) ctx->numCU * 8);
                     if (guided) hipLaunchKernelGGL(assembleNuclThreadKernel<true>, dim3(grid), dim3(NT_BLOCK), 0, st, a);
                     else hipLaunchKernelGGL(assembleNuclThreadKernel<false>, dim3(grid), dim3(NT_BLOCK), 0, st, a);
@@ -2194,26 +2192,17 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     } else {
     // (round 4: the protein tiers' lists in work classes like the nucleotide list changed nothing — 82.2 against 81.0 ms for the stage: the
     //  tiers already group the queries by queue size, and id order keeps a wavefront's alignment records adjacent; profiles/r04_ab_knobs.txt)
-    // wavefronts per SIMD of the register-queue kernels (PLASSHIP_TUNE_ASM16 / ASM64): the grid is what the CUs hold at once
-    const int w16 = tuneInt("ASM16", 5), w64 = tuneInt("ASM64", 4);      // round 3 (after the copy tails went word-wise): 16.6 ms at 5 wavefronts, 17.0 at 6, 18.0 at 4
-    const uint32_t gx = (uint32_t) std::max(1, tuneInt("ASM_GRIDX", 1));      // grid = gx x what the CUs hold at once (round 6 A/B: finer shares against the tail)
-    const dim3 g16(std::min<uint32_t>((a.nSmall + 15) / 16, (uint32_t) ctx->numCU * (uint32_t) w16 * gx)), g64(std::min<uint32_t>((a.nMid + 3) / 4, (uint32_t) ctx->numCU * (uint32_t) w64 * gx));
+    // wavefronts per SIMD of the register-queue kernels: the grid is what the CUs hold at once
+    // (<16>, round 3, after the copy tails went word-wise: 16.6 ms at 5 wavefronts, 17.0 at 6, 18.0 at 4)
+    const dim3 g16(std::min<uint32_t>((a.nSmall + 15) / 16, (uint32_t) ctx->numCU * 5u)), g64(std::min<uint32_t>((a.nMid + 3) / 4, (uint32_t) ctx->numCU * 4u));
     // (round 5: the four tiers — disjoint queries — launched side by side on four streams, so that one tier's tail of long queues lies under
     //  the next tier: 88.8 against 82.7 ms for the stage; the tiers' wavefronts evict each other's lines.  profiles/r05_ab_knobs.txt)
     PH_CHECK(hipEventRecord(ctx->ev[2], st));
-    if (a.nSmall) {
-        if (w16 == 6) hipLaunchKernelGGL((assembleGroupKernel<16, 6>), g16, dim3(256), 0, st, a);
-        else if (w16 == 5) hipLaunchKernelGGL((assembleGroupKernel<16, 5>), g16, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((assembleGroupKernel<16, 4>), g16, dim3(256), 0, st, a);
-    }
+    if (a.nSmall) hipLaunchKernelGGL((assembleGroupKernel<16, 5>), g16, dim3(256), 0, st, a);
     PH_CHECK(hipEventRecord(ctx->ev[3], st));
     PH_CHECK(hipEventRecord(ctx->ev[4], st));
-    if (a.nMid32) hipLaunchKernelGGL((assembleGroupKernel<32, 5>), dim3(std::min<uint32_t>((a.nMid32 + 7) / 8, (uint32_t) ctx->numCU * 5u * gx)), dim3(256), 0, st, a);      // (4 wavefronts per SIMD: 28.3 against 28.0 ms)
-    if (a.nMid) {
-        if (w64 == 5) hipLaunchKernelGGL((assembleGroupKernel<64, 5>), g64, dim3(256), 0, st, a);
-        else if (w64 == 4) hipLaunchKernelGGL((assembleGroupKernel<64, 4>), g64, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((assembleGroupKernel<64, 3>), g64, dim3(256), 0, st, a);
-    }
+    if (a.nMid32) hipLaunchKernelGGL((assembleGroupKernel<32, 5>), dim3(std::min<uint32_t>((a.nMid32 + 7) / 8, (uint32_t) ctx->numCU * 5u)), dim3(256), 0, st, a);      // (4 wavefronts per SIMD: 28.3 against 28.0 ms)
+    if (a.nMid) hipLaunchKernelGGL((assembleGroupKernel<64, 4>), g64, dim3(256), 0, st, a);
     PH_CHECK(hipEventRecord(ctx->ev[5], st));
     PH_CHECK(hipEventRecord(ctx->ev[6], st));
     DevBuf dDbgRounds, dDbgCycles;
@@ -2228,7 +2217,7 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     // first kernel lists on the device (PLASSHIP_TUNE_ASMQ=2: assembleBigKernel for all of them; PLASSHIP_TUNE_ASMQ_CAP=n: a smaller cap)
     const bool onChip = tuneInt("ASMQ", 1) != 2;
     const uint32_t qCap = (uint32_t) std::max(0, std::min(tuneInt("ASMQ_CAP", (int) ASMQ_CAP), (int) ASMQ_CAP));
-    const dim3 gBig(std::min<uint32_t>((a.nBig + 3) / 4, (uint32_t) ctx->numCU * (uint32_t) tuneInt("ASMBIG", 4)));
+    const dim3 gBig(std::min<uint32_t>((a.nBig + 3) / 4, (uint32_t) ctx->numCU * 4u));
     DevBuf dOverList[2], dOverCount;
     if (a.nBig && onChip) {
         if (dOverList[0].alloc(((size_t) a.nBig + 1) * 4) != hipSuccess || dOverList[1].alloc(((size_t) a.nBig + 1) * 4) != hipSuccess || dOverCount.alloc(8) != hipSuccess) {

@@ -17,6 +17,7 @@
 #include <mutex>
 #include <numeric>
 #include <unordered_map>
+#include <unistd.h>
 
 namespace plasship {
 // ---- device memory arena (see common.hpp) ---------------------------------------------------------------
@@ -198,6 +199,21 @@ int tuneInt(const char *name, int dflt) {
     const char *e = getenv(key); const int v = e ? atoi(e) : 0;
     return v > 0 ? v : dflt;
 }
+// The switches of this build: each is set by a committed test or tool, or turns an optimisation off so that a wrong result can be bisected
+// to a stage or memory be capped (README.md, "Environment switches").  Any other PLASSHIP_TUNE_<x> in the environment is reported once.
+static const char *const TUNE_NAMES[] = {"AGGWAVE", "AGGWAVE_CAP", "ASMQ", "ASMQ_CAP", "ROWTIER", "KMCACHE", "FORCE_LONG", "CYC_PASSES", "CYCSKIP", "SHARD_EXTRACT",
+                                         "FASTA_CHUNK_MB", "DBHEAP", "DBHEAP_GB", "LAZY_SELF"};
+static void reportUnknownTunes() {
+    static const char PREFIX[] = "PLASSHIP_TUNE_";
+    for (char **e = environ; e && *e; e++) {
+        if (strncmp(*e, PREFIX, sizeof(PREFIX) - 1) != 0) continue;
+        const char *x = *e + sizeof(PREFIX) - 1, *eq = strchr(x, '=');
+        const std::string name(x, eq ? (size_t) (eq - x) : strlen(x));
+        bool known = false;
+        for (const char *k : TUNE_NAMES) known = known || name == k;
+        if (!known) fprintf(stderr, "[plasship] PLASSHIP_TUNE_%s is not a switch of this build (ignored)\n", name.c_str());
+    }
+}
 bool traceOn() { static const bool v = getenv("PLASSHIP_TRACE") != nullptr; return v; }
 void setError(const std::string &msg) { g_err = msg; }
 static std::atomic<unsigned long long> g_hostSyncs(0);
@@ -259,6 +275,8 @@ extern "C" const char *plasship_version(void) { return "plasship 0.1 (gfx950)"; 
 
 extern "C" int plasship_ctx_create(int device_ordinal, plasship_ctx **out) {
     if (!out) { setError("plasship_ctx_create: out is NULL"); return PLASSHIP_ERR_ARG; }
+    static std::once_flag tunesChecked;
+    std::call_once(tunesChecked, reportUnknownTunes);
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count == 0) {

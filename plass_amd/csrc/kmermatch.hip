@@ -297,13 +297,12 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
     else PH_CHECK(hipMemsetAsync(dRTag1.p, 0xFF, capR1 * 4, st));                       // nothing to sort: no piece will write the tag array
     PH_CHECK(hipMemcpyAsync(dRNP.p, &nPR1, 4, hipMemcpyHostToDevice, st));
     // grouped records arrive with many records per representative: lines that complete inside a tile are written directly (linepart.hpp)
-    static const int directLines = [] { const char *e = getenv("PLASSHIP_DIRECT_LINES"); return e ? atoi(e) : 1; }();
     LineKey rkey; rkey.rangeBits = repBits; rkey.repBase = repBase; rkey.shift = s1 ? 64 - s1 : 63; rkey.scrambleBits = repBits;      // ranges of the bit-reversed id
     int rc;
     {
         LinePartArgs a; memset(&a, 0, sizeof(a));
         a.in = in; a.out = dR1.p; a.tags = dRTag1.as<uint32_t>(); a.pieces = dRPieces.as<LinePiece>(); a.nPieces = dRNP.as<uint32_t>(); a.nb = nS1; a.key = rkey;
-        a.direct = directLines;
+        a.direct = 1;
         rc = launchLinePart<NUCL, PL, KEY_RANGE, false, false>(ctx, a, std::max<uint32_t>(nPR1, 1)); if (rc) return rc;
     }
     if (nPR1 && !hpPinned) PH_CHECK(plasship::streamSync(st));   // hp goes out of use (async copy of a pageable host vector)
@@ -317,7 +316,7 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
                            dRRegBeg.as<uint64_t>(), dRRegEnd.as<uint64_t>(), dRTot2.as<uint64_t>());
         LinePartArgs a; memset(&a, 0, sizeof(a));
         a.in = dR1.p; a.list = dRList1.as<uint32_t>(); a.out = dR2.p; a.tags = dRTag2.as<uint32_t>(); a.pieces = dRPieces2.as<LinePiece>(); a.nPieces = dRNP2.as<uint32_t>(); a.nb = nS2;
-        a.direct = directLines;
+        a.direct = 1;
         a.key = rkey; a.key.shift = 64 - s1 - s2;
         rc = launchLinePart<NUCL, PL, KEY_RANGE, true, false>(ctx, a, maxPR2); if (rc) return rc;
         hipLaunchKernelGGL(tagSortRegionKernel, dim3(std::min<uint32_t>(nS1, (uint32_t) numCU * 4)), dim3(512), 0, st, (const uint32_t *) dRTag2.as<uint32_t>(), (const uint64_t *) dRRegBeg.as<uint64_t>(),
@@ -346,7 +345,7 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
     // PLASSHIP_TUNE_AGGWAVE_CAP=n shrinks the wave caps to n distinct keys and 16 n record slots (tests: many buckets take the fall-back).
     const bool aggWave = tuneInt("AGGWAVE", 1) != 2;
     const AggLines aggLn{sortList, dSortBeg.as<uint32_t>(), dSortCnt.as<uint32_t>()};
-    const unsigned aggGrid = std::min<uint32_t>(nSort, (uint32_t) numCU * (uint32_t) tuneInt("AGGSORT", 16));
+    const unsigned aggGrid = std::min<uint32_t>(nSort, (uint32_t) numCU * 16u);
     DevBuf dOver;                                             // [0]: buckets over the wave caps, [1 ..]: their list
     const uint32_t *ovList = nullptr, *ovCount = nullptr;
     if (aggWave) {
@@ -357,7 +356,7 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
         wa.ovCount = dOver.as<uint32_t>(); wa.ovList = wa.ovCount + 1; wa.repCnt = dRepCnt.as<uint32_t>();
         ovCount = wa.ovCount; ovList = wa.ovList;
         constexpr int WPB = AggWaveGeo<NUCL>::WPB;
-        const unsigned wGrid = std::min<uint32_t>((nSort + WPB - 1) / WPB, (uint32_t) numCU * (uint32_t) tuneInt("AGGWAVE_GRID", (int) AggWaveGeo<NUCL>::PER_CU));
+        const unsigned wGrid = std::min<uint32_t>((nSort + WPB - 1) / WPB, (uint32_t) numCU * (uint32_t) AggWaveGeo<NUCL>::PER_CU);
         hipLaunchKernelGGL((aggSortWaveKernel<NUCL, LONG, TRIPLES, ORDOUT>), dim3(wGrid), dim3(WPB * 64), 0, st, sortRecs, dSparse.p, nSort, dUnique.as<uint32_t>(),
                            repBits - sBits, idBits, (uint64_t) repBase, aggLn, repBits, wa);
     }
@@ -553,7 +552,7 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
         if (geo.nb2) arenaBuf = dRx.p;
         else { if (dArena.alloc(std::max<uint64_t>(finalCap, 1) * RPL * sizeof(R)) != hipSuccess) { setError("kmermatch: out of device memory for the grouped records"); return PLASSHIP_ERR_DEVICE; } arenaBuf = dArena.p; }
     } else arenaBuf = geo.nb2 ? dB.p : dA.p;
-    const uint32_t gBlocks = std::max<uint32_t>(1, std::min<uint32_t>(nBuckets, (uint32_t) numCU * (uint32_t) tuneInt("GROUP", 24)));      // (6 until round 6; with the look-ahead 24 measures 1 ms better at 50 M reads — smaller arenas for the rep sort: profiles/r06_ab_knobs.txt, call 26)
+    const uint32_t gBlocks = std::max<uint32_t>(1, std::min<uint32_t>(nBuckets, (uint32_t) numCU * 24u));      // (6 until round 6; with the look-ahead 24 measures 1 ms better at 50 M reads — smaller arenas for the rep sort: profiles/r06_ab_knobs.txt, call 26)
     const uint32_t bpb = (std::max<uint32_t>(nBuckets, 1) + gBlocks - 1) / gBlocks;
     const uint32_t gGrid = (std::max<uint32_t>(nBuckets, 1) + bpb - 1) / bpb;
     DevBuf dOutCnt, dArenaStart, dMaxRT, dLastRun;
@@ -566,13 +565,10 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
     ga.includeOnlyExtendable = par->include_only_extendable; ga.covMode = par->cov_mode; ga.covThr = par->cov_thr; ga.minKey = NUCL ? dMinKey.as<unsigned long long>() : nullptr;
     // positions per bucket (sentinel padding included) decide the workgroup shape of the 16-byte-record kernel
     const uint64_t avgPos = finalCap * RPL / std::max<uint32_t>(nBuckets, 1);
-    const bool wideGroup = !LONG && (getenv("PLASSHIP_GROUP_WIDE") ? atoi(getenv("PLASSHIP_GROUP_WIDE")) != 0 : avgPos > 1600);
+    const bool wideGroup = !LONG && avgPos > 1600;
     if (nBuckets == 0) PH_CHECK(hipMemsetAsync(dOutCnt.p, 0, (size_t) gGrid * 8, st));
     else if constexpr (LONG) hipLaunchKernelGGL((groupKernel<NUCL, LONG, true>), dim3(gGrid), dim3(GR_BLOCK), 0, st, ga);
-    else if (wideGroup && tuneInt("GROUP_WPE", 4) == 4 && tuneInt("GROUP_LAHEAD", 1) == 1) hipLaunchKernelGGL((groupLinesKernel<NUCL, 512, 4096, 4, true>), dim3(gGrid), dim3(512), 0, st, ga);      // PLASSHIP_TUNE_GROUP_LAHEAD=2: without the list look-ahead
-    else if (wideGroup && tuneInt("GROUP_WPE", 4) == 4) hipLaunchKernelGGL((groupLinesKernel<NUCL, 512, 4096, 4>), dim3(gGrid), dim3(512), 0, st, ga);
-    else if (wideGroup) hipLaunchKernelGGL((groupLinesKernel<NUCL, 512, 4096, 2>), dim3(gGrid), dim3(512), 0, st, ga);
-    else if (tuneInt("GROUP_LAHEAD", 1) == 1) hipLaunchKernelGGL((groupLinesKernel<NUCL, GR_BLOCK, GR_HT, 3, true>), dim3(gGrid), dim3(GR_BLOCK), 0, st, ga);
+    else if (wideGroup) hipLaunchKernelGGL((groupLinesKernel<NUCL, 512, 4096, 4>), dim3(gGrid), dim3(512), 0, st, ga);
     else hipLaunchKernelGGL((groupLinesKernel<NUCL, GR_BLOCK, GR_HT, 3>), dim3(gGrid), dim3(GR_BLOCK), 0, st, ga);
     if (nBuckets) hipLaunchKernelGGL(arenaStartKernel, dim3(gridFor(gGrid, 256, 64)), dim3(256), 0, st, (const uint32_t *) dFineBeg.as<uint32_t>(), bpb, gGrid, nBuckets, dArenaStart.as<uint64_t>());
     else PH_CHECK(hipMemsetAsync(dArenaStart.p, 0, (size_t) gGrid * 8, st));
@@ -920,12 +916,11 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     ea.seed = (uint64_t) par->hash_shift; ea.overflowIds = dOvIds.as<uint32_t>(); ea.overflowCount = dOvCnt.as<uint32_t>();
     ea.idLo = sLo; ea.idHi = sHi; ea.slotBias = slotBias;
     // candidate k-mers per sequence held in LDS.  128 covers every protein sequence (59 considered k-mers) and every
-    // nucleotide sequence up to ~690 nt (59 + 0.1 L); the 1024-candidate instantiation (35 KB of LDS, one wavefront per SIMD)
-    // only sees the longer nucleotide contigs, queued by the first launch; what does not fit there either goes to the
+    // nucleotide sequence up to ~690 nt (59 + 0.1 L); longer nucleotide contigs, queued by the first launches, get 512 candidates
+    // in the 48-scores tier (CAP48 below) and 1024 in the three-pass tier (CAP2); what does not fit there either goes to the
     // HBM-scratch launch.
     constexpr int CAP = 128, CAP2 = NUCL ? 1024 : 128;
     DevBuf dWaveList, dWaveCount, dLongList, dLongCount, dKStats;
-    static const bool tier0 = [] { const char *e = getenv("PLASSHIP_TIER0"); return e ? atoi(e) != 0 : true; }();
     constexpr uint32_t TIER0_WINDOWS = 256;                  // 4 scores per lane (an 8-scores tier at 5 wavefronts per SIMD gained 0.3 %: not kept)
     if (dWaveList.alloc(((size_t) N + 1) * 4) != hipSuccess || dWaveCount.alloc(4) != hipSuccess || dLongList.alloc(((size_t) N + 1) * 4) != hipSuccess || dLongCount.alloc(4) != hipSuccess ||
         dKStats.alloc(64) != hipSuccess) { setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE; }
@@ -946,7 +941,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     // The lines are only worth their N x 128 bytes (11 GB at 88 M sequences) when a later call can use them: a DB that was DERIVED from another
     // one (a chained iteration), or a context that has made an eligible call before (a single `plass-hip kmermatcher` call on a DB
     // read from files paid for them in memory and in 128-byte stores per long sequence for nothing)
-    const bool cacheWanted = cacheEligible && N && (cacheReuse || db->parentGen != 0 || db->ancestorGen != 0 || kc.seenEligible || tuneInt("KMCACHE_EAGER", 0) == 1);
+    const bool cacheWanted = cacheEligible && N && (cacheReuse || db->parentGen != 0 || db->ancestorGen != 0 || kc.seenEligible);
     if (cacheEligible) kc.seenEligible = true;
     if (cacheWanted) {
         if (kc.lines.bytes < (size_t) N * KMC_LINE) { kc.lines.release(); if (kc.lines.allocLong((size_t) N * KMC_LINE) != hipSuccess) { setError("kmermatch: out of device memory for the selected-window cache"); return PLASSHIP_ERR_DEVICE; } }
@@ -959,11 +954,11 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     // ---- position cache of nucleotide runs (kmermatch_extract.hpp section 2d) ----
     typedef typename std::conditional<LONG, uint32_t, unsigned short>::type PosT;
     plasship_ctx::KmPosCache &pc = ctx->kmPosCache;
-    const bool posEligible = NUCL && !cm && N && tier0 && tuneInt("CLASSIFY", 1) == 1 && tuneInt("KMCACHE", 1) == 1;      // PLASSHIP_TUNE_KMCACHE=2 switches it off
+    const bool posEligible = NUCL && !cm && N && tuneInt("KMCACHE", 1) == 1;      // PLASSHIP_TUNE_KMCACHE=2 switches it off
     bool posReuse = posEligible && pc.valid && pc.gen != 0 && db->originGen == pc.gen && db->d_origin.p && pc.lng == LONG && pc.k == k && pc.kps == par->kmers_per_seq &&
                           pc.scale == par->kmers_per_seq_scale && pc.ignoreMulti == par->ignore_multi_kmer && pc.hashShift == par->hash_shift;
     // (like the lines of section 2c, the positions are only written when a later call can use them: a derived DB, or a context that has run kmermatcher before)
-    bool posWanted = posEligible && (posReuse || db->parentGen != 0 || db->ancestorGen != 0 || db->originGen != 0 || pc.seen || ctx->kmermatchCalls > 0 || tuneInt("KMCACHE_EAGER", 0) == 1);
+    bool posWanted = posEligible && (posReuse || db->parentGen != 0 || db->ancestorGen != 0 || db->originGen != 0 || pc.seen || ctx->kmermatchCalls > 0);
     if (posEligible) pc.seen = true;
     ctx->kmermatchCalls++;
     DevBuf dPosNew, dIdHashNew;
@@ -980,7 +975,6 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     }
     PH_CHECK(hipMemcpyAsync(dKStats.as<unsigned long long>() + 4, cachePtrs, 24, hipMemcpyHostToDevice, st));      // (cachePtrs lives until the function's last wait)
     PH_CHECK(hipEventRecord(ctx->ev[2], st));
-    bool twoLists = false;
     if (!NUCL && k <= 16 && nMine) {
         // short sequences: one thread each; everything else is queued for the wave-per-sequence kernels, in two lists by length
         ShortArgs sa; memset(&sa, 0, sizeof(sa));
@@ -988,36 +982,33 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         sa.scale = ea.scale; sa.seed = ea.seed; sa.base = (uint64_t) (alph - 1); sa.top = ea.powers[k - 1];
         { uint64_t b = sa.base; int tz = 0; while ((b & 1) == 0) { b >>= 1; tz++; } uint64_t inv = b; for (int i = 0; i < 6; i++) inv *= 2 - b * inv; sa.tz = tz; sa.inv = inv; }
         sa.waveList = dWaveList.as<uint32_t>(); sa.waveCount = dWaveCount.as<uint32_t>(); sa.kstats = dKStats.as<unsigned long long>();
-        if (tier0) {
-            sa.longList = dLongList.as<uint32_t>(); sa.longCount = dLongCount.as<uint32_t>(); sa.longWindows = TIER0_WINDOWS; twoLists = true;
-            // more than 16 scores per lane: straight into the queue the 48-scores tier reads (tiers 0 and 1 append their rare overflows
-            // to the same queue, one atomic per sequence)
-            sa.hugeList = dOvIds.as<uint32_t>(); sa.hugeCount = dOvCnt.as<uint32_t>(); sa.hugeWindows = 64 * 16;
-        }
+        sa.longList = dLongList.as<uint32_t>(); sa.longCount = dLongCount.as<uint32_t>(); sa.longWindows = TIER0_WINDOWS;
+        // more than 16 scores per lane: straight into the queue the 48-scores tier reads (tiers 0 and 1 append their rare overflows
+        // to the same queue, one atomic per sequence)
+        sa.hugeList = dOvIds.as<uint32_t>(); sa.hugeCount = dOvCnt.as<uint32_t>(); sa.hugeWindows = 64 * 16;
         sa.idLo = sLo; sa.idHi = sHi; sa.slotBias = slotBias;
         if (cacheReuse) { sa.changed = db->d_changed.as<unsigned char>(); sa.cachedList = dCachedList.as<uint32_t>(); sa.cachedCount = dCachedCount.as<uint32_t>(); }
         // the fast restatement needs k = 14 and the half-indices (7 digits of the base, each at most the X code = base) in 32 bits
         constexpr int KF = 14, HF = KF / 2;
-        bool fast = k == KF && tuneInt("SHORT_FAST", 1) == 1;      // PLASSHIP_TUNE_SHORT_FAST=2: the kernel above
+        bool fast = k == KF;
         uint64_t pwH = 1; for (int i = 0; i < HF; i++) pwH *= sa.base;
         if (pwH * 2 >= (1ull << 32)) fast = false;
         sa.topLo = (uint32_t) (pwH / sa.base); sa.topHi = (uint32_t) ea.powers[KF - HF - 1]; sa.baseH = (uint32_t) pwH;
-        const dim3 shortGrid(std::min<uint32_t>((nMine + 63) / 64, (uint32_t) ctx->numCU * (uint32_t) tuneInt("SHORT", nMine > 20000000u ? 288 : 18)));
+        const dim3 shortGrid(std::min<uint32_t>((nMine + 63) / 64, (uint32_t) ctx->numCU * (nMine > 20000000u ? 288u : 18u)));
         // Resident wavefronts (round 4): every working lane has one partly written 128-byte line of records open; at the 18 wavefronts per CU
         // the kernel's own LDS allows, those are 4.7 MB per XCD against 4 MB of L2 — lines leave the L2 half written and the kernel moves
         // 71 GB for 35 GB of records (profiles/r03_pmc_hbm_traffic.txt).  Unused dynamic LDS caps the residency: 8 KB more per wavefront
         // (10 per CU) took 34.6 -> 29.9 ms off iteration 0 and 28.4 -> 24.2 off iteration 1; with 16 KB (6 per CU) iteration 0, where
         // every lane works, fell to 26.4 ms but the later iterations, where most lanes only queue their sequence, rose by 4-6 ms
-        // (profiles/r04_ab_knobs.txt, call 18).  PLASSHIP_TUNE_SHORT_PAD_KB overrides (1 = none).
+        // (profiles/r04_ab_knobs.txt, call 18).
         const bool allWork = (int64_t) db->maxEntryLen - 2 - k + 1 <= (int64_t) par->kmers_per_seq - 1;      // no sequence long enough to be queued for the wave kernels
-        const int padKb = tuneInt("SHORT_PAD_KB", allWork ? 16 : 8);
-        const size_t padLds = padKb > 1 ? (size_t) padKb << 10 : 0;
-        // records through LDS (extractShortFastKernel<..., STAGE>; 1: on, no residency pad; 3: on, with the pad; 2: off): measured at 50 M reads (profiles/r06_ab_knobs.txt,
+        const size_t padLds = (size_t) (allWork ? 16 : 8) << 10;
+        // records through LDS (extractShortFastKernel<..., STAGE>, without the residency pad): measured at 50 M reads (profiles/r06_ab_knobs.txt,
         // call 15) it takes 2.8 ms off iteration 0, where every lane works (30.5 -> 27.7 ms), and costs 1.5-2 ms in the later iterations, where a third of
         // the lanes only queue their sequence and the flushes' barriers are paid for fewer records -> on exactly when no sequence can be queued
-        const int stageMode = LONG ? 0 : tuneInt("SHORT_STAGE", allWork ? 1 : 2);
-        if (fast && sa.base < (1u << 8) && sa.topLo < (1u << 24) && sa.topHi < (1u << 24) && (stageMode == 1 || stageMode == 3)) {
-            if constexpr (!LONG) hipLaunchKernelGGL((extractShortFastKernel<LONG, KF, true, true>), shortGrid, dim3(64), stageMode == 3 ? padLds : 0, st, sa);
+        const bool staged = !LONG && allWork;
+        if (fast && sa.base < (1u << 8) && sa.topLo < (1u << 24) && sa.topHi < (1u << 24) && staged) {
+            if constexpr (!LONG) hipLaunchKernelGGL((extractShortFastKernel<LONG, KF, true, true>), shortGrid, dim3(64), 0, st, sa);
         }
         else if (fast && sa.base < (1u << 8) && sa.topLo < (1u << 24) && sa.topHi < (1u << 24)) hipLaunchKernelGGL((extractShortFastKernel<LONG, KF, true>), shortGrid, dim3(64), padLds, st, sa);
         else if (fast) hipLaunchKernelGGL((extractShortFastKernel<LONG, KF, false>), shortGrid, dim3(64), 0, st, sa);
@@ -1028,22 +1019,21 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
             ca.s = ea.s; ca.slotOff = ea.slotOff; ca.arr = ea.arr; ca.map = ea.map; ca.lines = kc.lines.as<unsigned char>();
             ca.list = dCachedList.as<uint32_t>(); ca.count = dCachedCount.as<uint32_t>(); ca.k = k; ca.xCode = ea.xCode;
             ca.base = (uint32_t) ea.powers[1]; ca.base7 = (uint32_t) ea.powers[7]; ca.slotBias = slotBias; ca.seed = ea.seed; ca.kstats = dKStats.as<unsigned long long>();
-            hipLaunchKernelGGL(extractCachedKernel, dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * (uint32_t) tuneInt("CACHED", 32))), dim3(64), 0, st, ca);
+            hipLaunchKernelGGL(extractCachedKernel, dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * 32u)), dim3(64), 0, st, ca);
         }
     }
-    else if (nMine && tier0 && tuneInt("CLASSIFY", 1) == 1) {                   // PLASSHIP_TUNE_CLASSIFY=2: the 16-scores tier takes every id itself
+    else if (nMine) {
         hipLaunchKernelGGL(classifyWindowsKernel, dim3(std::min<uint32_t>((nMine + 2047) / 2048, (uint32_t) ctx->numCU * 8)), dim3(256), 0, st, (const uint32_t *) db->d_len.as<uint32_t>(), sLo, sHi, (uint32_t) k,
                            TIER0_WINDOWS, 64u * 16u, dWaveList.as<uint32_t>(), dWaveCount.as<uint32_t>(), dLongList.as<uint32_t>(), dLongCount.as<uint32_t>(), dOvIds.as<uint32_t>(), dOvCnt.as<uint32_t>(),
                            posReuse ? (const uint32_t *) db->d_origin.as<uint32_t>() : (const uint32_t *) nullptr, dCachedList.as<uint32_t>(), dCachedCount.as<uint32_t>());
         ea.waveList = dWaveList.as<uint32_t>(); ea.waveCount = dWaveCount.as<uint32_t>();
-        twoLists = true;
         if constexpr (NUCL) {
             if (posReuse) {      // entries the position cache describes: their records rebuilt from the cached window positions
                 CachedPosArgs<LONG> ca; memset(&ca, 0, sizeof(ca));
                 ca.s = ea.s; ca.slotOff = ea.slotOff; ca.arr = ea.arr; ca.map = ea.map; ca.posOld = pc.pos.p; ca.slotOffOld = pc.slotOff.as<uint64_t>();
                 ca.idHashOld = pc.idHash.as<unsigned long long>(); ca.origin = db->d_origin.as<uint32_t>(); ca.posNew = dPosNew.p; ca.idHashNew = dIdHashNew.as<unsigned long long>();
                 ca.list = dCachedList.as<uint32_t>(); ca.count = dCachedCount.as<uint32_t>(); ca.k = k; ca.seed = ea.seed; ca.kstats = dKStats.as<unsigned long long>();
-                hipLaunchKernelGGL((extractCachedPosKernel<LONG>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * (uint32_t) tuneInt("CACHEDPOS", 32))), dim3(64), 0, st, ca);
+                hipLaunchKernelGGL((extractCachedPosKernel<LONG>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * 32u)), dim3(64), 0, st, ca);
             }
         }
     }
@@ -1052,13 +1042,12 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     // one-wavefront workgroups per CU of the register tiers' grids.  32 was measured best of 12..64 on the 1 M-read set; on the 50 M-read chain
     // (round 6, profiles/r06_ab_knobs.txt call 7) a CU holds 20 / 16 of them at once and a grid of 32 leaves a second, 60 %-filled round: 40: 57.5 ms
     // for the wave tiers per iteration, 64: 55.8, 96: 54.5, 128: 54.1, 192: 53.7, 256: 53.7, 512: 54.7 against 58.1 at 32 -> 192 for large sets
-    static const int waveBlocksEnv = [] { const char *e = getenv("PLASSHIP_EXTRACT_BLOCKS_PER_CU"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
-    const int waveBlocksPerCU = waveBlocksEnv ? waveBlocksEnv : (nMine > 5000000u ? 192 : 32);
+    const int waveBlocksPerCU = nMine > 5000000u ? 192 : 32;
     // launch chain, each tier queueing what it cannot hold for the next: (1) register front end, up to 1024 windows (every read,
     // most contigs); (2) the same with 48 scores per lane, up to 3072 windows (proteins longer than that are rare) and, for
-    // nucleotides, up to 1024 candidates; (3) three-pass path with codes and scores of up to 8160 residues resident in LDS;
+    // nucleotides, up to 512 candidates; (3) three-pass path with codes and scores of up to 8160 residues resident in LDS;
     // (4) the HBM-scratch launch below
-    // (0) the same register front end with 4 scores per lane (up to 256 windows: merged read fragments and young contigs) at six
+    // (0) the same register front end with 4 scores per lane (up to 256 windows: merged read fragments and young contigs) at five
     // wavefronts per SIMD instead of four: the per-sequence steps (staging, ballots, LDS round trips between barriers) are what a
     // 100-250 residue sequence mostly consists of, and more resident wavefronts hide them (2.1 instead of 2.8 ns per sequence).
     // Tiers 0 and 1 take their sequences from the two lists of the thread-per-sequence kernel; what either cannot hold goes to
@@ -1074,7 +1063,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         // repeat) is queued for the 4-scores tier, which reads that queue instead of the list
         ExtractArgs e0 = ea;
         DevBuf dRowLists, dRowCounts, dRowFall, dRowFallCnt;
-        const bool rowTier = !NUCL && !LONG && twoLists && ea.waveList == dWaveList.as<uint32_t>() && fastIndex && k <= 14 && par->kmers_per_seq >= 1 && par->kmers_per_seq <= (int) KMC_POS + 1 &&
+        const bool rowTier = !NUCL && !LONG && fastIndex && k <= 14 && par->kmers_per_seq >= 1 && par->kmers_per_seq <= (int) KMC_POS + 1 &&
                              par->kmers_per_seq_scale == 0.0f && (tuneInt("ROWTIER", nMine > 4000000u ? 1 : 2) & 1) == 1;      // PLASSHIP_TUNE_ROWTIER=2: the 4-scores tier takes the whole list; 3: rows whatever the size
         // (large sets only: at 1 M reads the five extra launches in a row — each a chain of dependent round trips with the chip a tenth full — cost the
         //  wave tiers 0.35 ms per iteration, 1.64 -> 1.99 ms; at 12.5 M reads the rows win 1.9 ms, at 50 M 5.8: profiles/r06_ab_knobs.txt)
@@ -1091,38 +1080,34 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
             ra.s = ea.s; ra.slotOff = ea.slotOff; ra.arr = ea.arr; ra.map = ea.map; ra.fallList = dRowFall.as<uint32_t>(); ra.fallCount = dRowFallCnt.as<uint32_t>();
             ra.k = k; ra.xCode = ea.xCode; ra.kps = ea.kps; ra.ignoreMulti = ea.ignoreMulti; ra.seed = ea.seed; ra.base = (uint32_t) ea.powers[1]; ra.base7 = (uint32_t) ea.powers[7];
             ra.slotBias = slotBias; ra.kstats = dKStats.as<unsigned long long>();
-            const dim3 rowGrid(std::min<uint32_t>((nMine + 3) / 4, (uint32_t) ctx->numCU * (uint32_t) tuneInt("ROWGRID", 32)));
-            const bool w5 = tuneInt("ROW_WPE", 4) == 5;
+            const dim3 rowGrid(std::min<uint32_t>((nMine + 3) / 4, (uint32_t) ctx->numCU * 32u));
             for (int b = 0; b < 4; b++) {
                 ra.list = dRowLists.as<uint32_t>() + (size_t) b * rs; ra.count = dRowCounts.as<uint32_t>() + b;
-                if (b == 0) { if (w5) hipLaunchKernelGGL((extractRowKernel<6, 5>), rowGrid, dim3(64), 0, st, ra); else hipLaunchKernelGGL((extractRowKernel<6, 4>), rowGrid, dim3(64), 0, st, ra); }
-                else if (b == 1) { if (w5) hipLaunchKernelGGL((extractRowKernel<8, 5>), rowGrid, dim3(64), 0, st, ra); else hipLaunchKernelGGL((extractRowKernel<8, 4>), rowGrid, dim3(64), 0, st, ra); }
-                else if (b == 2) hipLaunchKernelGGL((extractRowKernel<12, 4>), rowGrid, dim3(64), 0, st, ra);
-                else hipLaunchKernelGGL((extractRowKernel<16, 4>), rowGrid, dim3(64), 0, st, ra);
+                if (b == 0) hipLaunchKernelGGL((extractRowKernel<6>), rowGrid, dim3(64), 0, st, ra);
+                else if (b == 1) hipLaunchKernelGGL((extractRowKernel<8>), rowGrid, dim3(64), 0, st, ra);
+                else if (b == 2) hipLaunchKernelGGL((extractRowKernel<12>), rowGrid, dim3(64), 0, st, ra);
+                else hipLaunchKernelGGL((extractRowKernel<16>), rowGrid, dim3(64), 0, st, ra);
             }
             e0.waveList = dRowFall.as<uint32_t>(); e0.waveCount = dRowFallCnt.as<uint32_t>();
         }
         // tiers 0 and 1 both queue into dOvIds
-        if (twoLists) {
-            // (round 5: tiers 0 and 1 — disjoint lists — and the cached kernel side by side on three streams: extraction 81.7 against 81.2 ms
-            //  per iteration, nothing gained; profiles/r05_ab_knobs.txt)
-            if (tuneInt("TIER0_WPE", 5) == 6) hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 4, 256, 6>), dim3(wide), dim3(64), 0, st, e0);
-            else hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 4, 256>), dim3(wide), dim3(64), 0, st, e0);
-            ExtractArgs e1 = ea; e1.waveList = dLongList.as<uint32_t>(); e1.waveCount = dLongCount.as<uint32_t>();
-            hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 16, 992>), dim3(wide), dim3(64), 0, st, e1);
-        } else hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 16, 992>), dim3(wide), dim3(64), 0, st, ea);
+        // (round 5: tiers 0 and 1 — disjoint lists — and the cached kernel side by side on three streams: extraction 81.7 against 81.2 ms
+        //  per iteration, nothing gained; profiles/r05_ab_knobs.txt)
+        hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 4, 256>), dim3(wide), dim3(64), 0, st, e0);
+        ExtractArgs e1 = ea; e1.waveList = dLongList.as<uint32_t>(); e1.waveCount = dLongCount.as<uint32_t>();
+        hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 16, 992>), dim3(wide), dim3(64), 0, st, e1);
         ExtractArgs e2 = ea; e2.waveList = dOvIds.as<uint32_t>(); e2.waveCount = dOvCnt.as<uint32_t>();
         e2.overflowIds = dOv2Ids.as<uint32_t>(); e2.overflowCount = dOv2Cnt.as<uint32_t>();
         // (round 4: a nucleotide sequence of this tier has at most 3 072 windows, i.e. 60 + 0.1 L <= 370 selected k-mers at the workflow's
         //  scaling: 512 candidates instead of 1 024 halve its LDS and let eight instead of four wavefronts work per CU; a candidate set
         //  that does not fit is queued for the next tier like any other overflow)
         constexpr int CAP48 = NUCL ? 512 : 128;
-        if (NUCL && tuneInt("NUCL_CAP48", 1) == 1) hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP48, false, 48, 992, NUCL ? 2 : 0>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * (uint32_t) tuneInt("TIER2", 8))), dim3(64), 0, st, e2);
-        else hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP2, false, 48, 992>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * (uint32_t) tuneInt("TIER2", NUCL ? 4 : 16))), dim3(64), 0, st, e2);
+        if constexpr (NUCL) hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP48, false, 48, 992, 2>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * 8u)), dim3(64), 0, st, e2);
+        else hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP2, false, 48, 992>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * 16u)), dim3(64), 0, st, e2);
         PH_CHECK(hipMemsetAsync(dOvCnt.p, 0, 4, st));            // tier 2 has consumed the first queue: it becomes tier 3's output queue
         ExtractArgs e3 = ea; e3.waveList = dOv2Ids.as<uint32_t>(); e3.waveCount = dOv2Cnt.as<uint32_t>();
         e3.overflowIds = dOvIds.as<uint32_t>(); e3.overflowCount = dOvCnt.as<uint32_t>();
-        hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP2, false, 0, 8160>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * (uint32_t) tuneInt("TIER3", NUCL ? 2 : 5))), dim3(64), 0, st, e3);
+        hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP2, false, 0, 8160>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * (NUCL ? 2u : 5u))), dim3(64), 0, st, e3);
     }
     // what the last stage could not hold either (candidate sets beyond LDS)
     DevBuf &dLastIds = *lastIds, &dLastCnt = *lastCnt;

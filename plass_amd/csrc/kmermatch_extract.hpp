@@ -1187,8 +1187,8 @@ __global__ __launch_bounds__(256) void binWaveListKernel(const uint32_t *__restr
     }
 }
 
-template <int REGS, int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void extractRowKernel(RowArgs a) {
+template <int REGS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void extractRowKernel(RowArgs a) {
     constexpr uint32_t MAXWIN = 16u * REGS, MAXL = MAXWIN + 13u;           // k <= 14
     constexpr uint32_t ROWB = (MAXL + 31u + 15u) & ~15u;                    // staged codes of a row, X padding included
     constexpr bool TWO = MAXL > 256u;                                       // a second 16-byte chunk per lane

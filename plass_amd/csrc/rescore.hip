@@ -458,7 +458,7 @@ int finishSelfAlns(plasship_ctx *ctx, const plasship_alns *al, const uint32_t *d
     a.covMode = par.cov_mode; a.covThr = par.cov_thr; a.seqIdThr = par.seq_id_thr; a.alnLenThr = par.min_aln_len; a.seqIdMode = par.seq_id_mode;
     a.lambda = ev.g[0]; a.logK = ev.logK; a.ln2 = ev.ln2; a.stats = dStats.as<unsigned long long>();
     a.longList = dLongList.as<unsigned long long>(); a.longCount = dLongCount.as<unsigned long long>();
-    a.shortMax = (uint32_t) tuneInt("RESCORE_SHORT", (int) RS_SHORT_MAX);
+    a.shortMax = RS_SHORT_MAX;
     a.mode = dQueryList ? 2 : 1; a.lazySelf = 0; a.queryList = dQueryList; a.nQueryList = nQueryList;
     const uint64_t work = dQueryList ? (uint64_t) nQueryList : n;
     if (work) {
@@ -528,19 +528,16 @@ extern "C" int plasship_rescore(plasship_ctx *ctx, const plasship_seqdb *qdb, co
     if (dLongList.alloc(std::max<uint64_t>(nHits, 1) * 8) != hipSuccess || dLongCount.alloc(8) != hipSuccess) { setError("plasship_rescore: out of device memory"); return PLASSHIP_ERR_DEVICE; }
     PH_CHECK(hipMemsetAsync(dLongCount.p, 0, 8, ctx->stream));
     a.longList = dLongList.as<unsigned long long>(); a.longCount = dLongCount.as<unsigned long long>();
-    a.shortMax = (uint32_t) tuneInt("RESCORE_SHORT", (int) RS_SHORT_MAX);
+    a.shortMax = RS_SHORT_MAX;
     a.mode = 0; a.lazySelf = tuneInt("LAZY_SELF", 1) == 1 ? 1 : 0;      // PLASSHIP_TUNE_LAZY_SELF=2: every identity pair scored here (rounds 1-4)
-    const unsigned grid = (unsigned) std::min<uint64_t>((nHits + 255) / 256 + 1, (uint64_t) ctx->numCU * (uint64_t) tuneInt("RESCORE", nHits > 50000000ull ? 32 : 12));   // large lists: smaller shares per workgroup even out the tail (37.8 -> 35.9 ms at 250 M pairs)
+    const unsigned grid = (unsigned) std::min<uint64_t>((nHits + 255) / 256 + 1, (uint64_t) ctx->numCU * (nHits > 50000000ull ? 32u : 12u));   // large lists: smaller shares per workgroup even out the tail (37.8 -> 35.9 ms at 250 M pairs)
     PH_CHECK(hipEventRecord(ctx->ev[0], ctx->stream));
     // wavefronts per SIMD of the thread-per-pair kernel (registers against chains in flight).  Round 5: 4 — with the stub and finishing paths
     // the kernel spills 88 bytes per lane at 5 (96 VGPRs) and nothing at 4 (125): 35.5 -> 31.2 ms per iteration at 50 M reads; 3: 33.2, 6: 43.9
     // (profiles/r05_ab_knobs.txt, calls 12-13)
-    static const int wpe = [] { const int v = tuneInt("RESCORE_WPE", 4); if (v < 4 || v > 6) fprintf(stderr, "[plasship] PLASSHIP_TUNE_RESCORE_WPE=%d: only 4, 5 and 6 are built, using 4\n", v); return v; }();
     // (16 or 8 lanes per pair for EVERY pair, and a second thread-per-pair pass for the overlaps of 128-512 columns, were both
     // slower — 76 / 53 ms and 83 ms against 45 ms per iteration at 50 M reads: profiles/r03_ab_knobs.txt)
-    if (wpe == 5) hipLaunchKernelGGL((rescoreKernel<1, 5, 0>), dim3(grid), dim3(RS_BLOCK), 0, ctx->stream, a);
-    else if (wpe == 6) hipLaunchKernelGGL((rescoreKernel<1, 6, 0>), dim3(grid), dim3(RS_BLOCK), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((rescoreKernel<1, 4, 0>), dim3(grid), dim3(RS_BLOCK), 0, ctx->stream, a);
+    hipLaunchKernelGGL((rescoreKernel<1, 4, 0>), dim3(grid), dim3(RS_BLOCK), 0, ctx->stream, a);
     hipLaunchKernelGGL((rescoreKernel<16, 6>), dim3((unsigned) ctx->numCU * 8), dim3(RS_BLOCK), 0, ctx->stream, a);     // long overlaps (count read on the device)
     PH_CHECK(hipEventRecord(ctx->ev[1], ctx->stream));
     // the list stays SPARSE (common.hpp: plasship_alns): record h belongs to candidate pair h, the CSR is the candidate list's
