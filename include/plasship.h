@@ -382,6 +382,43 @@ typedef struct plasship_merge_stats {
 int plasship_mergereads(plasship_ctx *ctx, const char *const *fastq, size_t n_files, const plasship_merge_params *par,
                         plasship_seqdb **reads, plasship_seqdb **headers, plasship_merge_stats *stats);
 
+/* ---- createdb for reads  (replaces int createdb(int, const char**, const Command&), lib/mmseqs/src/util/createdb.cpp:15-333, as the workflows
+ *      run it on unpaired input, data/assemble.sh:27-38: a single-end library, merged reads, FASTA).  `files`: FASTQ or FASTA, plain or .gz
+ *      (by file name), the format of each file decided by its first byte; the entries of all files are counted through.  The host only reads
+ *      (or gunzips) the bytes; line structure, validation, kseq's name / comment split, the shuffle permutation and the placement of every
+ *      "SEQ\n\0" and header entry run on the device (createdb.hip).  `out_reads`: the read DB (dbtype 1) in the canonical layout — one data
+ *      file in key order, what plasship_seqdb_read makes of the reference's files.
+ *      shuffle (default 1, createdb.cpp:60,219,275-277): entry i goes to split (id_offset + i) % 32, the splits are concatenated and renumbered
+ *      0..n-1; shuffle 0: key id_offset + i in input order.  dbtype: 0 = from the first 10 entries like the reference (createdb.cpp:171-200),
+ *      2 = nucleotides.  Case is kept, an empty sequence is an entry "\n\0".
+ *      PLASSHIP_ERR_UNSUPPORTED before anything is computed or written for what the reference reads and this path does not: "stdin", .bz2,
+ *      amino-acid input (dbtype 1, or what the probe finds), multi-line FASTQ, a FASTQ sequence line starting with '>', '@' or '+', FASTA with
+ *      lines starting with '@' or '+', a file that starts with neither '>' nor '@'.  PLASSHIP_ERR_IO with the file and the record number
+ *      for a FASTQ that is broken (a record without '@' or '+', a quality string of another length than the sequence, a quality byte >= 128)
+ *      and for an entry without a name (the reference exits there too).  par may be NULL (the reference's defaults).
+ *      plasship_createdb_write is the stand-alone command: the same, and <db_path>, .index, .dbtype, <db_path>_h, _h.index, _h.dbtype,
+ *      .lookup and .source written as the reference writes them (createdb.cpp:84,121,291-329); out_reads may be NULL there. ---------- */
+typedef struct plasship_createdb_params {
+    int32_t shuffle;              /* 1                                                                                      */
+    uint32_t id_offset;           /* 0                                                                                      */
+    int32_t dbtype;               /* 0 = auto, 1 = amino acids (refused), 2 = nucleotides                                   */
+} plasship_createdb_params;
+typedef struct plasship_createdb_stats {
+    uint64_t entries, files, chunks;  /* chunks: pieces the raw bytes went to the device in (PLASSHIP_TUNE_FASTQ_CHUNK_KB)  */
+    uint64_t bytes_in;            /* raw (decompressed) bytes parsed                                                        */
+    uint64_t bytes_out;           /* bytes of the read DB and the header DB                                                 */
+    uint64_t lines;
+    float ms_read;                /* host: pread / gunzip of the files                                                      */
+    float ms_upload;              /* host -> device copies of the chunks, the newline count of chunk c running under copy c+1 */
+    float ms_kernel;              /* HIP events around the kernels behind the last chunk (lines, records, placement, write) */
+    float ms_write_kernel;        /* of these: the kernel that writes the entries                                           */
+    float ms_total;
+} plasship_createdb_stats;
+int plasship_createdb(plasship_ctx *ctx, const char *const *files, size_t n_files, const plasship_createdb_params *par,
+                      plasship_seqdb **out_reads, plasship_createdb_stats *stats);
+int plasship_createdb_write(plasship_ctx *ctx, const char *const *files, size_t n_files, const plasship_createdb_params *par,
+                            const char *db_path, plasship_seqdb **out_reads, plasship_createdb_stats *stats);
+
 /* ---- the workflows' tail: the contigs worth reporting, as a FASTA file
  *      plasship_select_contigs replaces the `_only_assembled` index filters and createsubdb of data/assemble.sh:170-189 (with
  *      --filter-proteins 0) and data/nuclassemble.sh:151-169 (FASTA mode); plasship_fasta_write replaces createhdb

@@ -107,6 +107,16 @@ class MergeStats(C.Structure):
                 ("ms_parse", C.c_float), ("ms_upload", C.c_float), ("ms_kernel", C.c_float)]
 
 
+class _CreatedbParams(C.Structure):
+    _fields_ = [("shuffle", C.c_int32), ("id_offset", C.c_uint32), ("dbtype", C.c_int32)]
+
+
+class CreatedbStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("files", C.c_uint64), ("chunks", C.c_uint64), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64),
+                ("lines", C.c_uint64), ("ms_read", C.c_float), ("ms_upload", C.c_float), ("ms_kernel", C.c_float), ("ms_write_kernel", C.c_float),
+                ("ms_total", C.c_float)]
+
+
 class _SelectParams(C.Structure):
     _fields_ = [("mode", C.c_int32), ("only_extended", C.c_int32), ("min_contig_len", C.c_int64)]
 
@@ -178,6 +188,8 @@ SYMBOLS = [
     ("plasship_orfhdr_count", C.c_int, [P, C.POINTER(C.c_size_t)]),
     ("plasship_orfhdr_free", None, [P, P]),
     ("plasship_mergereads", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_MergeParams), C.POINTER(P), C.POINTER(P), C.POINTER(MergeStats)]),
+    ("plasship_createdb", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_CreatedbParams), C.POINTER(P), C.POINTER(CreatedbStats)]),
+    ("plasship_createdb_write", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(_CreatedbParams), C.c_char_p, C.POINTER(P), C.POINTER(CreatedbStats)]),
     ("plasship_select_contigs", C.c_int, [P, P, P, P, C.POINTER(_SelectParams), C.POINTER(P), C.POINTER(SelectStats)]),
     ("plasship_fasta_write", C.c_int, [P, P, P, C.c_char_p, C.POINTER(FastaStats)]),
     ("plasship_subdb_write", C.c_int, [P, P, P, C.c_char_p, C.POINTER(SubdbStats)]),
@@ -497,6 +509,19 @@ class Context:
         h = P(); hh = P(); st = MergeStats(); cp = (par or MergeParams())._c()
         _check(self.lib.plasship_mergereads(self.h, arr, len(paths), C.byref(cp), C.byref(h), C.byref(hh), C.byref(st)), "plasship_mergereads")
         return SeqDB(self, h), SeqDB(self, hh), st
+
+    def createdb(self, files, shuffle=True, id_offset=0, dbtype=0, out=None):
+        """unpaired read files (FASTQ or FASTA, plain or .gz) -> (read DB, CreatedbStats); reference module createdb as the workflows run it
+        on single-end input (lib/mmseqs/src/util/createdb.cpp).  `out`: also write <out>, <out>_h, <out>.lookup and <out>.source"""
+        files = [os.fsencode(str(p)) for p in files]
+        arr = (C.c_char_p * len(files))(*files)
+        h = P(); st = CreatedbStats(); cp = _CreatedbParams(1 if shuffle else 0, int(id_offset), int(dbtype))
+        if out is None:
+            _check(self.lib.plasship_createdb(self.h, arr, len(files), C.byref(cp), C.byref(h), C.byref(st)), "plasship_createdb")
+        else:
+            _check(self.lib.plasship_createdb_write(self.h, arr, len(files), C.byref(cp), os.fsencode(str(out)), C.byref(h), C.byref(st)),
+                   "plasship_createdb_write")
+        return SeqDB(self, h), st
 
     def select_contigs(self, result, source, mode, cycles=None, only_extended=True, min_contig_len=1000):
         """the workflows' `_only_assembled` selection (data/assemble.sh:170-189 with --filter-proteins 0, data/nuclassemble.sh:151-169)

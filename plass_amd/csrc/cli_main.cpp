@@ -66,6 +66,8 @@ struct Flags {
     std::string fastaOut; int filterProteins = 1, minContigLen = 1000, contigOutputMode = 1;
     // the workflows' --db-mode end (nuclassemble.sh:200-207): nuclassemble-chain --db-mode 1 --db-out DB, and the nested nuclassemble of
     // guidedassemble-chain --nuclassembly-out DB with the nucleotide halves of the multi-parameters (GuidedNuclassembler.cpp:10-14,167-174)
+    // createdb-reads and the chains' --single-end 1 (unpaired read files through plasship_createdb): createdb's own defaults (Parameters.cpp: --shuffle 1)
+    int singleEnd = 0, shuffle = 1, dbtypeArg = 0, createdbMode = 0, writeLookup = 1; unsigned long long idOffset = 0;
     std::string dbOut, nuclAssemblyOut; int dbMode = 0, numIterationsNucl = 5, kNucl = 22, minAlnLenNucl = 0;
     std::set<std::string> seen;
 };
@@ -227,6 +229,9 @@ static const std::map<std::string, std::set<std::string>> &moduleFlags() {
         m["guidedassemble-chain"].insert({"--nuclassembly-out", "--chop-cycle", "--min-contig-len", "--contig-output-mode"});
         m["nuclassemble-chain"] = m["assemble-chain"]; m["nuclassemble-chain"].insert({"--chop-cycle", "--fasta-out", "--min-contig-len", "--contig-output-mode", "--db-mode", "--db-out"});
         m["assemble-chain"].insert({"--fasta-out", "--filter-proteins", "--protein-filter-threshold"});
+        for (const char *c : {"assemble-chain", "nuclassemble-chain", "guidedassemble-chain"}) m[c].insert("--single-end");
+        // createdb on the device for read files (our own name, like the chains: `createdb` itself stays with the reference); createdb's flags
+        m["createdb-reads"] = {"--shuffle", "--id-offset", "--dbtype", "--createdb-mode", "--write-lookup"};
         m["mergereads"] = {};       // the reference's onlythreads set (plass.cpp:47, Parameters.cpp:301-303): --threads, -v
         for (auto &kv : m) kv.second.insert(common.begin(), common.end());
     }
@@ -236,7 +241,7 @@ static const std::map<std::string, std::set<std::string>> &moduleFlags() {
 static const std::set<std::string> &boolFlags() {
     static const std::set<std::string> b = {"-a", "--add-self-matches", "--wrapped-scoring", "--filter-hits", "--include-only-extendable", "--ignore-multi-kmer",
                                             "--keep-target", "--chop-cycle", "--adjust-kmer-len", "--use-all-table-starts", "--add-orf-stop", "--preserve-keys",
-                                            "--take-larger-entry", "--db-mode"};
+                                            "--take-larger-entry", "--db-mode", "--shuffle"};
     return b;
 }
 static bool parseBool(const std::string &v, bool &ok) {                 // Parameters::parseBool: TRUE/1 | FALSE/0
@@ -258,7 +263,9 @@ int main(int argc, char **argv) {
                         "       (nuclassemble-chain --db-mode 1 --db-out DB: the selected contigs as DB, DB.index, DB.dbtype and DB_cycle.index instead, nuclassemble.sh:200-207)\n"
                         "       plass-hip guidedassemble-chain <i:readDB | r1.fastq r2.fastq …> <o:nuclAssemblyDB> <o:aaAssemblyDB> [--num-iterations aa:5,nucl:5]\n"
                         "       (--nuclassembly-out DB: goes on with data/guidedNuclAssemble.sh:135-170 — the extended ORFs + the reads through nuclassemble --db-mode 1)\n"
-                        "       (FASTQ pairs: merged on the GPU first, as the workflows' mergereads step, data/assemble.sh:27-38)\n");
+                        "       (FASTQ pairs: merged on the GPU first, as the workflows' mergereads step, data/assemble.sh:27-38)\n"
+                        "       (--single-end 1 on the three chains: every file before the output(s) is an unpaired FASTQ / FASTA read file, the workflows' createdb step)\n"
+                        "       plass-hip createdb-reads <i:file[.gz]> [<i:file2> …] <o:readDB> [--shuffle 1] [--id-offset 0] [--dbtype 0]   (writes <o>, <o>_h, <o>.lookup, <o>.source)\n");
         return EXIT_FAILURE;
     }
     const std::string mod = argv[1];
@@ -370,6 +377,12 @@ int main(int argc, char **argv) {
                 return unsupported("plass-hip: --sub-mat %s is not supported (built for blosum62.out / nucleotide.out)\n", v.c_str());
             }
         }
+        else if (a == "--single-end") f.singleEnd = atoi(v.c_str());
+        else if (a == "--shuffle") { if (!setBool(f.shuffle)) return EXIT_FAILURE; }
+        else if (a == "--dbtype") f.dbtypeArg = atoi(v.c_str());
+        else if (a == "--createdb-mode") f.createdbMode = atoi(v.c_str());
+        else if (a == "--write-lookup") f.writeLookup = atoi(v.c_str());
+        else if (a == "--id-offset" && mod == "createdb-reads") f.idOffset = strtoull(v.c_str(), nullptr, 10);
         else if (a == "--spaced-kmer-mode" || a == "--mask" || a == "--mask-lower-case" || a == "--compressed" || a == "--create-lookup" || a == "--id-offset") {
             if (atoi(v.c_str()) != 0) return unsupported("%s %s is not supported by plass-hip\n", a.c_str(), v.c_str());
         }
@@ -411,7 +424,18 @@ int main(int argc, char **argv) {
     // PLASSHIP_ERR_UNSUPPORTED before anything is written
     const size_t nChainOut = mod == "guidedassemble-chain" ? 2 : 1;
     std::vector<std::string> fastqIn;
-    if (mod == "mergereads") {
+    if (mod == "createdb-reads") {
+        if (pos.size() < 2) { fprintf(stdout, "createdb-reads <i:file1[.gz]> ... <i:fileN[.gz]> <o:sequenceDB>\n"); return EXIT_FAILURE; }
+        if (f.createdbMode != 0) return unsupported("plass-hip createdb-reads: --createdb-mode %d (soft links) is left to the reference\n", f.createdbMode);
+        if (f.writeLookup != 1) return unsupported("plass-hip createdb-reads: --write-lookup %d is left to the reference\n", f.writeLookup);
+        if (f.dbtypeArg < 0 || f.dbtypeArg > 2) { fprintf(stdout, "Error in argument --dbtype\n"); return EXIT_FAILURE; }
+        if (f.dbtypeArg == 1) return unsupported("plass-hip createdb-reads: --dbtype 1 (amino acids) is not an input of the assembly workflows; left to the reference\n");
+        if (f.idOffset > 0xFFFFFFFEull) { fprintf(stdout, "Error in argument --id-offset\n"); return EXIT_FAILURE; }
+        fastqIn.assign(pos.begin(), pos.end() - 1);
+    } else if (chain && f.singleEnd) {      // every positional before the output(s) is an unpaired read file (data/assemble.sh:27-38: createdb in place of mergereads)
+        if (pos.size() < nChainOut + 1) { fprintf(stdout, "%s: --single-end 1 needs at least one read file before the output\n", mod.c_str()); return EXIT_FAILURE; }
+        fastqIn.assign(pos.begin(), pos.end() - nChainOut);
+    } else if (mod == "mergereads") {
         if (pos.size() < 3 || (pos.size() - 1) % 2) { fprintf(stdout, "mergereads <i:fastqFile1[.gz]> <i:fastqFile2[.gz]> ... <o:sequenceDB>\n"); return EXIT_FAILURE; }
         fastqIn.assign(pos.begin(), pos.end() - 1);
     } else if (chain && pos.size() > nChainOut + 1) {
@@ -586,6 +610,14 @@ int main(int argc, char **argv) {
             if (KW(plasship_orfhdr_write(ctx, o, pos[2].c_str()))) return fail("concatdbs");
             plasship_orfhdr_free(ctx, o); plasship_orfhdr_free(ctx, b); plasship_orfhdr_free(ctx, a);
         } else { fprintf(stdout, "plass-hip concatdbs: cannot read the database type of %s\n", pos[0].c_str()); return EXIT_FAILURE; }      // (other types were refused above)
+    } else if (mod == "createdb-reads") {
+        // writes <out>, <out>_h, <out>.lookup and <out>.source like the reference's createdb (createdb.cpp:84,92-95,291-329)
+        std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
+        plasship_createdb_params cp; cp.shuffle = f.shuffle; cp.id_offset = (uint32_t) f.idOffset; cp.dbtype = f.dbtypeArg;
+        plasship_createdb_stats st; memset(&st, 0, sizeof(st));
+        if (KW(plasship_createdb_write(ctx, files.data(), files.size(), &cp, pos.back().c_str(), nullptr, &st))) return fail("createdb-reads");
+        fprintf(stdout, "entries: %llu lines: %llu chunks: %llu | read %.3f s upload %.3f s kernels %.3f ms (write %.3f ms) total %.3f s\n", (unsigned long long) st.entries,
+                (unsigned long long) st.lines, (unsigned long long) st.chunks, st.ms_read * 1e-3, st.ms_upload * 1e-3, st.ms_kernel, st.ms_write_kernel, st.ms_total * 1e-3);
     } else if (mod == "mergereads") {
         // writes <out> and <out>_h like the reference (mergereads.cpp:28-31)
         std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
@@ -622,7 +654,12 @@ int main(int argc, char **argv) {
         // a multi-GB input: the library takes its device arena (seconds of hipMalloc) while this thread reads and parses the DB files
         { struct stat stIn; if (stat(pos[0].c_str(), &stIn) == 0 && stIn.st_size >= ((off_t) 1 << 30)) (void) plasship_ctx_reserve_async(ctx); }
         plasship_seqdb *in = nullptr;
-        if (!fastqIn.empty()) {         // the workflows' mergereads step (data/assemble.sh:27-38): the merged reads stay in HBM, the header DB is not needed
+        if (!fastqIn.empty() && f.singleEnd) {      // the workflows' createdb step for unpaired input (data/assemble.sh:27-38): the reads stay in HBM
+            std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
+            plasship_createdb_stats cs;
+            if (K(plasship_createdb(ctx, files.data(), files.size(), nullptr, &in, &cs))) return fail(mod.c_str());
+            fprintf(stdout, "createdb: %llu reads from %llu files\n", (unsigned long long) cs.entries, (unsigned long long) cs.files);
+        } else if (!fastqIn.empty()) {         // the workflows' mergereads step (data/assemble.sh:27-38): the merged reads stay in HBM, the header DB is not needed
             std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
             plasship_seqdb *h = nullptr; plasship_merge_stats ms;
             if (K(plasship_mergereads(ctx, files.data(), files.size(), nullptr, &in, &h, &ms))) return fail(mod.c_str());

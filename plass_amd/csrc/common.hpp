@@ -297,7 +297,10 @@ int buildOutputDB(plasship_ctx *ctx, const plasship_seqdb *db, const uint32_t *d
 // ---- host boundary (core.hip): bulk copies through the context's pinned double buffer, on the context stream ----
 // H2D of `total` bytes the caller produces chunk by chunk: produce(dst, byteOffset, bytes) fills a pinned chunk (consecutive chunks,
 // in order; it may use the host threads) while the previous chunk is in flight.  Returns after the last copy has completed.
-int stagedUpload(plasship_ctx *ctx, void *dDst, uint64_t total, const std::function<void(char *, uint64_t, uint64_t)> &produce);
+// chunk != 0: chunks of that many bytes (at most a staging buffer); enqueued(end) runs after the copy of the bytes [.., end) has been put on
+// the stream — kernels it launches there work on that chunk while the next one is produced and copied (createdb.hip); non-zero aborts.
+int stagedUpload(plasship_ctx *ctx, void *dDst, uint64_t total, const std::function<void(char *, uint64_t, uint64_t)> &produce,
+                 uint64_t chunk = 0, const std::function<int(uint64_t)> *enqueued = nullptr);
 // D2H: consume(src, byteOffset, bytes) sees consecutive chunks in order (false aborts with PLASSHIP_ERR_IO); the next chunk is
 // already being copied while it runs
 int stagedDownload(plasship_ctx *ctx, const void *dSrc, uint64_t total, const std::function<bool(const char *, uint64_t, uint64_t)> &consume);

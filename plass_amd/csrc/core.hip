@@ -202,7 +202,7 @@ int tuneInt(const char *name, int dflt) {
 // The switches of this build: each is set by a committed test or tool, or turns an optimisation off so that a wrong result can be bisected
 // to a stage or memory be capped (README.md, "Environment switches").  Any other PLASSHIP_TUNE_<x> in the environment is reported once.
 static const char *const TUNE_NAMES[] = {"AGGWAVE", "AGGWAVE_CAP", "ASMQ", "ASMQ_CAP", "ROWTIER", "KMCACHE", "FORCE_LONG", "CYC_PASSES", "CYCSKIP", "SHARD_EXTRACT",
-                                         "FASTA_CHUNK_MB", "DBHEAP", "DBHEAP_GB", "LAZY_SELF"};
+                                         "FASTA_CHUNK_MB", "DBHEAP", "DBHEAP_GB", "LAZY_SELF", "FASTQ_CHUNK_KB"};
 static void reportUnknownTunes() {
     static const char PREFIX[] = "PLASSHIP_TUNE_";
     for (char **e = environ; e && *e; e++) {
@@ -374,16 +374,18 @@ void *ctxPinnedTable(plasship_ctx *ctx, size_t bytes) {
     if (!ctx->pinnedTable && hipHostMalloc(&ctx->pinnedTable, 1u << 20, hipHostMallocDefault) != hipSuccess) { ctx->pinnedTable = nullptr; (void) hipGetLastError(); }
     return ctx->pinnedTable;
 }
-int stagedUpload(plasship_ctx *ctx, void *dDst, uint64_t total, const std::function<void(char *, uint64_t, uint64_t)> &produce) {
+int stagedUpload(plasship_ctx *ctx, void *dDst, uint64_t total, const std::function<void(char *, uint64_t, uint64_t)> &produce,
+                 uint64_t chunk, const std::function<int(uint64_t)> *enqueued) {
     if (!total) return PLASSHIP_OK;
     int rc = stageReady(ctx); if (rc) return rc;
-    const uint64_t CH = ctx->stageBytes; int b = 0; bool used[2] = {false, false};
+    const uint64_t CH = chunk ? std::min<uint64_t>(chunk, ctx->stageBytes) : ctx->stageBytes; int b = 0; bool used[2] = {false, false};
     for (uint64_t o = 0; o < total; o += CH, b ^= 1) {
         const uint64_t n = std::min<uint64_t>(CH, total - o);
         if (used[b]) PH_CHECK(hipEventSynchronize(ctx->stageEv[b]));            // the copy that read this buffer two chunks ago
         produce(ctx->stage[b], o, n);
         PH_CHECK(hipMemcpyAsync((char *) dDst + o, ctx->stage[b], n, hipMemcpyHostToDevice, ctx->stream));
         PH_CHECK(hipEventRecord(ctx->stageEv[b], ctx->stream)); used[b] = true;
+        if (enqueued) { rc = (*enqueued)(o + n); if (rc) { (void) plasship::streamSync(ctx->stream); return rc; } }
     }
     PH_CHECK(plasship::streamSync(ctx->stream));
     return PLASSHIP_OK;

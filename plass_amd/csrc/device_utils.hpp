@@ -33,6 +33,18 @@ __device__ __forceinline__ unsigned long long rowMax16(unsigned long long v) {
     o = dppMov64<0x140>(v); v = o > v ? o : v;
     return v;
 }
+__device__ __forceinline__ uint32_t rowMin16U32(uint32_t v) {
+    uint32_t o;
+    o = dppMov<0xB1>(v); v = o < v ? o : v;
+    o = dppMov<0x4E>(v); v = o < v ? o : v;
+    o = dppMov<0x141>(v); v = o < v ? o : v;
+    o = dppMov<0x140>(v); v = o < v ? o : v;
+    return v;
+}
+__device__ __forceinline__ uint32_t rowOr16(uint32_t v) {
+    v |= dppMov<0xB1>(v); v |= dppMov<0x4E>(v); v |= dppMov<0x141>(v); v |= dppMov<0x140>(v);
+    return v;
+}
 // number of lanes in the own row of 16 whose value is smaller than `mine` (own lane excluded by the strict compare
 // when other == mine); `other` is the value to rotate: the own value, or another row's value fetched by a shuffle
 template <int N> struct RowCountLess {

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <sys/stat.h>
 #include <fcntl.h>
+#include <dlfcn.h>
 #include <unistd.h>
 #include <sched.h>
 #include <atomic>
@@ -343,6 +344,76 @@ int nuclPosteriorClass(uint32_t alpha1, uint32_t beta1, uint32_t alpha2, uint32_
     if (p < 0.45) return 0;
     if (p > 0.55) return 1;
     return 2;
+}
+
+// ---- read-file input shared by mergereads and createdb (kseq's sources, KSeqWrapper.cpp:160-195) ----
+// zlib without zlib.h or -lz: libamdhip64.so itself needs libz.so.1, so it is on every machine this library runs on
+struct Zlib {
+    void *(*gzopen)(const char *, const char *) = nullptr;
+    int (*gzread)(void *, void *, unsigned) = nullptr;
+    int (*gzclose)(void *) = nullptr;
+    int (*gzbuffer)(void *, unsigned) = nullptr;
+    bool ok = false;
+};
+static const Zlib &zlib() {
+    static const Zlib z = [] {
+        Zlib t;
+        void *h = dlopen("libz.so.1", RTLD_NOW | RTLD_LOCAL);
+        if (!h) return t;
+        t.gzopen = (void *(*)(const char *, const char *)) dlsym(h, "gzopen");
+        t.gzread = (int (*)(void *, void *, unsigned)) dlsym(h, "gzread");
+        t.gzclose = (int (*)(void *)) dlsym(h, "gzclose");
+        t.gzbuffer = (int (*)(void *, unsigned)) dlsym(h, "gzbuffer");
+        t.ok = t.gzopen && t.gzread && t.gzclose;
+        return t;
+    }();
+    return z;
+}
+
+bool pathEndsWith(const std::string &s, const char *suf) { const size_t n = strlen(suf); return s.size() >= n && s.compare(s.size() - n, n, suf) == 0; }
+
+// the whole file into memory: .gz through one zlib stream (gzread also passes a file through that is not compressed, like the reference's
+// KSeqGzip), everything else with pread on the host threads
+bool readSeqFileBytes(const std::string &path, HostBytes &buf, std::string &err) {
+    if (pathEndsWith(path, ".gz")) {
+        const Zlib &z = zlib();
+        if (!z.ok) { err = "cannot load libz.so.1 to read " + path; return false; }
+        struct stat st; if (stat(path.c_str(), &st) != 0) { err = "cannot open " + path; return false; }
+        void *g = z.gzopen(path.c_str(), "rb");
+        if (!g) { err = "cannot open " + path; return false; }
+        if (z.gzbuffer) z.gzbuffer(g, 1u << 20);
+        size_t cap = std::max<size_t>((size_t) st.st_size * 4, 1u << 20), n = 0;
+        char *p = (char *) malloc(cap + 64);
+        for (;;) {
+            if (!p) { z.gzclose(g); err = "out of host memory reading " + path; return false; }
+            if (cap - n < (16u << 20)) { cap *= 2; char *q = (char *) realloc(p, cap + 64); if (!q) { free(p); p = nullptr; continue; } p = q; }
+            const int got = z.gzread(g, p + n, (unsigned) std::min<size_t>(cap - n, 1u << 30));
+            if (got < 0) { free(p); z.gzclose(g); err = "error while decompressing " + path; return false; }
+            if (got == 0) break;
+            n += (size_t) got;
+        }
+        z.gzclose(g);
+        memset(p + n, 0, 64);
+        buf.p = p; buf.n = n;
+        return true;
+    }
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) { err = "cannot open " + path; return false; }
+    struct stat st; if (fstat(fd, &st) != 0) { close(fd); err = "cannot stat " + path; return false; }
+    const uint64_t S = (uint64_t) st.st_size;
+    if (!buf.alloc(S)) { close(fd); err = "out of host memory reading " + path; return false; }
+    const uint64_t SL = 64ull << 20;
+    std::atomic<bool> ok(true);
+    parallelRanges((size_t) ((S + SL - 1) / SL), [&](int, size_t b, size_t e) {
+        for (uint64_t o = b * SL, end = std::min<uint64_t>(S, e * SL); o < end && ok;) {
+            const ssize_t g = pread(fd, buf.p + o, (size_t) (end - o), (off_t) o);
+            if (g <= 0) { ok = false; break; }
+            o += (uint64_t) g;
+        }
+    }, nullptr, 1);
+    close(fd);
+    if (!ok) { err = "error while reading " + path; return false; }
+    return true;
 }
 
 }  // namespace plasship

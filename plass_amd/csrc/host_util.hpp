@@ -42,6 +42,10 @@ struct HostDB {
 // NAME or NAME.0 .. NAME.k (the unmerged per-thread files of the reference's DBWriter; offsets run over their concatenation),
 // NAME.index, NAME.dbtype.  The data is read with pread() on all host threads, the index is parsed on all host threads.
 bool readDBFiles(const std::string &path, HostDB &db, std::string &err);
+// a read file (FASTQ / FASTA) whole into memory: ".gz" through one zlib stream (gzread also passes a file through that is not compressed,
+// like the reference's KSeqGzip; zlib is dlopen'ed as libz.so.1), everything else with pread on the host threads
+bool readSeqFileBytes(const std::string &path, HostBytes &buf, std::string &err);
+bool pathEndsWith(const std::string &s, const char *suf);
 bool ioTimingOn();      // PLASSHIP_IO_TIMING=1: phase timings of the host boundary on stderr
 double ioNow();
 

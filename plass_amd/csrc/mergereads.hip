@@ -16,8 +16,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
-#include <dlfcn.h>
-#include <fcntl.h>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -87,14 +85,6 @@ __device__ __forceinline__ unsigned long long rowMin16U64(unsigned long long v) 
     o = dppMov64<0x4E>(v); v = o < v ? o : v;
     o = dppMov64<0x141>(v); v = o < v ? o : v;
     o = dppMov64<0x140>(v); v = o < v ? o : v;
-    return v;
-}
-__device__ __forceinline__ uint32_t rowMin16U32(uint32_t v) {
-    uint32_t o;
-    o = dppMov<0xB1>(v); v = o < v ? o : v;
-    o = dppMov<0x4E>(v); v = o < v ? o : v;
-    o = dppMov<0x141>(v); v = o < v ? o : v;
-    o = dppMov<0x140>(v); v = o < v ? o : v;
     return v;
 }
 
@@ -273,78 +263,12 @@ __global__ void mergeRunKernel(uint64_t *run, const uint64_t *entBase, const uin
 }
 
 // ---- host: FASTQ input (kseq semantics, lib/mmseqs/lib/ksw2/kseq.h; KSeqWrapper.cpp:160-195) -------------------------------------
-// zlib without zlib.h or -lz: libamdhip64.so itself needs libz.so.1, so it is on every machine this library runs on
-struct Zlib {
-    void *(*gzopen)(const char *, const char *) = nullptr;
-    int (*gzread)(void *, void *, unsigned) = nullptr;
-    int (*gzclose)(void *) = nullptr;
-    int (*gzbuffer)(void *, unsigned) = nullptr;
-    bool ok = false;
-};
-static const Zlib &zlib() {
-    static const Zlib z = [] {
-        Zlib t;
-        void *h = dlopen("libz.so.1", RTLD_NOW | RTLD_LOCAL);
-        if (!h) return t;
-        t.gzopen = (void *(*)(const char *, const char *)) dlsym(h, "gzopen");
-        t.gzread = (int (*)(void *, void *, unsigned)) dlsym(h, "gzread");
-        t.gzclose = (int (*)(void *)) dlsym(h, "gzclose");
-        t.gzbuffer = (int (*)(void *, unsigned)) dlsym(h, "gzbuffer");
-        t.ok = t.gzopen && t.gzread && t.gzclose;
-        return t;
-    }();
-    return z;
-}
-
-static bool endsWith(const std::string &s, const char *suf) { const size_t n = strlen(suf); return s.size() >= n && s.compare(s.size() - n, n, suf) == 0; }
-
 // one record of a FASTQ file: offsets into the file's bytes
 struct FastqRec { uint64_t name, seq, qual; uint32_t nameLen, len; };
 struct FastqFile { std::string path; HostBytes buf; std::vector<FastqRec> rec; int rc = 0; std::string err; };
 
-// the whole file into memory: .gz through one zlib stream (gzread also passes a file through that is not compressed, like the reference's
-// KSeqGzip), everything else with pread on the host threads
-static int readFastqBytes(FastqFile &f) {
-    if (endsWith(f.path, ".gz")) {
-        const Zlib &z = zlib();
-        if (!z.ok) { f.err = "cannot load libz.so.1 to read " + f.path; return PLASSHIP_ERR_IO; }
-        struct stat st; if (stat(f.path.c_str(), &st) != 0) { f.err = "cannot open " + f.path; return PLASSHIP_ERR_IO; }
-        void *g = z.gzopen(f.path.c_str(), "rb");
-        if (!g) { f.err = "cannot open " + f.path; return PLASSHIP_ERR_IO; }
-        if (z.gzbuffer) z.gzbuffer(g, 1u << 20);
-        size_t cap = std::max<size_t>((size_t) st.st_size * 4, 1u << 20), n = 0;
-        char *p = (char *) malloc(cap + 64);
-        for (;;) {
-            if (!p) { z.gzclose(g); f.err = "out of host memory reading " + f.path; return PLASSHIP_ERR_IO; }
-            if (cap - n < (16u << 20)) { cap *= 2; char *q = (char *) realloc(p, cap + 64); if (!q) { free(p); p = nullptr; continue; } p = q; }
-            const int got = z.gzread(g, p + n, (unsigned) std::min<size_t>(cap - n, 1u << 30));
-            if (got < 0) { free(p); z.gzclose(g); f.err = "error while decompressing " + f.path; return PLASSHIP_ERR_IO; }
-            if (got == 0) break;
-            n += (size_t) got;
-        }
-        z.gzclose(g);
-        memset(p + n, 0, 64);
-        f.buf.p = p; f.buf.n = n;
-        return PLASSHIP_OK;
-    }
-    const int fd = open(f.path.c_str(), O_RDONLY);
-    if (fd < 0) { f.err = "cannot open " + f.path; return PLASSHIP_ERR_IO; }
-    struct stat st; if (fstat(fd, &st) != 0) { close(fd); f.err = "cannot stat " + f.path; return PLASSHIP_ERR_IO; }
-    const uint64_t S = (uint64_t) st.st_size;
-    if (!f.buf.alloc(S)) { close(fd); f.err = "out of host memory reading " + f.path; return PLASSHIP_ERR_IO; }
-    const uint64_t SL = 64ull << 20;
-    std::atomic<bool> ok(true);
-    parallelRanges((size_t) ((S + SL - 1) / SL), [&](int, size_t b, size_t e) {
-        for (uint64_t o = b * SL, end = std::min<uint64_t>(S, e * SL); o < end && ok;) {
-            const ssize_t g = pread(fd, f.buf.p + o, (size_t) (end - o), (off_t) o);
-            if (g <= 0) { ok = false; break; }
-            o += (uint64_t) g;
-        }
-    }, nullptr, 1);
-    close(fd);
-    if (!ok) { f.err = "error while reading " + f.path; return PLASSHIP_ERR_IO; }
-    return PLASSHIP_OK;
-}
+// the whole file into memory (host_util.cpp, readSeqFileBytes: shared with createdb.hip)
+static int readFastqBytes(FastqFile &f) { return readSeqFileBytes(f.path, f.buf, f.err) ? PLASSHIP_OK : PLASSHIP_ERR_IO; }
 
 static inline bool kseqSpace(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\v' || c == '\f' || c == '\r'; }
 
@@ -442,7 +366,7 @@ extern "C" int plasship_mergereads(plasship_ctx *ctx, const char *const *fastq, 
     for (size_t k = 0; k < n_files; k++) {
         const std::string p = fastq[k];
         if (p == "stdin") { setError("plasship_mergereads: reading stdin is left to the reference"); return PLASSHIP_ERR_UNSUPPORTED; }
-        if (endsWith(p, ".bz2")) { setError("plasship_mergereads: " + p + ": bzip2 input is left to the reference"); return PLASSHIP_ERR_UNSUPPORTED; }
+        if (pathEndsWith(p, ".bz2")) { setError("plasship_mergereads: " + p + ": bzip2 input is left to the reference"); return PLASSHIP_ERR_UNSUPPORTED; }
     }
     PH_ENTER(ctx);
     hipStream_t st = ctx->stream;
