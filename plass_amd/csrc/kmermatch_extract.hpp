@@ -612,7 +612,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : 
         if (P > cap) P = cap;      // cap is a power of two >= C in both modes
         for (uint32_t i = C + lane; i < P; i += 64) { Cand cd; cd.kmer = ~0ULL; cd.pos = 0xFFFFFFFFu; cd.score = 0xFFFFFFFFu; cand[i] = cd; }
         __syncthreads();
-        bool sortedNeeded = true;
+        // (--ignore-multi-kmer 0: the reference does not sort, kmermatcher.cpp:266-272 — its walk meets the k-mers in window order, so the
+        //  threshold bin's surplus and the `considered` limit keep the FIRST windows of the sequence, not the smallest k-mers.  The candidates
+        //  were pushed in window order by every front end above.)
+        const bool sortedNeeded = a.ignoreMulti;
         if (sortedNeeded && C > 1) waveBitonicSortCands(cand, P, NUCL);
         // ---- repeated k-mer skipping (kmermatcher.cpp:277-301), exact emulation of the index walk ----
         if (a.ignoreMulti) {

@@ -2,12 +2,16 @@
 include/plasship.h) against (a) golden DBs written by the unmodified reference and (b) the CPU oracle on
 seeded synthetic and adversarial inputs.  Everything is bit-exact: DB entries are compared byte for byte."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import (AA_AS, AA_KM, AA_RS, GD_AS, GD_KM, GD_P2N, GD_RS, NUCL_AS, NUCL_KM, NUCL_RS, ROOT, aa_iter_flags, assert_same_db, read_db, run_oracle,
                       sweep_positional, sweep_variants)
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+from extract_ladder import assert_counts  # noqa: E402  (KmermatchStats against the oracle's N_k / N_m / N_c)
 
 pytestmark = pytest.mark.gpu
 
@@ -198,12 +202,13 @@ def test_synthetic_nucl_three_iterations_vs_oracle(ctx, oracle_bin, tmp_path):
     synth.write_db(str(tmp_path / "o_seq_0"), data, off, elen, key, 1)
     db = ctx.upload_seqdb(data, off, elen, key, 1)
     for it in range(3):
-        run_oracle(oracle_bin, ["kmermatcher", tmp_path / f"o_seq_{it}", tmp_path / f"o_pref_{it}"] + NUCL_KM)
+        log = run_oracle(oracle_bin, ["kmermatcher", tmp_path / f"o_seq_{it}", tmp_path / f"o_pref_{it}"] + NUCL_KM)
         run_oracle(oracle_bin, ["rescorediagonal", tmp_path / f"o_seq_{it}", tmp_path / f"o_seq_{it}", tmp_path / f"o_pref_{it}", tmp_path / f"o_aln_{it}"] + NUCL_RS)
         run_oracle(oracle_bin, ["nuclassembleresults", tmp_path / f"o_seq_{it}", tmp_path / f"o_aln_{it}", tmp_path / f"o_seq_{it + 1}"] + NUCL_AS)
         cands, kst = ctx.kmermatcher(db, km_params(it, nucl=True))
         cands.write(tmp_path / "g_pref")
         assert_same_db(tmp_path / f"o_pref_{it}", tmp_path / "g_pref", f"nucl kmermatcher it{it}")
+        assert_counts(kst, log, f"nucl kmermatcher it{it}")
         alns, rst = ctx.rescorediagonal(db, db, cands, plass_amd.RescoreParams(min_seq_id=0.99))
         alns.write(tmp_path / "g_aln")
         assert_same_db(tmp_path / f"o_aln_{it}", tmp_path / "g_aln", f"nucl rescorediagonal it{it}")
@@ -455,9 +460,10 @@ def test_golden_stale_scan_quirk(ctx, golden, tmp_path, case):
 
 
 def _oracle_iteration(oracle_bin, d, it):
-    run_oracle(oracle_bin, ["kmermatcher", d / f"o_seq_{it}", d / f"o_pref_{it}"] + AA_KM + aa_iter_flags(it))
+    log = run_oracle(oracle_bin, ["kmermatcher", d / f"o_seq_{it}", d / f"o_pref_{it}"] + AA_KM + aa_iter_flags(it))
     run_oracle(oracle_bin, ["rescorediagonal", d / f"o_seq_{it}", d / f"o_seq_{it}", d / f"o_pref_{it}", d / f"o_aln_{it}"] + AA_RS)
     run_oracle(oracle_bin, ["assembleresults", d / f"o_seq_{it}", d / f"o_aln_{it}", d / f"o_seq_{it + 1}"] + AA_AS)
+    return log          # (the kmermatcher's: its N_k / N_m / N_c line)
 
 
 def test_synthetic_three_iterations_vs_oracle(ctx, oracle_bin, tmp_path):
@@ -469,10 +475,11 @@ def test_synthetic_three_iterations_vs_oracle(ctx, oracle_bin, tmp_path):
     synth.write_db(str(tmp_path / "o_seq_0"), data, off, elen, key, 0)
     db = ctx.upload_seqdb(data, off, elen, key, 0)
     for it in range(3):
-        _oracle_iteration(oracle_bin, tmp_path, it)
+        log = _oracle_iteration(oracle_bin, tmp_path, it)
         cands, kst = ctx.kmermatcher(db, km_params(it))
         cands.write(tmp_path / "g_pref")
         assert_same_db(tmp_path / f"o_pref_{it}", tmp_path / "g_pref", f"kmermatcher it{it}")
+        assert_counts(kst, log, f"kmermatcher it{it}")
         alns, rst = ctx.rescorediagonal(db, db, cands, plass_amd.RescoreParams(min_seq_id=0.9))
         alns.write(tmp_path / "g_aln")
         assert_same_db(tmp_path / f"o_aln_{it}", tmp_path / "g_aln", f"rescorediagonal it{it}")
@@ -612,11 +619,12 @@ def test_adversarial_inputs_vs_oracle(ctx, oracle_bin, tmp_path):
     assert db.info()["max_entry_len"] >= 32767
     for it, ext in ((0, False), (1, True)):
         flags = ["--hash-shift", "67", "--include-only-extendable", "1" if ext else "0"]
-        run_oracle(oracle_bin, ["kmermatcher", tmp_path / "seq", tmp_path / f"o_pref{it}"] + AA_KM + flags)
+        log = run_oracle(oracle_bin, ["kmermatcher", tmp_path / "seq", tmp_path / f"o_pref{it}"] + AA_KM + flags)
         par = km_params(0); par.include_only_extendable = ext
-        cands, _ = ctx.kmermatcher(db, par)
+        cands, kst = ctx.kmermatcher(db, par)
         cands.write(tmp_path / f"g_pref{it}")
         assert_same_db(tmp_path / f"o_pref{it}", tmp_path / f"g_pref{it}", f"adversarial kmermatcher ext={ext}")
+        assert_counts(kst, log, f"adversarial kmermatcher ext={ext}")
         run_oracle(oracle_bin, ["rescorediagonal", tmp_path / "seq", tmp_path / "seq", tmp_path / f"o_pref{it}", tmp_path / f"o_aln{it}"] + AA_RS)
         alns, _ = ctx.rescorediagonal(db, db, cands, plass_amd.RescoreParams(min_seq_id=0.9))
         alns.write(tmp_path / f"g_aln{it}")
@@ -649,11 +657,12 @@ def test_protein_repeats_overflow_the_candidate_set(ctx, oracle_bin, tmp_path):
     scratch = restarts = 0
     for hs in (67, 68, 69, 70):
         for ext in (0, 1):
-            run_oracle(oracle_bin, ["kmermatcher", tmp_path / "seq", tmp_path / "o_pref"] + AA_KM + ["--hash-shift", str(hs), "--include-only-extendable", str(ext)])
+            log = run_oracle(oracle_bin, ["kmermatcher", tmp_path / "seq", tmp_path / "o_pref"] + AA_KM + ["--hash-shift", str(hs), "--include-only-extendable", str(ext)])
             par = km_params(0); par.hash_shift = hs; par.include_only_extendable = bool(ext)
             cands, st = ctx.kmermatcher(db, par)
             cands.write(tmp_path / "g_pref")
             assert_same_db(tmp_path / "o_pref", tmp_path / "g_pref", f"repeats, hash shift {hs}, extendable {ext}")
+            assert_counts(st, log, f"repeats, hash shift {hs}, extendable {ext}")
             scratch += st.n_scratch_sequences; restarts += st.n_restarts
             cands.free()
     assert scratch > 0 and restarts > 0, "no sequence overflowed the candidate set: the test does not reach the path it is for"
