@@ -227,6 +227,17 @@ def load_library():
     return lib
 
 
+def resume_point(dir, num_iterations, name="assembly_"):
+    """where `plass-hip assemble-chain / nuclassemble-chain --write-intermediate dir --resume 1 --num-iterations num_iterations` would go on:
+    the highest i < num_iterations for which dir/assembly_<i>.done and the DB it vouches for (data, .index, .dbtype) exist — the run continues
+    at iteration i + 1 — or None for a fresh run.  The rule of resumePoint() in csrc/cli_main.cpp; pure Python, no GPU."""
+    for i in range(int(num_iterations) - 1, -1, -1):
+        p = os.path.join(str(dir), "%s%d" % (name, i))
+        if all(os.path.isfile(p + s) for s in (".done", "", ".index", ".dbtype")):
+            return i
+    return None
+
+
 def _check(rc, what):
     if rc != 0:
         msg = load_library().plasship_last_error()

@@ -60,7 +60,7 @@ struct Flags {
     int chopCycle = 1;                   // LocalParameters.h:202
     int orfMin = 30, orfMax = 32734, orfGaps = INT_MAX, contigStart = 2, contigEnd = 2, orfStart = 1, fwdFrames = 7, revFrames = 7;
     int translationTable = 1, translate = 0, allStarts = 0, addOrfStop = 0, preserveKeys = 0, takeLarger = 0;
-    int numIterations = 0, fromReads = 0; std::string writeIntermediate; float seqIdThrNucl = 0.99f;
+    int numIterations = 0, fromReads = 0, resume = 0; std::string writeIntermediate; float seqIdThrNucl = 0.99f;
     // the workflows' tail (--fasta-out): Assembler.cpp / Nuclassembler.cpp defaults (--filter-proteins 1, --min-contig-len 1000,
     // --contig-output-mode 1)
     std::string fastaOut; int filterProteins = 1, minContigLen = 1000, contigOutputMode = 1;
@@ -105,16 +105,19 @@ static double now() { return std::chrono::duration<double>(std::chrono::steady_c
 enum ChainKind { CHAIN_PROTEIN, CHAIN_NUCL, CHAIN_GUIDED };
 struct ChainLoop {
     plasship_ctx *ctx = nullptr; const char *name = ""; ChainKind kind = CHAIN_PROTEIN;
-    int numIterations = 1, k = 0, alph = 13, kps = 60, ignoreMulti = 1, covMode = 0, hashShift = 67, gapOpenNucl = 5, gapExtendNucl = 2, chopCycle = 1;
+    int numIterations = 1, startIteration = 0, k = 0, alph = 13, kps = 60, ignoreMulti = 1, covMode = 0, hashShift = 67, gapOpenNucl = 5, gapExtendNucl = 2, chopCycle = 1;
     float kpsScale = 0.0f, covThr = 0.0f; unsigned long long maxSeqLen = 65535;
     plasship_rescore_params rp; plasship_assemble_params ap;
     bool keepForTail = false;            // keep SOURCE and every iteration's circular contigs: a tail follows
     std::string cyclePrefix;             // nucleotide: circular contigs of iteration i are written to <cyclePrefix><i> ("": they are not)
     std::string intermediateName;        // --write-intermediate: "assembly_" / "assembly_nucl_" ("": nothing is written)
+    bool writeLastIntermediate = false;  // --resume 1: the last iteration's DB is a resume point too (a finished run can be extended)
     std::function<int()> joinWriter; std::function<void(const plasship_seqdb *, const std::string &)> writeAsync;
-    // in: the DB(s) the loop starts from; out: the last iteration's
+    // in: the DB(s) iteration startIteration starts from; out: the last iteration's
     plasship_seqdb *db = nullptr, *aa = nullptr;
-    plasship_seqdb *source = nullptr, *cycAll = nullptr;       // keepForTail: SOURCE of the tail, PREV_CYCLE_ALL (nullptr: no circular contig)
+    // keepForTail: SOURCE of the tail, PREV_CYCLE_ALL (nullptr: no circular contig).  A loop that starts at iteration 0 sets both; one that
+    // starts later (--resume 1) is handed what the iterations before startIteration would have left here
+    plasship_seqdb *source = nullptr, *cycAll = nullptr;
     unsigned long long overlaps = 0; double kernelMs = 0, tStart = 0;
 };
 static int runChainLoop(ChainLoop &L) {
@@ -122,14 +125,14 @@ static int runChainLoop(ChainLoop &L) {
     const bool prot = L.kind == CHAIN_PROTEIN, nuc = L.kind == CHAIN_NUCL, gd = L.kind == CHAIN_GUIDED;
     plasship_seqdb *&db = L.db, *&aa = L.aa, *&source = L.source, *&cycAll = L.cycAll;
     // SOURCE is the DB the loop starts from (the reads; the guided chain's nucl_6f_start_long; the fragments before findassemblystart: kept below)
-    if (L.keepForTail && !prot) source = db;
-    int hashShift = L.hashShift;
-    for (int it = 0; it < L.numIterations; it++) {
+    if (L.keepForTail && !prot && !source) source = db;
+    for (int it = L.startIteration; it < L.numIterations; it++) {
         plasship_kmermatch_params kp; memset(&kp, 0, sizeof(kp));
         kp.kmer_size = L.k; kp.alphabet_size = L.alph; kp.kmers_per_seq = L.kps; kp.kmers_per_seq_scale = L.kpsScale; kp.ignore_multi_kmer = L.ignoreMulti;
         kp.cov_mode = L.covMode; kp.cov_thr = L.covThr;
         // plass assemble: --hash-shift grows with every second iteration, iteration 0 keeps non-extendable matches (Assembler.cpp:99-110)
-        if (prot) { hashShift += it % 2; kp.hash_shift = hashShift; kp.include_only_extendable = it > 0; } else { kp.hash_shift = L.hashShift; kp.include_only_extendable = 1; }
+        // (67, 68, 68, 69, …: a function of the iteration's index, wherever this loop starts)
+        if (prot) { kp.hash_shift = L.hashShift + (it + 1) / 2; kp.include_only_extendable = it > 0; } else { kp.hash_shift = L.hashShift; kp.include_only_extendable = 1; }
         plasship_seqdb *q = gd ? aa : db;
         plasship_cands *c = nullptr; plasship_alns *al = nullptr; plasship_kmermatch_stats ks; plasship_rescore_stats rs; plasship_assemble_stats as;
         if (K(plasship_kmermatch(ctx, q, &kp, &c, &ks)) || K(plasship_rescore(ctx, q, q, c, &L.rp, &al, &rs))) return fail(L.name);
@@ -166,7 +169,7 @@ static int runChainLoop(ChainLoop &L) {
             plasship_seqdb_free(ctx, db); db = rest;
         }
         fprintf(stdout, "iteration %d: candidates %llu verified %llu extended %llu (%.3f s since the DB was read)\n", it, (unsigned long long) ks.n_candidates, (unsigned long long) rs.n_accepted, (unsigned long long) as.n_extended, now() - L.tStart);
-        if (it + 1 < L.numIterations && L.writeAsync && !L.intermediateName.empty()) L.writeAsync(db, L.intermediateName + std::to_string(it));
+        if ((it + 1 < L.numIterations || L.writeLastIntermediate) && L.writeAsync && !L.intermediateName.empty()) L.writeAsync(db, L.intermediateName + std::to_string(it));
     }
     return EXIT_SUCCESS;
 }
@@ -200,6 +203,82 @@ static int chainTail(plasship_ctx *ctx, const char *name, bool nuc, plasship_seq
     return EXIT_SUCCESS;
 }
 
+// ---- --resume 1: the resume points --write-intermediate DIR leaves (DIR/assembly_<i> + DIR/assembly_<i>.done, data/assemble.sh:147) and
+//      DIR/chain.manifest, the parameters and the input they were computed with ----
+static bool isFile(const std::string &p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
+// the highest i < numIterations whose sentinel and DB files exist (the sentinel is touched after the DB is complete); -1: none
+static int resumePoint(const std::string &dir, const std::string &name, int numIterations) {
+    for (int i = numIterations - 1; i >= 0; i--) {
+        const std::string p = dir + "/" + name + std::to_string(i);
+        if (isFile(p + ".done") && isFile(p) && isFile(p + ".index") && isFile(p + ".dbtype")) return i;
+    }
+    return -1;
+}
+typedef std::vector<std::pair<std::string, std::string>> Manifest;
+static std::string fmtNum(const char *fmt, ...) { char b[96]; va_list ap; va_start(ap, fmt); vsnprintf(b, sizeof(b), fmt, ap); va_end(ap); return b; }
+// what a continuation must share with the run that wrote the resume points: the module, every parameter the loop's result depends on (keyed
+// by its flag) and the input files.  Not --num-iterations, the outputs or the tail's flags: those may differ.
+static Manifest chainManifest(const std::string &mod, const Flags &f, const std::vector<std::string> &inputs) {
+    Manifest m;
+    m.emplace_back("module", mod);
+    m.emplace_back("-k", std::to_string(f.k));
+    m.emplace_back("--alph-size", std::to_string(f.alph));
+    m.emplace_back("--kmer-per-seq", std::to_string(f.kps));
+    m.emplace_back("--kmer-per-seq-scale", fmtNum("%.9g", (double) (mod == "nuclassemble-chain" ? f.scaleNucl : f.scaleAA)));
+    m.emplace_back("--hash-shift", std::to_string(f.hashShift));
+    m.emplace_back("--min-seq-id", fmtNum("%.9g", (double) f.seqIdThr));
+    m.emplace_back("-e", fmtNum("%.17g", f.evalThr));
+    m.emplace_back("-c", fmtNum("%.9g", (double) f.covThr));
+    m.emplace_back("--cov-mode", std::to_string(f.covMode));
+    m.emplace_back("--min-aln-len", std::to_string(f.minAlnLen));
+    m.emplace_back("--seq-id-mode", std::to_string(f.seqIdMode));
+    m.emplace_back("--rescore-mode", std::to_string(f.rescoreMode));
+    m.emplace_back("--ignore-multi-kmer", std::to_string(f.ignoreMulti));
+    m.emplace_back("--include-only-extendable", std::to_string(f.onlyExt));
+    m.emplace_back("--keep-target", std::to_string(f.keepTarget));
+    m.emplace_back("--max-seq-len", std::to_string(f.maxSeqLen));
+    m.emplace_back("--chop-cycle", std::to_string(f.chopCycle));
+    m.emplace_back("--from-reads", std::to_string(f.fromReads));
+    m.emplace_back("--single-end", std::to_string(f.singleEnd));
+    m.emplace_back("inputs", std::to_string(inputs.size()));
+    for (size_t i = 0; i < inputs.size(); i++) {
+        const std::string key = "input." + std::to_string(i);
+        char *rp = realpath(inputs[i].c_str(), nullptr);
+        m.emplace_back(key + ".path", rp ? rp : inputs[i].c_str()); free(rp);
+        struct stat st; const bool have = stat(inputs[i].c_str(), &st) == 0;
+        m.emplace_back(key + ".size", have ? std::to_string((long long) st.st_size) : "-1");
+        m.emplace_back(key + ".mtime", have ? fmtNum("%lld.%09ld", (long long) st.st_mtim.tv_sec, (long) st.st_mtim.tv_nsec) : "-1");
+    }
+    return m;
+}
+static bool writeManifest(const std::string &path, const Manifest &m) {
+    const std::string tmp = path + ".tmp";
+    FILE *fd = fopen(tmp.c_str(), "w"); if (!fd) return false;
+    bool ok = true;
+    for (const auto &kv : m) ok &= fprintf(fd, "%s %s\n", kv.first.c_str(), kv.second.c_str()) > 0;
+    ok &= fclose(fd) == 0;
+    if (!ok || rename(tmp.c_str(), path.c_str()) != 0) { remove(tmp.c_str()); return false; }
+    return true;
+}
+// the first key of `m` that the manifest file does not hold with the same value ("": none).  A line is "key value", the value runs to its end.
+static std::string manifestDiffers(const std::string &path, const Manifest &m, std::string &inFile) {
+    std::map<std::string, std::string> have;
+    FILE *fd = fopen(path.c_str(), "r"); if (!fd) return m.front().first;
+    char line[PATH_MAX + 128];
+    while (fgets(line, sizeof(line), fd)) {
+        std::string l = line; while (!l.empty() && (l.back() == '\n' || l.back() == '\r')) l.pop_back();
+        const size_t sp = l.find(' ');
+        if (!l.empty()) have[l.substr(0, sp)] = sp == std::string::npos ? std::string() : l.substr(sp + 1);
+    }
+    fclose(fd);
+    for (const auto &kv : m) {
+        const auto it = have.find(kv.first);
+        if (it == have.end()) { inFile = "(missing)"; return kv.first; }
+        if (it->second != kv.second) { inFile = it->second; return kv.first; }
+    }
+    return std::string();
+}
+
 // which flags a module owns (its parameter vector in the reference)
 static const std::map<std::string, std::set<std::string>> &moduleFlags() {
     static const std::set<std::string> common = {"--threads", "-v", "--compressed"};
@@ -229,7 +308,7 @@ static const std::map<std::string, std::set<std::string>> &moduleFlags() {
         m["guidedassemble-chain"].insert({"--nuclassembly-out", "--chop-cycle", "--min-contig-len", "--contig-output-mode"});
         m["nuclassemble-chain"] = m["assemble-chain"]; m["nuclassemble-chain"].insert({"--chop-cycle", "--fasta-out", "--min-contig-len", "--contig-output-mode", "--db-mode", "--db-out"});
         m["assemble-chain"].insert({"--fasta-out", "--filter-proteins", "--protein-filter-threshold"});
-        for (const char *c : {"assemble-chain", "nuclassemble-chain", "guidedassemble-chain"}) m[c].insert("--single-end");
+        for (const char *c : {"assemble-chain", "nuclassemble-chain", "guidedassemble-chain"}) m[c].insert({"--single-end", "--resume"});
         // createdb on the device for read files (our own name, like the chains: `createdb` itself stays with the reference); createdb's flags
         m["createdb-reads"] = {"--shuffle", "--id-offset", "--dbtype", "--createdb-mode", "--write-lookup"};
         m["mergereads"] = {};       // the reference's onlythreads set (plass.cpp:47, Parameters.cpp:301-303): --threads, -v
@@ -263,6 +342,8 @@ int main(int argc, char **argv) {
                         "       (nuclassemble-chain --db-mode 1 --db-out DB: the selected contigs as DB, DB.index, DB.dbtype and DB_cycle.index instead, nuclassemble.sh:200-207)\n"
                         "       plass-hip guidedassemble-chain <i:readDB | r1.fastq r2.fastq …> <o:nuclAssemblyDB> <o:aaAssemblyDB> [--num-iterations aa:5,nucl:5]\n"
                         "       (--nuclassembly-out DB: goes on with data/guidedNuclAssemble.sh:135-170 — the extended ORFs + the reads through nuclassemble --db-mode 1)\n"
+                        "       (assemble-chain / nuclassemble-chain --write-intermediate DIR --resume 1: go on behind the highest complete DIR/assembly_<i> of an\n"
+                        "        earlier run, the workflows' .done sentinels, data/assemble.sh:86-147; DIR/chain.manifest holds the parameters and the input it may go on with)\n"
                         "       (FASTQ pairs: merged on the GPU first, as the workflows' mergereads step, data/assemble.sh:27-38)\n"
                         "       (--single-end 1 on the three chains: every file before the output(s) is an unpaired FASTQ / FASTA read file, the workflows' createdb step)\n"
                         "       plass-hip createdb-reads <i:file[.gz]> [<i:file2> …] <o:readDB> [--shuffle 1] [--id-offset 0] [--dbtype 0]   (writes <o>, <o>_h, <o>.lookup, <o>.source)\n");
@@ -320,6 +401,7 @@ int main(int argc, char **argv) {
         else if (a == "--min-contig-len") f.minContigLen = atoi(v.c_str());
         else if (a == "--contig-output-mode") f.contigOutputMode = atoi(v.c_str());
         else if (a == "--from-reads") f.fromReads = atoi(v.c_str());
+        else if (a == "--resume") f.resume = atoi(v.c_str());
         else if (a == "--alph-size") { if (multiParam(v, "aa", t)) f.alph = atoi(t.c_str()); }
         else if (a == "--kmer-per-seq") f.kps = atoi(v.c_str());
         else if (a == "--kmer-per-seq-scale") { if (multiParam(v, "aa", t)) f.scaleAA = strtof(t.c_str(), nullptr); if (multiParam(v, "nucl", t)) f.scaleNucl = strtof(t.c_str(), nullptr); }
@@ -468,6 +550,37 @@ int main(int argc, char **argv) {
         if (stat(o->c_str(), &stO) == 0) { fprintf(stdout, "%s exists already!\n", o->c_str()); return EXIT_FAILURE; }     // nuclassemble.sh:69, guidedNuclAssemble.sh:24
     }
     if (!f.nuclAssemblyOut.empty() && f.numIterationsNucl < 1) { fprintf(stdout, "--num-iterations must be at least 1 (nucl)\n"); return EXIT_FAILURE; }
+    // --resume 1 (assemble-chain, nuclassemble-chain): go on behind the highest complete DIR/assembly_<j> of an earlier run with the same
+    // --write-intermediate DIR.  What cannot be right is refused here, before anything is read: a continuation with other parameters or
+    // another input than DIR/chain.manifest records would be a chimera of two runs.
+    int resumeFrom = -1; Manifest manifest;
+    if (f.resume) {
+        if (mod == "guidedassemble-chain") {
+            // --write-intermediate keeps assembly_nucl_<i> only; the protein twins guidedassembleresults extends next to it (guidedassembleresult.cpp:340-365) are not stored
+            fprintf(stdout, "guidedassemble-chain: --resume is not supported: --write-intermediate stores the nucleotide assembly without its protein twins, which is not enough to restart\n");
+            return EXIT_FAILURE;
+        }
+        if (f.writeIntermediate.empty()) { fprintf(stdout, "%s: --resume 1 needs --write-intermediate DIR (the resume points are DIR/assembly_<i>)\n", mod.c_str()); return EXIT_FAILURE; }
+        std::vector<std::string> inputs = fastqIn;
+        if (inputs.empty() && !pos.empty()) for (const char *sfx : {"", ".index", ".dbtype"}) inputs.push_back(pos[0] + sfx);
+        manifest = chainManifest(mod, f, inputs);
+        resumeFrom = resumePoint(f.writeIntermediate, "assembly_", f.numIterations);
+        if (resumeFrom >= 0) {
+            const std::string mp = f.writeIntermediate + "/chain.manifest";
+            if (!isFile(mp)) {
+                fprintf(stdout, "%s: --resume 1: %s/assembly_%d.done exists but %s does not: what the stored DBs were computed with is unknown (delete the .done files to start over)\n",
+                        mod.c_str(), f.writeIntermediate.c_str(), resumeFrom, mp.c_str());
+                return EXIT_FAILURE;
+            }
+            std::string inFile; const std::string key = manifestDiffers(mp, manifest, inFile);
+            if (!key.empty()) {
+                std::string now; for (const auto &kv : manifest) if (kv.first == key) now = kv.second;
+                fprintf(stdout, "%s: --resume 1: %s differs from the run that wrote %s/assembly_%d (%s: %s, this run: %s); delete the .done files to start over\n",
+                        mod.c_str(), key.c_str(), f.writeIntermediate.c_str(), resumeFrom, mp.c_str(), inFile.c_str(), now.c_str());
+                return EXIT_FAILURE;
+            }
+        }
+    }
     if (getenv("PLASSHIP_CLI_DRYRUN") && atoi(getenv("PLASSHIP_CLI_DRYRUN")) != 0) {
         fprintf(stdout, "plass-hip dry run: %s accepted (%zu positional arguments, %zu flags); nothing read or computed\n", mod.c_str(), pos.size(), f.seen.size());
         return EXIT_DRYRUN_ACCEPTED;
@@ -651,54 +764,60 @@ int main(int argc, char **argv) {
                 FILE *fd = fopen((path + ".done").c_str(), "w"); if (fd) fclose(fd); else writerRc = 1;     // data/assemble.sh:147 `touch assembly_$STEP.done`
             });
         };
-        // a multi-GB input: the library takes its device arena (seconds of hipMalloc) while this thread reads and parses the DB files
-        { struct stat stIn; if (stat(pos[0].c_str(), &stIn) == 0 && stIn.st_size >= ((off_t) 1 << 30)) (void) plasship_ctx_reserve_async(ctx); }
-        plasship_seqdb *in = nullptr;
-        if (!fastqIn.empty() && f.singleEnd) {      // the workflows' createdb step for unpaired input (data/assemble.sh:27-38): the reads stay in HBM
-            std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
-            plasship_createdb_stats cs;
-            if (K(plasship_createdb(ctx, files.data(), files.size(), nullptr, &in, &cs))) return fail(mod.c_str());
-            fprintf(stdout, "createdb: %llu reads from %llu files\n", (unsigned long long) cs.entries, (unsigned long long) cs.files);
-        } else if (!fastqIn.empty()) {         // the workflows' mergereads step (data/assemble.sh:27-38): the merged reads stay in HBM, the header DB is not needed
-            std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
-            plasship_seqdb *h = nullptr; plasship_merge_stats ms;
-            if (K(plasship_mergereads(ctx, files.data(), files.size(), nullptr, &in, &h, &ms))) return fail(mod.c_str());
-            plasship_seqdb_free(ctx, h);
-            fprintf(stdout, "mergereads: %llu pairs, %llu combined\n", (unsigned long long) ms.pairs, (unsigned long long) ms.combined);
-        } else if (K(plasship_seqdb_read(ctx, pos[0].c_str(), &in))) return fail(mod.c_str());
-        const double tRead = now();
-        int dbtype = -1; plasship_seqdb_info(in, nullptr, nullptr, nullptr, &dbtype, nullptr);
-        auto orfPar = [&](bool start) {       // the two extractorfs passes (Assembler.cpp:116-130, GuidedNuclassembler.cpp:133-145)
-            plasship_orf_params p; memset(&p, 0, sizeof(p));
-            p.min_length = start ? 20 : 45; p.max_length = start ? 45 : 32734; p.max_gaps = 0; p.contig_start_mode = start ? 1 : 2; p.contig_end_mode = start ? 0 : 2;
-            p.orf_start_mode = 0; p.forward_frames = 7; p.reverse_frames = 7; p.translation_table = 1; p.max_seq_len = 65535;
-            return p;
-        };
-        plasship_translate_params tp; tp.translation_table = 1; tp.add_orf_stop = 1; tp.max_seq_len = 65535;
-        plasship_seqdb *db = in, *aa = nullptr;          // protein / nucleotide chain: db; guided chain: db = nucleotide ORFs, aa = their twins
-        if (gd || (prot && (f.fromReads || dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES))) {
-            if (dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { fprintf(stdout, "%s: the input must be a nucleotide read DB\n", mod.c_str()); return EXIT_FAILURE; }
-            plasship_seqdb *ol = nullptr, *os = nullptr; plasship_orfhdr *hl = nullptr, *hs = nullptr; plasship_orf_stats ost;
-            const plasship_orf_params pl = orfPar(false), ps = orfPar(true);
-            if (K(plasship_extract_orfs(ctx, in, &pl, &ol, &hl, &ost)) || K(plasship_extract_orfs(ctx, in, &ps, &os, &hs, &ost))) return fail(mod.c_str());
-            if (gd) {      // concatdbs of ORFs and headers, then one translatenucs (data/guidedNuclAssemble.sh:56-75)
-                plasship_seqdb *nu = nullptr; plasship_orfhdr *hh = nullptr;
-                if (K(plasship_seqdb_concat(ctx, ol, os, &nu)) || K(plasship_orfhdr_concat(ctx, hl, hs, &hh)) || K(plasship_translate_nucs(ctx, nu, hh, &tp, &aa, &ost))) return fail(mod.c_str());
-                plasship_orfhdr_free(ctx, hh); db = nu;
-            } else {       // translatenucs x2, then concatdbs (data/assemble.sh:41-77)
-                plasship_seqdb *al = nullptr, *as = nullptr;
-                if (K(plasship_translate_nucs(ctx, ol, hl, &tp, &al, &ost)) || K(plasship_translate_nucs(ctx, os, hs, &tp, &as, &ost)) || K(plasship_seqdb_concat(ctx, al, as, &db))) return fail(mod.c_str());
-                plasship_seqdb_free(ctx, al); plasship_seqdb_free(ctx, as);
-            }
-            plasship_orfhdr_free(ctx, hl); plasship_orfhdr_free(ctx, hs); plasship_seqdb_free(ctx, ol); plasship_seqdb_free(ctx, os);
-            if (!(gd && !f.nuclAssemblyOut.empty())) { plasship_seqdb_free(ctx, in); in = nullptr; }      // (the guided tail concatenates the reads: guidedNuclAssemble.sh:161-165)
-        } else if ((prot && dbtype != PLASSHIP_DBTYPE_AMINO_ACIDS) || (nuc && dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES)) {
-            fprintf(stdout, "%s: wrong input DB type %d\n", mod.c_str(), dbtype); return EXIT_FAILURE;
-        }
-        const double tPrep = now();
         // a tail (--fasta-out; --db-mode 1 --db-out; --nuclassembly-out) needs SOURCE — the DB the loop starts from — and, on nucleotides,
         // every iteration's circular contigs: the loop keeps both
         const bool wantFasta = !f.fastaOut.empty(), wantDb = nuc && f.dbMode, wantNuclAsm = gd && !f.nuclAssemblyOut.empty();
+        if (f.resume && resumeFrom < 0 && !writeManifest(f.writeIntermediate + "/chain.manifest", manifest)) {
+            fprintf(stdout, "%s: cannot write %s/chain.manifest\n", mod.c_str(), f.writeIntermediate.c_str()); return EXIT_FAILURE;
+        }
+        // a resumed run reads DIR/assembly_<j> in place of the input; only a tail still needs the input, as SOURCE, made the way a fresh run makes it
+        plasship_seqdb *in = nullptr, *db = nullptr, *aa = nullptr; double tRead = now();
+        if (resumeFrom < 0 || wantFasta || wantDb) {
+            // a multi-GB input: the library takes its device arena (seconds of hipMalloc) while this thread reads and parses the DB files
+            { struct stat stIn; if (stat(pos[0].c_str(), &stIn) == 0 && stIn.st_size >= ((off_t) 1 << 30)) (void) plasship_ctx_reserve_async(ctx); }
+            if (!fastqIn.empty() && f.singleEnd) {      // the workflows' createdb step for unpaired input (data/assemble.sh:27-38): the reads stay in HBM
+                std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
+                plasship_createdb_stats cs;
+                if (K(plasship_createdb(ctx, files.data(), files.size(), nullptr, &in, &cs))) return fail(mod.c_str());
+                fprintf(stdout, "createdb: %llu reads from %llu files\n", (unsigned long long) cs.entries, (unsigned long long) cs.files);
+            } else if (!fastqIn.empty()) {         // the workflows' mergereads step (data/assemble.sh:27-38): the merged reads stay in HBM, the header DB is not needed
+                std::vector<const char *> files; for (const std::string &q : fastqIn) files.push_back(q.c_str());
+                plasship_seqdb *h = nullptr; plasship_merge_stats ms;
+                if (K(plasship_mergereads(ctx, files.data(), files.size(), nullptr, &in, &h, &ms))) return fail(mod.c_str());
+                plasship_seqdb_free(ctx, h);
+                fprintf(stdout, "mergereads: %llu pairs, %llu combined\n", (unsigned long long) ms.pairs, (unsigned long long) ms.combined);
+            } else if (K(plasship_seqdb_read(ctx, pos[0].c_str(), &in))) return fail(mod.c_str());
+            tRead = now();
+            int dbtype = -1; plasship_seqdb_info(in, nullptr, nullptr, nullptr, &dbtype, nullptr);
+            auto orfPar = [&](bool start) {       // the two extractorfs passes (Assembler.cpp:116-130, GuidedNuclassembler.cpp:133-145)
+                plasship_orf_params p; memset(&p, 0, sizeof(p));
+                p.min_length = start ? 20 : 45; p.max_length = start ? 45 : 32734; p.max_gaps = 0; p.contig_start_mode = start ? 1 : 2; p.contig_end_mode = start ? 0 : 2;
+                p.orf_start_mode = 0; p.forward_frames = 7; p.reverse_frames = 7; p.translation_table = 1; p.max_seq_len = 65535;
+                return p;
+            };
+            plasship_translate_params tp; tp.translation_table = 1; tp.add_orf_stop = 1; tp.max_seq_len = 65535;
+            db = in;          // protein / nucleotide chain: db; guided chain: db = nucleotide ORFs, aa = their twins
+            if (gd || (prot && (f.fromReads || dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES))) {
+                if (dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { fprintf(stdout, "%s: the input must be a nucleotide read DB\n", mod.c_str()); return EXIT_FAILURE; }
+                plasship_seqdb *ol = nullptr, *os = nullptr; plasship_orfhdr *hl = nullptr, *hs = nullptr; plasship_orf_stats ost;
+                const plasship_orf_params pl = orfPar(false), ps = orfPar(true);
+                if (K(plasship_extract_orfs(ctx, in, &pl, &ol, &hl, &ost)) || K(plasship_extract_orfs(ctx, in, &ps, &os, &hs, &ost))) return fail(mod.c_str());
+                if (gd) {      // concatdbs of ORFs and headers, then one translatenucs (data/guidedNuclAssemble.sh:56-75)
+                    plasship_seqdb *nu = nullptr; plasship_orfhdr *hh = nullptr;
+                    if (K(plasship_seqdb_concat(ctx, ol, os, &nu)) || K(plasship_orfhdr_concat(ctx, hl, hs, &hh)) || K(plasship_translate_nucs(ctx, nu, hh, &tp, &aa, &ost))) return fail(mod.c_str());
+                    plasship_orfhdr_free(ctx, hh); db = nu;
+                } else {       // translatenucs x2, then concatdbs (data/assemble.sh:41-77)
+                    plasship_seqdb *al = nullptr, *as = nullptr;
+                    if (K(plasship_translate_nucs(ctx, ol, hl, &tp, &al, &ost)) || K(plasship_translate_nucs(ctx, os, hs, &tp, &as, &ost)) || K(plasship_seqdb_concat(ctx, al, as, &db))) return fail(mod.c_str());
+                    plasship_seqdb_free(ctx, al); plasship_seqdb_free(ctx, as);
+                }
+                plasship_orfhdr_free(ctx, hl); plasship_orfhdr_free(ctx, hs); plasship_seqdb_free(ctx, ol); plasship_seqdb_free(ctx, os);
+                if (!(gd && !f.nuclAssemblyOut.empty())) { plasship_seqdb_free(ctx, in); in = nullptr; }      // (the guided tail concatenates the reads: guidedNuclAssemble.sh:161-165)
+            } else if ((prot && dbtype != PLASSHIP_DBTYPE_AMINO_ACIDS) || (nuc && dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES)) {
+                fprintf(stdout, "%s: wrong input DB type %d\n", mod.c_str(), dbtype); return EXIT_FAILURE;
+            }
+        }
+        const double tPrep = now();
         ChainLoop L;
         L.ctx = ctx; L.name = mod.c_str(); L.kind = prot ? CHAIN_PROTEIN : nuc ? CHAIN_NUCL : CHAIN_GUIDED;
         L.numIterations = f.numIterations; L.k = f.k; L.alph = f.alph; L.kps = f.kps; L.kpsScale = nuc ? f.scaleNucl : f.scaleAA; L.ignoreMulti = f.ignoreMulti;
@@ -714,6 +833,29 @@ int main(int argc, char **argv) {
         L.intermediateName = gd ? "assembly_nucl_" : "assembly_";
         L.joinWriter = [&]() { if (joinWriter()) { fprintf(stdout, "%s: writing an intermediate DB failed: %s\n", mod.c_str(), writerErr.c_str()); return 1; } return 0; };
         L.writeAsync = writeAsync;
+        L.writeLastIntermediate = f.resume != 0;
+        if (resumeFrom >= 0) {
+            // DIR/assembly_<j> is the DB iteration j handed to iteration j + 1: on nucleotides the rest after cyclecheck took the circular contigs out
+            // (they are in <o>_cycle_<i>).  The library's caches (selected windows, positions, cyclecheck's "rest" lineage) start cold, as they do
+            // for any DB read from files; none of them changes a result.
+            const std::string from = f.writeIntermediate + "/" + L.intermediateName + std::to_string(resumeFrom);
+            fprintf(stdout, "resuming at iteration %d (from %s)\n", resumeFrom + 1, from.c_str());
+            L.startIteration = resumeFrom + 1; L.source = db; db = nullptr;
+            if (K(plasship_seqdb_read(ctx, from.c_str(), &db))) return fail(mod.c_str());
+            int dbtypeFrom = -1; plasship_seqdb_info(db, nullptr, nullptr, nullptr, &dbtypeFrom, nullptr);
+            if (dbtypeFrom != (prot ? PLASSHIP_DBTYPE_AMINO_ACIDS : PLASSHIP_DBTYPE_NUCLEOTIDES)) { fprintf(stdout, "%s: wrong DB type %d of %s\n", mod.c_str(), dbtypeFrom, from.c_str()); return EXIT_FAILURE; }
+            // PREV_CYCLE_ALL of the tail: the circular contigs of the iterations up to j, from the files the interrupted run wrote next to its output
+            for (int i = 0; nuc && L.keepForTail && i <= resumeFrom; i++) {
+                const std::string cp = L.cyclePrefix + std::to_string(i);
+                if (!isFile(cp) || !isFile(cp + ".index")) continue;       // (an iteration without circular contigs writes no file)
+                plasship_seqdb *cyc = nullptr;
+                if (K(plasship_seqdb_read(ctx, cp.c_str(), &cyc))) return fail(mod.c_str());
+                if (!L.cycAll) { L.cycAll = cyc; continue; }
+                plasship_seqdb *u = nullptr;
+                if (K(plasship_seqdb_concat_keys(ctx, L.cycAll, cyc, 1, &u))) return fail(mod.c_str());
+                plasship_seqdb_free(ctx, L.cycAll); plasship_seqdb_free(ctx, cyc); L.cycAll = u;
+            }
+        }
         L.db = db; L.aa = aa; L.tStart = tPrep;
         if (const int rcL = runChainLoop(L)) return rcL;
         db = L.db; aa = L.aa;
