@@ -205,6 +205,32 @@ int plasship_rescore(plasship_ctx *ctx, const plasship_seqdb *qdb, const plasshi
                      const plasship_cands *c, const plasship_rescore_params *par, plasship_alns **out,
                      plasship_rescore_stats *stats);
 
+/* ---- rescorediagonal --rescore-mode 0 [--wrapped-scoring 1]  (the Hamming pre-clustering call of linclust,
+ *      mm/data/workflow/linclust.sh:30, which `penguin guided_nuclassemble` ends with; doRescorediagonal for RESCORE_MODE_HAMMING,
+ *      mm/alignment/rescorediagonal.cpp:146-356, with DistanceCalculator::computeUngappedWrappedAlignment / computeUngappedAlignment,
+ *      mm/alignment/DistanceCalculator.h:57-175,276-295).  The score of a pair is the number of equal bytes along the diagonal (case-sensitive);
+ *      with `wrapped` the query is circular — every alias diagonal +/- d * 65536 of the stored 16-bit diagonal is tried against the doubled
+ *      query, a target longer than the query is skipped — and the DBs must be nucleotides (PLASSHIP_ERR_ARG otherwise, an error in the
+ *      reference too).  `c` is any candidate list (plasship_kmermatch, plasship_cands_read), with strands (DBTYPE_PREFILTER_REV_RES:
+ *      prefScore < 0 scores the reverse complement of the query) or without.  The result is a candidate list again: the lines that pass
+ *      canBeCovered, coverage, --min-seq-id, --min-aln-len and -e, and every identity pair (qdb == tdb, same id), in the order of the
+ *      input, with prefScore = (int)(100 * seqId), negated for a reverse hit, and the best alias' diagonal; plasship_cands_write writes
+ *      the DB the reference writes, with the input's dbtype.  --filter-hits and --sort-results are not implemented (the workflows pass 0).
+ *      A context with a communicator of more than one rank: PLASSHIP_ERR_UNSUPPORTED.
+ *      stats: n_scored = pairs in `c`, n_accepted = lines kept, overlap_residues = residues compared (diagonal length x aliases tried). ---- */
+typedef struct plasship_hamming_params {
+    int32_t wrapped;      /* --wrapped-scoring                       */
+    float   seq_id_thr;   /* --min-seq-id                            */
+    int32_t seq_id_mode;  /* --seq-id-mode                           */
+    int32_t cov_mode;     /* --cov-mode                              */
+    float   cov_thr;      /* -c                                      */
+    int32_t min_aln_len;  /* --min-aln-len                           */
+    double  eval_thr;     /* -e (the Hamming e-value is always 0)    */
+} plasship_hamming_params;
+int plasship_rescore_hamming(plasship_ctx *ctx, const plasship_seqdb *qdb, const plasship_seqdb *tdb,
+                             const plasship_cands *c, const plasship_hamming_params *par,
+                             plasship_cands **out, plasship_rescore_stats *stats);
+
 /* alignment DB <-> device (Matcher::resultToBuffer / parseAlignmentRecord, mm/alignment/Matcher.cpp:248-370) */
 int plasship_alns_write(plasship_ctx *ctx, const plasship_alns *a, const char *db_path);
 int plasship_alns_read(plasship_ctx *ctx, const plasship_seqdb *db, const char *db_path, plasship_alns **out);

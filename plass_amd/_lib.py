@@ -41,6 +41,11 @@ class RescoreStats(C.Structure):
     _fields_ = [("n_scored", C.c_uint64), ("n_accepted", C.c_uint64), ("overlap_residues", C.c_uint64), ("ms_kernel", C.c_float)]
 
 
+class _HammingParams(C.Structure):
+    _fields_ = [("wrapped", C.c_int32), ("seq_id_thr", C.c_float), ("seq_id_mode", C.c_int32), ("cov_mode", C.c_int32),
+                ("cov_thr", C.c_float), ("min_aln_len", C.c_int32), ("eval_thr", C.c_double)]
+
+
 class _AssembleParams(C.Structure):
     _fields_ = [("seq_id_thr", C.c_float), ("max_seq_len", C.c_uint64), ("keep_target", C.c_int32), ("rescore_mode", C.c_int32)]
 
@@ -168,6 +173,7 @@ SYMBOLS = [
     ("plasship_cands_download", C.c_int, [P, P, P, P, P, P, P, P]),
     ("plasship_cands_free", None, [P, P]),
     ("plasship_rescore", C.c_int, [P, P, P, P, C.POINTER(_RescoreParams), C.POINTER(P), C.POINTER(RescoreStats)]),
+    ("plasship_rescore_hamming", C.c_int, [P, P, P, P, C.POINTER(_HammingParams), C.POINTER(P), C.POINTER(RescoreStats)]),
     ("plasship_alns_write", C.c_int, [P, P, C.c_char_p]),
     ("plasship_alns_read", C.c_int, [P, P, C.c_char_p, C.POINTER(P)]),
     ("plasship_alns_count", C.c_int, [P, C.POINTER(C.c_uint64)]),
@@ -417,6 +423,15 @@ class Context:
         h = P(); st = RescoreStats(); cp = par._c()
         _check(self.lib.plasship_rescore(self.h, qdb.h, tdb.h, cands.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore")
         return Alignments(self, h, qdb, tdb), st
+
+    def rescore_hamming(self, qdb, tdb, cands, wrapped=True, min_seq_id=0.0, seq_id_mode=0, cov_mode=0, c=0.0, min_aln_len=0, e=1e-3):
+        """`rescorediagonal --rescore-mode 0` (the Hamming score; wrapped: --wrapped-scoring 1, the circular query of linclust's
+        pre-clustering call) on a candidate list -> (the kept lines as Candidates, RescoreStats).  Defaults = the reference module's,
+        except `wrapped`; linclust passes min_seq_id=0.97, cov_mode=1, c=0.99"""
+        h = P(); st = RescoreStats()
+        cp = _HammingParams(int(bool(wrapped)), min_seq_id, seq_id_mode, cov_mode, c, min_aln_len, e)
+        _check(self.lib.plasship_rescore_hamming(self.h, qdb.h, tdb.h, cands.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore_hamming")
+        return Candidates(self, h, qdb, tdb), st
 
     def read_alndb(self, db, path):
         h = P()

@@ -167,8 +167,9 @@ typedef Handle<plasship_cands, plasship_cands_free> Cands; typedef Handle<plassh
 enum : unsigned {
     KMERMATCHER = 1u << 0, RESCOREDIAGONAL = 1u << 1, ASSEMBLERESULTS = 1u << 2, NUCLASSEMBLERESULTS = 1u << 3, GUIDEDASSEMBLERESULTS = 1u << 4, PROTEINALN2NUCL = 1u << 5,
     FINDASSEMBLYSTART = 1u << 6, CYCLECHECK = 1u << 7, EXTRACTORFS = 1u << 8, TRANSLATENUCS = 1u << 9, CONCATDBS = 1u << 10, ASSEMBLE_CHAIN = 1u << 11,
-    NUCLASSEMBLE_CHAIN = 1u << 12, GUIDEDASSEMBLE_CHAIN = 1u << 13, CREATEDB_READS = 1u << 14, MERGEREADS = 1u << 15,
-    ANY_ASSEMBLERESULTS = ASSEMBLERESULTS | NUCLASSEMBLERESULTS | GUIDEDASSEMBLERESULTS, CHAINS = ASSEMBLE_CHAIN | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN, ALL = 0xFFFFu
+    NUCLASSEMBLE_CHAIN = 1u << 12, GUIDEDASSEMBLE_CHAIN = 1u << 13, CREATEDB_READS = 1u << 14, MERGEREADS = 1u << 15, RESCOREDIAGONAL_HAMMING = 1u << 16,
+    ANY_ASSEMBLERESULTS = ASSEMBLERESULTS | NUCLASSEMBLERESULTS | GUIDEDASSEMBLERESULTS, CHAINS = ASSEMBLE_CHAIN | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN,
+    ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING, ALL = 0x1FFFFu     // (rescorediagonal-hamming takes rescorediagonal's flag set)
 };
 
 // ---- the flags: each once, with the modules that own it (its parameter vector in the reference; for the fused drivers the workflow's own),
@@ -210,21 +211,21 @@ static int idOffsetFlag(Flags &f, unsigned mod, const std::string &v) {       //
 static const Flag kFlags[] = {
     {"--threads", ALL, IGNORED}, {"-v", ALL, IGNORED}, {"--compressed", ALL, ZERO},
     // shared by several modules (and the fused drivers, which take the workflows' own flags)
-    {"--sub-mat", KMERMATCHER | RESCOREDIAGONAL | PROTEINALN2NUCL, CUSTOM, {}, {}, subMatFlag}, {"--alph-size", KMERMATCHER | CHAINS, AA, M(alph)},
-    {"--min-seq-id", KMERMATCHER | RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, CUSTOM, {}, {}, minSeqIdFlag}, {"--kmer-per-seq", KMERMATCHER | CHAINS, VALUE, M(kps)},
-    {"--kmer-per-seq-scale", KMERMATCHER | CHAINS, BOTH, M(scaleAA), M(scaleNucl)}, {"--cov-mode", KMERMATCHER | RESCOREDIAGONAL | CHAINS, VALUE, M(covMode)},
-    {"-k", KMERMATCHER | CHAINS, BOTH_GUIDED, M(k), M(kNucl)}, {"-c", KMERMATCHER | RESCOREDIAGONAL | CHAINS, VALUE, M(covThr)},
+    {"--sub-mat", KMERMATCHER | ANY_RESCOREDIAGONAL | PROTEINALN2NUCL, CUSTOM, {}, {}, subMatFlag}, {"--alph-size", KMERMATCHER | CHAINS, AA, M(alph)},
+    {"--min-seq-id", KMERMATCHER | ANY_RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, CUSTOM, {}, {}, minSeqIdFlag}, {"--kmer-per-seq", KMERMATCHER | CHAINS, VALUE, M(kps)},
+    {"--kmer-per-seq-scale", KMERMATCHER | CHAINS, BOTH, M(scaleAA), M(scaleNucl)}, {"--cov-mode", KMERMATCHER | ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(covMode)},
+    {"-k", KMERMATCHER | CHAINS, BOTH_GUIDED, M(k), M(kNucl)}, {"-c", KMERMATCHER | ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(covThr)},
     {"--max-seq-len", KMERMATCHER | ANY_ASSEMBLERESULTS | CYCLECHECK | CHAINS, VALUE, M(maxSeqLen)}, {"--hash-shift", KMERMATCHER | CHAINS, VALUE, M(hashShift)},
-    {"--ignore-multi-kmer", KMERMATCHER | CHAINS, BOOL, M(ignoreMulti)}, {"--rescore-mode", RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, VALUE, M(rescoreMode)},
-    {"-e", RESCOREDIAGONAL | CHAINS, VALUE, M(evalThr)}, {"--min-aln-len", RESCOREDIAGONAL | CHAINS, BOTH_GUIDED, M(minAlnLen), M(minAlnLenNucl)},
-    {"--seq-id-mode", RESCOREDIAGONAL | CHAINS, VALUE, M(seqIdMode)}, {"--keep-target", ANY_ASSEMBLERESULTS | CHAINS, BOOL, M(keepTarget)},
+    {"--ignore-multi-kmer", KMERMATCHER | CHAINS, BOOL, M(ignoreMulti)}, {"--rescore-mode", ANY_RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, VALUE, M(rescoreMode)},
+    {"-e", ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(evalThr)}, {"--min-aln-len", ANY_RESCOREDIAGONAL | CHAINS, BOTH_GUIDED, M(minAlnLen), M(minAlnLenNucl)},
+    {"--seq-id-mode", ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(seqIdMode)}, {"--keep-target", ANY_ASSEMBLERESULTS | CHAINS, BOOL, M(keepTarget)},
     {"--chop-cycle", CYCLECHECK | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN, BOOL, M(chopCycle)}, {"--translation-table", EXTRACTORFS | TRANSLATENUCS, VALUE, M(translationTable)},
     {"--id-offset", EXTRACTORFS | CREATEDB_READS, CUSTOM, {}, {}, idOffsetFlag},
     // one module's own
     {"--spaced-kmer-mode", KMERMATCHER, ZERO}, {"--spaced-kmer-pattern", KMERMATCHER, EMPTY}, {"--adjust-kmer-len", KMERMATCHER, ZERO_BOOL}, {"--mask", KMERMATCHER, ZERO},
     {"--mask-lower-case", KMERMATCHER, ZERO}, {"--split-memory-limit", KMERMATCHER, IGNORED}, {"--include-only-extendable", KMERMATCHER, BOOL, M(onlyExt)},
-    {"--wrapped-scoring", RESCOREDIAGONAL, BOOL, M(wrapped)}, {"--filter-hits", RESCOREDIAGONAL, BOOL, M(filterHits)}, {"-a", RESCOREDIAGONAL, BOOL, M(addBt)},
-    {"--add-self-matches", RESCOREDIAGONAL, BOOL, M(addSelf)}, {"--sort-results", RESCOREDIAGONAL, VALUE, M(sortResults)}, {"--db-load-mode", RESCOREDIAGONAL, IGNORED},
+    {"--wrapped-scoring", ANY_RESCOREDIAGONAL, BOOL, M(wrapped)}, {"--filter-hits", ANY_RESCOREDIAGONAL, BOOL, M(filterHits)}, {"-a", ANY_RESCOREDIAGONAL, BOOL, M(addBt)},
+    {"--add-self-matches", ANY_RESCOREDIAGONAL, BOOL, M(addSelf)}, {"--sort-results", ANY_RESCOREDIAGONAL, VALUE, M(sortResults)}, {"--db-load-mode", ANY_RESCOREDIAGONAL, IGNORED},
     {"--gap-open", PROTEINALN2NUCL, NUCL, M(gapOpenNucl)}, {"--gap-extend", PROTEINALN2NUCL, NUCL, M(gapExtendNucl)},
     {"--min-length", EXTRACTORFS, VALUE, M(orfMin)}, {"--max-length", EXTRACTORFS, VALUE, M(orfMax)}, {"--max-gaps", EXTRACTORFS, VALUE, M(orfGaps)},
     {"--contig-start-mode", EXTRACTORFS, VALUE, M(contigStart)}, {"--contig-end-mode", EXTRACTORFS, VALUE, M(contigEnd)}, {"--orf-start-mode", EXTRACTORFS, VALUE, M(orfStart)},
@@ -500,6 +501,12 @@ static int validateRescorediagonal(Call &c) {
     if (c.f.wrapped || c.f.filterHits || c.f.sortResults) return unsupported("--wrapped-scoring/--filter-hits/--sort-results are not supported by plass-hip\n");
     return c.f.rescoreMode != 3 ? unsupported("plass-hip rescorediagonal: --rescore-mode %d is not part of the GPU path (the assembly workflows use mode 3)\n", c.f.rescoreMode) : 0;
 }
+// rescorediagonal-hamming (our own name: the row above keeps its answers): linclust's Hamming pre-clustering call, lib/mmseqs/data/workflow/linclust.sh:30
+static int validateRescoreHamming(Call &c) {
+    if (c.f.filterHits || c.f.sortResults > 0) return unsupported("plass-hip rescorediagonal-hamming: --filter-hits 1 / --sort-results are not part of the GPU path\n");
+    if (c.f.rescoreMode != 0) return unsupported("plass-hip rescorediagonal-hamming: --rescore-mode %d is not this module's (0, the Hamming score, only)\n", c.f.rescoreMode);
+    return c.pos.size() == 4 && c.pos[0] != c.pos[1] ? unsupported("plass-hip rescorediagonal-hamming: separate query and target DBs are not part of the GPU path (linclust uses one DB)\n") : 0;
+}
 // Requests that are valid for the reference and lie outside the GPU path are all refused in validate(), before the dry-run exit and before anything
 // is read or written (data/nuclassemble.sh:41,145 calls `concatdbs ... --preserve-keys` whenever circular contigs exist; with exit
 // code 1 the wrapper ended the workflow instead of handing the call to the reference, and the dry run reported it as accepted)
@@ -604,6 +611,19 @@ static int runRescorediagonal(Call &c) {
     if (K(plasship_rescore(ctx, q, t, cands, &p, al.out(), &st))) return fail("rescorediagonal");
     fprintf(stdout, "scored: %llu accepted: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_scored, (unsigned long long) st.n_accepted, st.ms_kernel);
     return KW(plasship_alns_write(ctx, al, pos[3].c_str())) ? fail("rescorediagonal") : EXIT_SUCCESS;
+}
+static int runRescoreHamming(Call &c) {           // (query and target are one DB: validateRescoreHamming)
+    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos; const Flags &f = c.f;
+    SeqDb db(ctx); Cands cands(ctx), kept(ctx);
+    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out())) || K(plasship_cands_read(ctx, db, db, pos[2].c_str(), cands.out()))) return fail("rescorediagonal-hamming");
+    plasship_hamming_params p = {}; plasship_rescore_stats st = {};
+    p.wrapped = f.wrapped; p.seq_id_thr = f.seqIdThr; p.seq_id_mode = f.seqIdMode; p.cov_mode = f.covMode; p.cov_thr = f.covThr; p.min_aln_len = f.minAlnLen; p.eval_thr = f.evalThr;
+    if (K(plasship_rescore_hamming(ctx, db, db, cands, &p, kept.out(), &st))) {
+        // (wrapped scoring on a DB that is not nucleotides is an error of the call, in the reference as well: not a case for the reference binary)
+        return fail("rescorediagonal-hamming");
+    }
+    fprintf(stdout, "scored: %llu kept: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_scored, (unsigned long long) st.n_accepted, st.ms_kernel);
+    return KW(plasship_cands_write(ctx, kept, db, pos[3].c_str())) ? fail("rescorediagonal-hamming") : EXIT_SUCCESS;
 }
 static int runAssembleresults(Call &c) {          // assembleresults and nuclassembleresults
     plasship_ctx *ctx = c.ctx; SeqDb db(ctx); Alns al(ctx); SeqDb o(ctx);
@@ -867,6 +887,7 @@ static void chainDefaults(Flags &f) { f.alph = 13; f.kps = 60; f.ignoreMulti = 1
 static const Module kModules[] = {
     {"kmermatcher", KMERMATCHER, 2, "kmermatcher <i:sequenceDB> <o:prefDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; }, validateKmermatcher, runKmermatcher},
     {"rescorediagonal", RESCOREDIAGONAL, 4, "rescorediagonal <i:queryDB> <i:targetDB> <i:prefDB> <o:alnDB>", nullptr, validateRescorediagonal, runRescorediagonal},
+    {"rescorediagonal-hamming", RESCOREDIAGONAL_HAMMING, 4, "rescorediagonal-hamming <i:queryDB> <i:targetDB> <i:prefDB> <o:prefDB>", nullptr, validateRescoreHamming, runRescoreHamming},
     {"assembleresults", ASSEMBLERESULTS, 3, "assembleresults <i:sequenceDB> <i:alnResult> <o:reprSeqDB>", nullptr, nullptr, runAssembleresults},
     {"nuclassembleresults", NUCLASSEMBLERESULTS, 3, "nuclassembleresults <i:sequenceDB> <i:alnResult> <o:reprSeqDB>", nullptr, nullptr, runAssembleresults},
     {"guidedassembleresults", GUIDEDASSEMBLERESULTS, 5, "guidedassembleresults <i:nuclSequenceDB> <i:aaSequenceDB> <i:nuclAlnResult> <o:nuclAssembly> <o:aaAssembly>", nullptr, nullptr, runGuidedassembleresults},
