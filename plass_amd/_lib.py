@@ -11,6 +11,11 @@ def lib_path():
     return os.environ.get("PLASSHIP_LIB") or os.path.join(_HERE, "libplasship.so")
 
 
+def clust_lib_path():
+    """the extension library with greedy clustering (include/plasship_ext/clust.h), beside the C-ABI library"""
+    return os.path.join(os.path.dirname(lib_path()), "libplasship_clust.so")
+
+
 class PlasshipError(RuntimeError):
     pass
 
@@ -44,6 +49,11 @@ class RescoreStats(C.Structure):
 class _HammingParams(C.Structure):
     _fields_ = [("wrapped", C.c_int32), ("seq_id_thr", C.c_float), ("seq_id_mode", C.c_int32), ("cov_mode", C.c_int32),
                 ("cov_thr", C.c_float), ("min_aln_len", C.c_int32), ("eval_thr", C.c_double)]
+
+
+class ClustStats(C.Structure):
+    _fields_ = [("n_sequences", C.c_uint64), ("n_edges", C.c_uint64), ("n_clusters", C.c_uint64), ("n_promoted", C.c_uint64),
+                ("n_long_queries", C.c_uint64), ("ms_kernel", C.c_float)]
 
 
 class _AssembleParams(C.Structure):
@@ -200,6 +210,16 @@ SYMBOLS = [
     ("plasship_fasta_write", C.c_int, [P, P, P, C.c_char_p, C.POINTER(FastaStats)]),
     ("plasship_subdb_write", C.c_int, [P, P, P, C.c_char_p, C.POINTER(SubdbStats)]),
 ]
+# include/plasship_ext/clust.h (the extension library libplasship_clust.so: linclust's greedy clustering and pre-cluster subset)
+CLUST_SYMBOLS = [
+    ("plasship_clust_greedy_cands", C.c_int, [P, P, P, C.POINTER(P), C.POINTER(ClustStats)]),
+    ("plasship_clust_greedy_alns", C.c_int, [P, P, P, C.POINTER(P), C.POINTER(ClustStats)]),
+    ("plasship_clusters_count", C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("plasship_clusters_download", C.c_int, [P, P, P, P, P]),
+    ("plasship_clusters_write", C.c_int, [P, P, P, C.c_char_p]),
+    ("plasship_clusters_free", None, [P, P]),
+    ("plasship_cands_filter", C.c_int, [P, P, P, C.POINTER(P)]),
+]
 # include/plasship_rccl.h (native RCCL communicator of a sharded run)
 RCCL_SYMBOLS = [
     ("plasship_rccl_get_unique_id", C.c_int, [P]),
@@ -227,6 +247,15 @@ def load_library():
     lib = C.CDLL(path)
     for name, res, args in SYMBOLS + SYNTH_SYMBOLS + RCCL_SYMBOLS:
         fn = getattr(lib, name)          # AttributeError if the export is missing
+        fn.restype = res
+        fn.argtypes = args
+    # the extension library beside it (greedy clustering): its entry points are reached as lib.clust.<name>
+    cpath = clust_lib_path()
+    if not os.path.exists(cpath):
+        raise PlasshipError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`" % cpath)
+    lib.clust = C.CDLL(cpath)
+    for name, res, args in CLUST_SYMBOLS:
+        fn = getattr(lib.clust, name)
         fn.restype = res
         fn.argtypes = args
     _lib = lib
@@ -432,6 +461,23 @@ class Context:
         cp = _HammingParams(int(bool(wrapped)), min_seq_id, seq_id_mode, cov_mode, c, min_aln_len, e)
         _check(self.lib.plasship_rescore_hamming(self.h, qdb.h, tdb.h, cands.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore_hamming")
         return Candidates(self, h, qdb, tdb), st
+
+    def clust_greedy(self, db, cands_or_alns):
+        """`clust --cluster-mode 2 | 3` (greedy incremental clustering: the longest sequence that lists a sequence represents it) on a
+        candidate list or an alignment list made on `db` -> (Clusters, ClustStats)"""
+        h = P(); st = ClustStats()
+        if isinstance(cands_or_alns, Alignments):
+            _check(self.lib.clust.plasship_clust_greedy_alns(self.h, db.h, cands_or_alns.h, C.byref(h), C.byref(st)), "plasship_clust_greedy_alns")
+        else:
+            _check(self.lib.clust.plasship_clust_greedy_cands(self.h, db.h, cands_or_alns.h, C.byref(h), C.byref(st)), "plasship_clust_greedy_cands")
+        return Clusters(self, h, db), st
+
+    def filter_cands(self, cands, clusters):
+        """what linclust's createsubdb + filterdb leave of a candidate list: the representatives' entries, and in them the lines whose
+        target is a representative -> Candidates (write() writes the representatives' entries only)"""
+        h = P()
+        _check(self.lib.clust.plasship_cands_filter(self.h, cands.h, clusters.h, C.byref(h)), "plasship_cands_filter")
+        return Candidates(self, h, cands.qdb, cands.tdb)
 
     def read_alndb(self, db, path):
         h = P()
@@ -707,6 +753,33 @@ class Candidates:
     def free(self):
         if self.h:
             self.ctx.lib.plasship_cands_free(self.ctx.h, self.h); self.h = P()
+
+
+class Clusters:
+    """greedy clustering of a DB, device resident"""
+    def __init__(self, ctx, h, db):
+        self.ctx, self.h, self.db = ctx, h, db      # keeps the DB alive (ids -> keys)
+
+    def count(self):
+        """(members = DB size, clusters)"""
+        n = C.c_uint64(); k = C.c_uint64()
+        _check(self.ctx.lib.clust.plasship_clusters_count(self.h, C.byref(n), C.byref(k)), "plasship_clusters_count")
+        return n.value, k.value
+
+    def download(self, db=None):
+        """(representative keys, member keys), sorted by representative key, then member key"""
+        import numpy as np
+        n = self.count()[0]
+        rep = np.zeros(n, dtype=np.uint32); mem = np.zeros(n, dtype=np.uint32)
+        _check(self.ctx.lib.clust.plasship_clusters_download(self.ctx.h, self.h, (db or self.db).h, rep.ctypes.data, mem.ctypes.data), "plasship_clusters_download")
+        return rep, mem
+
+    def write(self, path, db=None):
+        _check(self.ctx.lib.clust.plasship_clusters_write(self.ctx.h, self.h, (db or self.db).h, os.fsencode(path)), "plasship_clusters_write")
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.clust.plasship_clusters_free(self.ctx.h, self.h); self.h = P()
 
 
 class Alignments:

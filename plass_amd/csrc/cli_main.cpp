@@ -10,6 +10,7 @@
 // the result (--threads, -v, --db-load-mode, --compressed 0 …) are accepted and ignored; values this build cannot honour
 // (another substitution matrix, spaced k-mers, masking, automatic k …) fail loudly like Debug(Debug::ERROR) + EXIT(EXIT_FAILURE).
 #include "../../include/plasship.h"
+#include "../../include/plasship_ext/clust.h"
 #include <chrono>
 #include <unistd.h>
 #include <cstdarg>
@@ -69,6 +70,7 @@ struct Flags {
     // createdb-reads and the chains' --single-end 1 (unpaired read files through plasship_createdb): createdb's own defaults (Parameters.cpp: --shuffle 1)
     int singleEnd = 0, shuffle = 1, dbtypeArg = 0, createdbMode = 0, writeLookup = 1; unsigned long long idOffset = 0;
     std::string dbOut, nuclAssemblyOut; int dbMode = 0, numIterationsNucl = 5, kNucl = 22, minAlnLenNucl = 0;
+    int clusterMode = 0;                 // clust: Parameters::SET_COVER (not one of kMembers: the dump's lines are pinned as they are)
     std::set<std::string> seen;
 };
 
@@ -162,6 +164,7 @@ template <class T, void (*Free)(plasship_ctx *, T *)> struct Handle {
 };
 typedef Handle<plasship_seqdb, plasship_seqdb_free> SeqDb; typedef Handle<plasship_orfhdr, plasship_orfhdr_free> OrfHdr;
 typedef Handle<plasship_cands, plasship_cands_free> Cands; typedef Handle<plasship_alns, plasship_alns_free> Alns;
+typedef Handle<plasship_clusters, plasship_clusters_free> Clusters;
 
 // ---- the modules: one bit each, so that a flag states its owners as a mask ----
 enum : unsigned {
@@ -169,7 +172,10 @@ enum : unsigned {
     FINDASSEMBLYSTART = 1u << 6, CYCLECHECK = 1u << 7, EXTRACTORFS = 1u << 8, TRANSLATENUCS = 1u << 9, CONCATDBS = 1u << 10, ASSEMBLE_CHAIN = 1u << 11,
     NUCLASSEMBLE_CHAIN = 1u << 12, GUIDEDASSEMBLE_CHAIN = 1u << 13, CREATEDB_READS = 1u << 14, MERGEREADS = 1u << 15, RESCOREDIAGONAL_HAMMING = 1u << 16,
     ANY_ASSEMBLERESULTS = ASSEMBLERESULTS | NUCLASSEMBLERESULTS | GUIDEDASSEMBLERESULTS, CHAINS = ASSEMBLE_CHAIN | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN,
-    ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING, ALL = 0x1FFFFu     // (rescorediagonal-hamming takes rescorediagonal's flag set)
+    CLUST_GREEDY = 1u << 17, LINCLUST_PRE = 1u << 18,
+    // (rescorediagonal-hamming takes rescorediagonal's flag set, clust-greedy clust's; linclust-pre the union of its three steps')
+    ANY_KMERMATCHER = KMERMATCHER | LINCLUST_PRE, ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING | LINCLUST_PRE, ANY_CLUST = CLUST_GREEDY | LINCLUST_PRE,
+    ALL = 0x7FFFFu
 };
 
 // ---- the flags: each once, with the modules that own it (its parameter vector in the reference; for the fused drivers the workflow's own),
@@ -211,21 +217,22 @@ static int idOffsetFlag(Flags &f, unsigned mod, const std::string &v) {       //
 static const Flag kFlags[] = {
     {"--threads", ALL, IGNORED}, {"-v", ALL, IGNORED}, {"--compressed", ALL, ZERO},
     // shared by several modules (and the fused drivers, which take the workflows' own flags)
-    {"--sub-mat", KMERMATCHER | ANY_RESCOREDIAGONAL | PROTEINALN2NUCL, CUSTOM, {}, {}, subMatFlag}, {"--alph-size", KMERMATCHER | CHAINS, AA, M(alph)},
-    {"--min-seq-id", KMERMATCHER | ANY_RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, CUSTOM, {}, {}, minSeqIdFlag}, {"--kmer-per-seq", KMERMATCHER | CHAINS, VALUE, M(kps)},
-    {"--kmer-per-seq-scale", KMERMATCHER | CHAINS, BOTH, M(scaleAA), M(scaleNucl)}, {"--cov-mode", KMERMATCHER | ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(covMode)},
-    {"-k", KMERMATCHER | CHAINS, BOTH_GUIDED, M(k), M(kNucl)}, {"-c", KMERMATCHER | ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(covThr)},
-    {"--max-seq-len", KMERMATCHER | ANY_ASSEMBLERESULTS | CYCLECHECK | CHAINS, VALUE, M(maxSeqLen)}, {"--hash-shift", KMERMATCHER | CHAINS, VALUE, M(hashShift)},
-    {"--ignore-multi-kmer", KMERMATCHER | CHAINS, BOOL, M(ignoreMulti)}, {"--rescore-mode", ANY_RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, VALUE, M(rescoreMode)},
+    {"--sub-mat", ANY_KMERMATCHER | ANY_RESCOREDIAGONAL | PROTEINALN2NUCL, CUSTOM, {}, {}, subMatFlag}, {"--alph-size", ANY_KMERMATCHER | CHAINS, AA, M(alph)},
+    {"--min-seq-id", ANY_KMERMATCHER | ANY_RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, CUSTOM, {}, {}, minSeqIdFlag}, {"--kmer-per-seq", ANY_KMERMATCHER | CHAINS, VALUE, M(kps)},
+    {"--kmer-per-seq-scale", ANY_KMERMATCHER | CHAINS, BOTH, M(scaleAA), M(scaleNucl)}, {"--cov-mode", ANY_KMERMATCHER | ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(covMode)},
+    {"-k", ANY_KMERMATCHER | CHAINS, BOTH_GUIDED, M(k), M(kNucl)}, {"-c", ANY_KMERMATCHER | ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(covThr)},
+    {"--max-seq-len", ANY_KMERMATCHER | ANY_ASSEMBLERESULTS | CYCLECHECK | CHAINS, VALUE, M(maxSeqLen)}, {"--hash-shift", ANY_KMERMATCHER | CHAINS, VALUE, M(hashShift)},
+    {"--ignore-multi-kmer", ANY_KMERMATCHER | CHAINS, BOOL, M(ignoreMulti)}, {"--rescore-mode", ANY_RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, VALUE, M(rescoreMode)},
     {"-e", ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(evalThr)}, {"--min-aln-len", ANY_RESCOREDIAGONAL | CHAINS, BOTH_GUIDED, M(minAlnLen), M(minAlnLenNucl)},
     {"--seq-id-mode", ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(seqIdMode)}, {"--keep-target", ANY_ASSEMBLERESULTS | CHAINS, BOOL, M(keepTarget)},
     {"--chop-cycle", CYCLECHECK | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN, BOOL, M(chopCycle)}, {"--translation-table", EXTRACTORFS | TRANSLATENUCS, VALUE, M(translationTable)},
     {"--id-offset", EXTRACTORFS | CREATEDB_READS, CUSTOM, {}, {}, idOffsetFlag},
     // one module's own
-    {"--spaced-kmer-mode", KMERMATCHER, ZERO}, {"--spaced-kmer-pattern", KMERMATCHER, EMPTY}, {"--adjust-kmer-len", KMERMATCHER, ZERO_BOOL}, {"--mask", KMERMATCHER, ZERO},
-    {"--mask-lower-case", KMERMATCHER, ZERO}, {"--split-memory-limit", KMERMATCHER, IGNORED}, {"--include-only-extendable", KMERMATCHER, BOOL, M(onlyExt)},
+    {"--spaced-kmer-mode", ANY_KMERMATCHER, ZERO}, {"--spaced-kmer-pattern", ANY_KMERMATCHER, EMPTY}, {"--adjust-kmer-len", ANY_KMERMATCHER, ZERO_BOOL}, {"--mask", ANY_KMERMATCHER, ZERO},
+    {"--mask-lower-case", ANY_KMERMATCHER, ZERO}, {"--split-memory-limit", ANY_KMERMATCHER, IGNORED}, {"--include-only-extendable", ANY_KMERMATCHER, BOOL, M(onlyExt)},
     {"--wrapped-scoring", ANY_RESCOREDIAGONAL, BOOL, M(wrapped)}, {"--filter-hits", ANY_RESCOREDIAGONAL, BOOL, M(filterHits)}, {"-a", ANY_RESCOREDIAGONAL, BOOL, M(addBt)},
     {"--add-self-matches", ANY_RESCOREDIAGONAL, BOOL, M(addSelf)}, {"--sort-results", ANY_RESCOREDIAGONAL, VALUE, M(sortResults)}, {"--db-load-mode", ANY_RESCOREDIAGONAL, IGNORED},
+    {"--cluster-mode", ANY_CLUST, VALUE, M(clusterMode)}, {"--max-iterations", ANY_CLUST, IGNORED}, {"--similarity-type", ANY_CLUST, IGNORED},
     {"--gap-open", PROTEINALN2NUCL, NUCL, M(gapOpenNucl)}, {"--gap-extend", PROTEINALN2NUCL, NUCL, M(gapExtendNucl)},
     {"--min-length", EXTRACTORFS, VALUE, M(orfMin)}, {"--max-length", EXTRACTORFS, VALUE, M(orfMax)}, {"--max-gaps", EXTRACTORFS, VALUE, M(orfGaps)},
     {"--contig-start-mode", EXTRACTORFS, VALUE, M(contigStart)}, {"--contig-end-mode", EXTRACTORFS, VALUE, M(contigEnd)}, {"--orf-start-mode", EXTRACTORFS, VALUE, M(orfStart)},
@@ -283,6 +290,11 @@ static plasship_rescore_params rescoreParams(const Flags &f) {
     plasship_rescore_params p = {};
     p.rescore_mode = f.rescoreMode; p.eval_thr = f.evalThr; p.seq_id_thr = f.seqIdThr; p.cov_mode = f.covMode; p.cov_thr = f.covThr;
     p.min_aln_len = f.minAlnLen; p.seq_id_mode = f.seqIdMode; p.add_backtrace = f.addBt; p.include_identity = f.addSelf;
+    return p;
+}
+static plasship_hamming_params hammingParams(const Flags &f) {
+    plasship_hamming_params p = {};
+    p.wrapped = f.wrapped; p.seq_id_thr = f.seqIdThr; p.seq_id_mode = f.seqIdMode; p.cov_mode = f.covMode; p.cov_thr = f.covThr; p.min_aln_len = f.minAlnLen; p.eval_thr = f.evalThr;
     return p;
 }
 static plasship_assemble_params assembleParams(const Flags &f) {
@@ -507,6 +519,25 @@ static int validateRescoreHamming(Call &c) {
     if (c.f.rescoreMode != 0) return unsupported("plass-hip rescorediagonal-hamming: --rescore-mode %d is not this module's (0, the Hamming score, only)\n", c.f.rescoreMode);
     return c.pos.size() == 4 && c.pos[0] != c.pos[1] ? unsupported("plass-hip rescorediagonal-hamming: separate query and target DBs are not part of the GPU path (linclust uses one DB)\n") : 0;
 }
+// clust-greedy (our own name: `clust` stays with the reference): clust's greedy modes, Parameters::GREEDY = 2 and GREEDY_MEM = 3, which both run
+// greedyIncrementalLowMem (Clustering.cpp:42-47).  The module's default is set cover: a call without --cluster-mode is the reference's.
+static int validateClustMode(Call &c) {
+    return c.f.clusterMode != 2 && c.f.clusterMode != 3
+        ? unsupported("plass-hip %s: --cluster-mode %d is not part of the GPU path (2 and 3, the greedy modes, only)\n", c.m->name, c.f.clusterMode) : 0;
+}
+static int validateClustGreedy(Call &c) {
+    if (const int rc = validateClustMode(c)) return rc;
+    if (c.pos.size() != 3) return 0;
+    const int dbtype = probeDbtype(c.pos[1]);     // prefilter DBs (7, 14) and alignment DBs (5)
+    return dbtype >= 0 && dbtype != PLASSHIP_DBTYPE_PREFILTER_RES && dbtype != PLASSHIP_DBTYPE_PREFILTER_REV_RES && dbtype != PLASSHIP_DBTYPE_ALIGNMENT_RES
+        ? unsupported("plass-hip clust-greedy: a result DB of type %d is not part of the GPU path (prefilter and alignment DBs only)\n", dbtype) : 0;
+}
+// linclust-pre: linclust.sh:21-57 from the sequence DB to pre_clust and pref_filter2, one DB as query and target
+static int validateLinclustPre(Call &c) {
+    if (const int rc = validateClustMode(c)) return rc;
+    if (const int rc = validateKmermatcher(c)) return rc;
+    return validateRescoreHamming(c);
+}
 // Requests that are valid for the reference and lie outside the GPU path are all refused in validate(), before the dry-run exit and before anything
 // is read or written (data/nuclassemble.sh:41,145 calls `concatdbs ... --preserve-keys` whenever circular contigs exist; with exit
 // code 1 the wrapper ended the workflow instead of handing the call to the reference, and the dry run reported it as accepted)
@@ -616,14 +647,54 @@ static int runRescoreHamming(Call &c) {           // (query and target are one D
     plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos; const Flags &f = c.f;
     SeqDb db(ctx); Cands cands(ctx), kept(ctx);
     if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out())) || K(plasship_cands_read(ctx, db, db, pos[2].c_str(), cands.out()))) return fail("rescorediagonal-hamming");
-    plasship_hamming_params p = {}; plasship_rescore_stats st = {};
-    p.wrapped = f.wrapped; p.seq_id_thr = f.seqIdThr; p.seq_id_mode = f.seqIdMode; p.cov_mode = f.covMode; p.cov_thr = f.covThr; p.min_aln_len = f.minAlnLen; p.eval_thr = f.evalThr;
+    const plasship_hamming_params p = hammingParams(f); plasship_rescore_stats st = {};
     if (K(plasship_rescore_hamming(ctx, db, db, cands, &p, kept.out(), &st))) {
         // (wrapped scoring on a DB that is not nucleotides is an error of the call, in the reference as well: not a case for the reference binary)
         return fail("rescorediagonal-hamming");
     }
     fprintf(stdout, "scored: %llu kept: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_scored, (unsigned long long) st.n_accepted, st.ms_kernel);
     return KW(plasship_cands_write(ctx, kept, db, pos[3].c_str())) ? fail("rescorediagonal-hamming") : EXIT_SUCCESS;
+}
+static long indexLines(const std::string &db) {       // entries of a DB on disk; -1: no index
+    FILE *fi = fopen((db + ".index").c_str(), "rb"); if (!fi) return -1;
+    long n = 0; char buf[65536]; size_t got;
+    while ((got = fread(buf, 1, sizeof(buf), fi)) > 0) for (size_t i = 0; i < got; i++) n += buf[i] == '\n';
+    fclose(fi);
+    return n;
+}
+static void printClustStats(const plasship_clust_stats &st) {
+    fprintf(stdout, "sequences: %llu edges: %llu clusters: %llu promoted: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_sequences, (unsigned long long) st.n_edges,
+            (unsigned long long) st.n_clusters, (unsigned long long) st.n_promoted, st.ms_kernel);
+}
+static int runClustGreedy(Call &c) {
+    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
+    SeqDb db(ctx); Cands cands(ctx); Alns al(ctx); Clusters cl(ctx); plasship_clust_stats st = {};
+    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out()))) return fail("clust-greedy");
+    size_t n = 0; plasship_seqdb_info(db, &n, nullptr, nullptr, nullptr, nullptr);
+    if (indexLines(pos[1]) != (long) n) { fprintf(stdout, "Sequence db size != result db size\n"); return EXIT_FAILURE; }      // ClusteringAlgorithms.cpp:20-23
+    if (probeDbtype(pos[1]) == PLASSHIP_DBTYPE_ALIGNMENT_RES) {
+        // (lines plasship_alns_read cannot take — fewer than ten columns — are left to the reference: nothing has been written)
+        if (K(plasship_alns_read(ctx, db, pos[1].c_str(), al.out())))
+            return g_lastRc == PLASSHIP_ERR_ARG ? unsupported("plass-hip clust-greedy: %s\n", plasship_last_error()) : fail("clust-greedy");
+        if (K(plasship_clust_greedy_alns(ctx, db, al, cl.out(), &st))) return fail("clust-greedy");
+    } else {
+        if (K(plasship_cands_read(ctx, db, db, pos[1].c_str(), cands.out())) || K(plasship_clust_greedy_cands(ctx, db, cands, cl.out(), &st))) return fail("clust-greedy");
+    }
+    printClustStats(st);
+    return KW(plasship_clusters_write(ctx, cl, db, pos[2].c_str())) ? fail("clust-greedy") : EXIT_SUCCESS;
+}
+static int runLinclustPre(Call &c) {              // kmermatcher -> rescorediagonal (Hamming) -> clust -> createsubdb + filterdb of pref, on handles
+    plasship_ctx *ctx = c.ctx; const Flags &f = c.f;
+    SeqDb db(ctx); Cands pref(ctx), rescored(ctx), filtered(ctx); Clusters cl(ctx);
+    if (K(plasship_seqdb_read(ctx, c.pos[0].c_str(), db.out()))) return fail("linclust-pre");
+    const plasship_kmermatch_params kp = kmermatchParams(f, dbtypeOf(db) == PLASSHIP_DBTYPE_NUCLEOTIDES ? f.scaleNucl : f.scaleAA); plasship_kmermatch_stats ks = {};
+    const plasship_hamming_params hp = hammingParams(f); plasship_rescore_stats rs = {}; plasship_clust_stats st = {};
+    if (K(plasship_kmermatch(ctx, db, &kp, pref.out(), &ks)) || K(plasship_rescore_hamming(ctx, db, db, pref, &hp, rescored.out(), &rs)) ||
+        K(plasship_clust_greedy_cands(ctx, db, rescored, cl.out(), &st)) || K(plasship_cands_filter(ctx, pref, cl, filtered.out()))) return fail("linclust-pre");
+    fprintf(stdout, "candidates: %llu scored: %llu kept: %llu | kernel ms: hamming %.3f\n", (unsigned long long) ks.n_candidates, (unsigned long long) rs.n_scored,
+            (unsigned long long) rs.n_accepted, rs.ms_kernel);
+    printClustStats(st);
+    return KW(plasship_clusters_write(ctx, cl, db, c.pos[1].c_str())) || KW(plasship_cands_write(ctx, filtered, db, c.pos[2].c_str())) ? fail("linclust-pre") : EXIT_SUCCESS;
 }
 static int runAssembleresults(Call &c) {          // assembleresults and nuclassembleresults
     plasship_ctx *ctx = c.ctx; SeqDb db(ctx); Alns al(ctx); SeqDb o(ctx);
@@ -888,6 +959,9 @@ static const Module kModules[] = {
     {"kmermatcher", KMERMATCHER, 2, "kmermatcher <i:sequenceDB> <o:prefDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; }, validateKmermatcher, runKmermatcher},
     {"rescorediagonal", RESCOREDIAGONAL, 4, "rescorediagonal <i:queryDB> <i:targetDB> <i:prefDB> <o:alnDB>", nullptr, validateRescorediagonal, runRescorediagonal},
     {"rescorediagonal-hamming", RESCOREDIAGONAL_HAMMING, 4, "rescorediagonal-hamming <i:queryDB> <i:targetDB> <i:prefDB> <o:prefDB>", nullptr, validateRescoreHamming, runRescoreHamming},
+    // linclust's greedy `clust` and its whole pre-cluster stage, lib/mmseqs/data/workflow/linclust.sh:21-57 (our own names: `clust` and `linclust` stay with the reference)
+    {"clust-greedy", CLUST_GREEDY, 3, "clust-greedy <i:sequenceDB> <i:resultDB> <o:clusterDB>", nullptr, validateClustGreedy, runClustGreedy},
+    {"linclust-pre", LINCLUST_PRE, 3, "linclust-pre <i:sequenceDB> <o:preClusterDB> <o:prefilterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; }, validateLinclustPre, runLinclustPre},
     {"assembleresults", ASSEMBLERESULTS, 3, "assembleresults <i:sequenceDB> <i:alnResult> <o:reprSeqDB>", nullptr, nullptr, runAssembleresults},
     {"nuclassembleresults", NUCLASSEMBLERESULTS, 3, "nuclassembleresults <i:sequenceDB> <i:alnResult> <o:reprSeqDB>", nullptr, nullptr, runAssembleresults},
     {"guidedassembleresults", GUIDEDASSEMBLERESULTS, 5, "guidedassembleresults <i:nuclSequenceDB> <i:aaSequenceDB> <i:nuclAlnResult> <o:nuclAssembly> <o:aaAssembly>", nullptr, nullptr, runGuidedassembleresults},

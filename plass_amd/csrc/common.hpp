@@ -230,6 +230,18 @@ struct plasship_cands {
     uint64_t nNonSelf = 0;
     plasship::DevBuf d_qoff;       // uint64 [nQueries+1]
     plasship::DevBuf d_hits;       // CandHit [nHits], sorted by (query, target order of the reference)
+    // plasship_cands_filter only: h_present[q] == 0: query q has no entry at all (createsubdb removed it), so plasship_cands_write leaves it
+    // out instead of writing an empty entry.  Empty (every other list): every query has an entry.
+    std::vector<uint8_t> h_present;
+};
+
+// greedy clustering (clust.hip): every sequence of the DB with its representative
+struct plasship_clusters {
+    size_t n = 0;                  // == DB size
+    uint64_t nClusters = 0;
+    uint64_t dbGen = 0;            // plasship_seqdb::gen of the DB it was made on
+    plasship::DevBuf d_pairs;      // uint64 [n]: representative id << 32 | member id, ascending (ids are ranks in key order: the keys' order)
+    plasship::DevBuf d_repOf;      // uint32 [n]: the representative's id of every id
 };
 
 struct plasship_alns {

@@ -131,8 +131,16 @@ extern "C" int plasship_cands_write(plasship_ctx *ctx, const plasship_cands *c, 
     std::vector<uint64_t> qoff; std::vector<CandHit> hits;
     rc = fetchCands(ctx, c, qoff, hits); if (rc) return rc;
     std::string err;
-    const bool ok = writeTextDB(db_path, c->reverseCapable ? PLASSHIP_DBTYPE_PREFILTER_REV_RES : PLASSHIP_DBTYPE_PREFILTER_RES, keys->data(), c->nQueries, qoff.data(),
-                                [&](size_t q, std::string &out) {
+    // a list made by plasship_cands_filter holds the entries of some queries only (common.hpp: h_present): those are written, under their keys
+    std::vector<size_t> sel; std::vector<uint32_t> selKeys; std::vector<uint64_t> selPrefix;
+    const bool subset = !c->h_present.empty();
+    if (subset) {
+        selPrefix.push_back(0);
+        for (size_t q = 0; q < c->nQueries; q++) if (c->h_present[q]) { sel.push_back(q); selKeys.push_back((*keys)[q]); selPrefix.push_back(selPrefix.back() + (qoff[q + 1] - qoff[q])); }
+    }
+    const bool ok = writeTextDB(db_path, c->reverseCapable ? PLASSHIP_DBTYPE_PREFILTER_REV_RES : PLASSHIP_DBTYPE_PREFILTER_RES, subset ? selKeys.data() : keys->data(),
+                                subset ? sel.size() : c->nQueries, subset ? selPrefix.data() : qoff.data(), [&](size_t e, std::string &out) {
+        const size_t q = subset ? sel[e] : e;
         for (uint64_t i = qoff[q]; i < qoff[q + 1]; i++) {
             char tmp[64]; char *p = fmtU32((*keys)[hits[i].target], tmp); *p++ = '\t';
             p = fmtI32(hits[i].prefScore, p); *p++ = '\t';
