@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "posterior_class.hpp"
+#include "ref_rules.hpp"
 #include "host_util.hpp"
 #include <algorithm>
 #include <memory>
@@ -83,19 +84,10 @@ __device__ __forceinline__ float seqIdThroughText(float f) {
     return (float) ((double) t / den);
 }
 
-// 8 residues per lane and memory round trip: the loops below are latency bound (a query is a chain of dependent
-// loads), so fewer, wider accesses are what counts.  gfx950 global loads/stores take unaligned addresses; sequence and
-// arena buffers are padded past their ends, bytes beyond the range are masked off.
-__device__ __forceinline__ uint64_t loadU64Unaligned(const char *p) { uint64_t w; __builtin_memcpy(&w, p, 8); return w; }
-__device__ __forceinline__ void storeU64Unaligned(char *p, uint64_t w) { __builtin_memcpy(p, &w, 8); }
-// the last, partial word of a copy: the source word is read whole (the buffers are padded), the destination gets its 1-7 bytes as one
-// 4-, 2- and 1-byte store each — never a byte beyond n (the next sequence of the arena / the output DB belongs to another group).
-// (Byte by byte the tail was up to seven loads and seven stores of the whole wavefront per copy: round 3, profiles/r03_pmc.)
-__device__ __forceinline__ void storeTail(char *d, uint64_t v, unsigned r) {
-    if (r & 4u) { const uint32_t x = (uint32_t) v; __builtin_memcpy(d, &x, 4); d += 4; v >>= 32; }
-    if (r & 2u) { const uint16_t x = (uint16_t) v; __builtin_memcpy(d, &x, 2); d += 2; v >>= 16; }
-    if (r & 1u) *d = (char) v;
-}
+// 8 residues per lane and memory round trip (loadU64Unaligned / storeU64Unaligned / storeTail, device_utils.hpp): the loops below are
+// latency bound (a query is a chain of dependent loads), so fewer, wider accesses are what counts.  Sequence and arena buffers are padded
+// past their ends, bytes beyond the range are masked off; a copy's last word never stores a byte beyond n (the next sequence of the
+// arena / the output DB belongs to another group).
 template <int G> __device__ __forceinline__ void copyBytesG(char *dst, const char *src, unsigned n, int gl) {
     for (unsigned i = 8u * (unsigned) gl; i < n; i += 8u * G) {
         const uint64_t w = loadU64Unaligned(src + i);
@@ -117,7 +109,7 @@ __device__ __forceinline__ uint64_t byteRangeMask(int lo, int hi) {
     return belowHi & ~belowLo;
 }
 // number of zero bytes of x among the bytes selected by mask (exact zero-byte test)
-__device__ __forceinline__ int zeroBytes(uint64_t x, uint64_t mask) {
+__device__ __forceinline__ int zeroBytesMasked(uint64_t x, uint64_t mask) {
     const uint64_t lo7 = 0x7F7F7F7F7F7F7F7FULL;
     return __popcll(~(((x & lo7) + lo7) | x | lo7) & mask);
 }
@@ -137,10 +129,10 @@ template <int G> __device__ __forceinline__ void scoreColumnsG(const char *q, co
         if (p != p0) { qw = loadU64Unaligned(q + p); tw = loadU64Unaligned(t + p); }
         const int lo = (int) first - (int) p, hi = (int) last - (int) p;       // columns [lo, hi] of this word are scored
         uint64_t qv = qw, tv = tw;
-        if (lo <= 0 && hi >= 8) ids += zeroBytes(qw ^ tw, ~0ULL);               // an interior word: all eight columns scored and counted (round 5: the two
+        if (lo <= 0 && hi >= 8) ids += zeroBytesMasked(qw ^ tw, ~0ULL);         // an interior word: all eight columns scored and counted (round 5: the two
         else {                                                                  // range masks cost as much as the eight lookups)
             const uint64_t m = byteRangeMask(lo, hi + 1);
-            ids += zeroBytes(qw ^ tw, byteRangeMask(lo, hi));                   // [qStart, qEnd): the last aligned column is not counted
+            ids += zeroBytesMasked(qw ^ tw, byteRangeMask(lo, hi));             // [qStart, qEnd): the last aligned column is not counted
             qv = qw & m; tv = tw & m;
         }
 #pragma unroll
@@ -167,10 +159,10 @@ __device__ __forceinline__ void scoreColumnsSerial(const char *q, const char *t,
         for (unsigned k = 0; k < 4; k++) {
             const int lo = (int) first - (int) (p + 8 * k), hi = (int) last - (int) (p + 8 * k);
             uint64_t qv = qw[k], tv = tw[k];
-            if (lo <= 0 && hi >= 8) ids += zeroBytes(qw[k] ^ tw[k], ~0ULL);     // an interior word (see scoreColumnsG)
+            if (lo <= 0 && hi >= 8) ids += zeroBytesMasked(qw[k] ^ tw[k], ~0ULL);     // an interior word (see scoreColumnsG)
             else {
                 const uint64_t m = byteRangeMask(lo, hi + 1);
-                ids += zeroBytes(qw[k] ^ tw[k], byteRangeMask(lo, hi));
+                ids += zeroBytesMasked(qw[k] ^ tw[k], byteRangeMask(lo, hi));
                 qv = qw[k] & m; tv = tw[k] & m;
             }
 #pragma unroll
@@ -628,14 +620,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 // within rounding distance of 0.45 / 0.55 (the reference itself depends on the host's libm variant there).
 // One wavefront per query; lane 0 runs the heap, all lanes copy and re-score.
 // =====================================================================================================
-__device__ __forceinline__ char nuclRevN(char c) {          // getNuclRevFragment: num2aa[reverse(aa2num[c])], X -> N
-    switch (c & ~0x20) {
-        case 'A': return 'T';
-        case 'C': case 'M': case 'Y': case 'H': return 'G';
-        case 'T': case 'U': case 'W': return 'A';
-        case 'G': case 'K': case 'B': case 'D': case 'V': case 'R': case 'S': return 'C';
-        default: return 'N';
-    }
+__device__ __forceinline__ char nuclRevN(char c) {          // getNuclRevFragment: num2aa[reverse(aa2num[c])] (nuclComplement), X -> N
+    const unsigned char r = nuclComplement((unsigned char) c);
+    return r == 'X' ? 'N' : (char) r;
 }
 // comparator state of one query: the first decision the table cannot answer aborts the query (it is re-run after
 // the host has evaluated the tuple with its libm)
@@ -1000,7 +987,7 @@ __device__ __forceinline__ void scoreColumnsRevWave(const char *q, const char *t
         const uint64_t qw = loadU64Unaligned(q + p), tc = compWord(loadRevWord(tSeq, tHi - p), sComp);
         const int lo = (int) first - (int) p, hi = (int) last - (int) p;
         const uint64_t m = byteRangeMask(lo, hi + 1);
-        ids += zeroBytes(qw ^ tc, byteRangeMask(lo, hi));
+        ids += zeroBytesMasked(qw ^ tc, byteRangeMask(lo, hi));
         const uint64_t qv = qw & m, tv = tc & m;
 #pragma unroll
         for (unsigned j = 0; j < 8; j++) {

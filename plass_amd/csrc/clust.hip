@@ -173,14 +173,6 @@ __global__ void clustFilterFlagKernel(const CandHit *__restrict__ hits, uint64_t
         if (bad) atomicAdd(&stats[2], (unsigned long long) bad);
     }
 }
-__global__ void clustCompactKernel(const CandHit *__restrict__ in, const uint32_t *__restrict__ keep, const uint64_t *__restrict__ pos, CandHit *__restrict__ out, uint64_t n) {
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x)
-        if (keep[i]) out[pos[i]] = in[i];
-}
-__global__ void clustOffsetsKernel(const uint64_t *__restrict__ inQoff, const uint64_t *__restrict__ pos, uint64_t *__restrict__ outQoff, uint64_t nQ) {
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i <= nQ; i += (uint64_t) gridDim.x * blockDim.x)
-        outQoff[i] = pos[inQoff[i]];
-}
 
 static unsigned gridFor(uint64_t n, const plasship_ctx *ctx) { return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->numCU * 32)); }
 
@@ -365,15 +357,13 @@ extern "C" int plasship_cands_filter(plasship_ctx *ctx, const plasship_cands *c,
     if (c->nQueries != cl->n) { setError(std::string(what) + ": the candidate list and the clustering belong to DBs of different sizes"); return PLASSHIP_ERR_ARG; }
     PH_ENTER(ctx);
     const uint64_t nHits = c->nHits; const size_t nQ = c->nQueries;
-    DevBuf dKeep, dPos, dTmp, dStats;
-    const size_t tmpBytes = exclusiveScanTmpBytes(nHits);
-    if (dKeep.alloc(std::max<uint64_t>(nHits, 1) * 4) != hipSuccess || dPos.alloc((nHits + 1) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess || dStats.alloc(32) != hipSuccess) {
+    DevBuf dKeep, dStats;
+    if (dKeep.alloc(std::max<uint64_t>(nHits, 1) * 4) != hipSuccess || dStats.alloc(32) != hipSuccess) {
         setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE;
     }
     PH_CHECK(hipMemsetAsync(dStats.p, 0, 32, ctx->stream));
     if (nHits) hipLaunchKernelGGL(clustFilterFlagKernel, dim3(gridFor(nHits, ctx)), dim3(256), 0, ctx->stream, c->d_hits.as<CandHit>(), nHits, cl->d_repOf.as<uint32_t>(), (uint32_t) cl->n,
                                   dKeep.as<uint32_t>(), dStats.as<unsigned long long>());
-    if (exclusiveScanU32(ctx->stream, dKeep.as<uint32_t>(), dPos.as<uint64_t>(), nHits, dTmp.p, tmpBytes)) { (void) plasship::streamSync(ctx->stream); setError("scan failed"); return PLASSHIP_ERR_DEVICE; }
     unsigned long long hs[4] = {0, 0, 0, 0};
     PH_CHECK(hipMemcpyAsync(hs, dStats.p, 32, hipMemcpyDeviceToHost, ctx->stream));
     PH_CHECK(plasship::streamSync(ctx->stream));
@@ -382,17 +372,9 @@ extern "C" int plasship_cands_filter(plasship_ctx *ctx, const plasship_cands *c,
     std::unique_ptr<plasship_cands> holder(new plasship_cands());     // released to the caller on success only
     plasship_cands *o = holder.get();
     o->reverseCapable = c->reverseCapable; o->nQueries = nQ; o->nHits = hs[0]; o->nNonSelf = hs[1];
-    if (o->d_qoff.alloc((nQ + 1) * 8) != hipSuccess || o->d_hits.alloc(std::max<uint64_t>(hs[0], 1) * sizeof(CandHit)) != hipSuccess) {
-        setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE;
-    }
-    if (nHits) hipLaunchKernelGGL(clustCompactKernel, dim3(gridFor(nHits, ctx)), dim3(256), 0, ctx->stream, c->d_hits.as<CandHit>(), dKeep.as<uint32_t>(), dPos.as<uint64_t>(),
-                                  o->d_hits.as<CandHit>(), nHits);
-    hipLaunchKernelGGL(clustOffsetsKernel, dim3((unsigned) std::min<uint64_t>((nQ + 256) / 256, 65535)), dim3(256), 0, ctx->stream, c->d_qoff.as<uint64_t>(), dPos.as<uint64_t>(),
-                       o->d_qoff.as<uint64_t>(), (uint64_t) nQ);
+    if (const int rc = compactCsr(ctx, what, c->d_qoff.as<uint64_t>(), nQ, c->d_hits.p, sizeof(CandHit), dKeep.as<uint32_t>(), nHits, hs[0], o->d_qoff, o->d_hits)) return rc;
     // the entries that are left: the representatives' (createsubdb --subdb-mode 1 with pre_clust's keys); plasship_cands_write writes these only
     std::vector<uint32_t> repOf(nQ);
-    PH_CHECK(plasship::streamSync(ctx->stream));          // (the local buffers above are released with the function: their kernels must be through)
-    PH_CHECK(hipGetLastError());
     if (nQ) { const int rc = stagedCopyToHost(ctx, repOf.data(), cl->d_repOf.p, nQ * 4); if (rc) return rc; }
     o->h_present.resize(nQ);
     for (size_t q = 0; q < nQ; q++) o->h_present[q] = repOf[q] == q ? 1 : 0;

@@ -325,6 +325,12 @@ int stagedCopyToDevice(plasship_ctx *ctx, void *dDst, const void *hSrc, uint64_t
 int stagedCopyToHost(plasship_ctx *ctx, void *hDst, const void *dSrc, uint64_t bytes);
 // sets *differ when two key arrays (device, n entries) are not identical
 int deviceKeysDiffer(plasship_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t n, bool *differ);
+// The flagged records of a CSR list (scan.hip): outRecs = the records with dKeep[i] != 0, in input order; outQoff[q] = the number of kept
+// records before dInQoff[q], q in [0, nQ].  recBytes is 16 (CandHit) or 64 (AlnRec).  nKept is what the caller counted: it sizes outRecs
+// (max(nKept, 1) records) and is checked against the scan's total.  Waits for the stream exactly once, at its end (on an
+// error too); dKeep may go after it.  what: the public call or list the error texts name.
+int compactCsr(plasship_ctx *ctx, const char *what, const uint64_t *dInQoff, uint64_t nQ, const void *dRecs, size_t recBytes, const uint32_t *dKeep,
+               uint64_t nRecs, uint64_t nKept, DevBuf &outQoff, DevBuf &outRecs);
 // dense (hole-free) copy of an alignment list's CSR and records on the device (rescore.hip); for a list that is not sparse the buffers
 // stay empty and *qoff / *recs point at the list's own arrays
 int denseAlnsCopy(plasship_ctx *ctx, const plasship_alns *a, DevBuf &qoffBuf, DevBuf &recsBuf, const uint64_t **qoff, const AlnRec **recs);

@@ -17,13 +17,6 @@
 
 namespace plasship {
 
-__device__ __forceinline__ uint64_t loadU64U(const char *p) { uint64_t w; __builtin_memcpy(&w, p, 8); return w; }
-__device__ __forceinline__ void storeU64U(char *p, uint64_t w) { __builtin_memcpy(p, &w, 8); }
-__device__ __forceinline__ void storeTailU(char *d, uint64_t v, unsigned r) {      // the 1-7 bytes of a last word, never one beyond
-    if (r & 4u) { const uint32_t x = (uint32_t) v; __builtin_memcpy(d, &x, 4); d += 4; v >>= 32; }
-    if (r & 2u) { const uint16_t x = (uint16_t) v; __builtin_memcpy(d, &x, 2); d += 2; v >>= 16; }
-    if (r & 1u) *d = (char) v;
-}
 // position of `k` in the ascending array keys[0, n), or -1
 __device__ __forceinline__ int64_t findKey(const uint32_t *__restrict__ keys, uint32_t n, uint32_t k) {
     uint32_t lo = 0, hi = n;
@@ -102,7 +95,7 @@ __global__ __launch_bounds__(256) void selWaveKernel(SelArgs a) {
         const char *p = a.r.data + a.r.off[k] + 1;
         const uint32_t m = L - 2;                      // the middle: bytes 1 .. L-2
         bool ok = true;
-        for (uint32_t j = 8u * (uint32_t) lane; j < m; j += 512u) ok &= upperWord(loadU64U(p + j), min(8u, m - j));   // (buffers are padded past their ends)
+        for (uint32_t j = 8u * (uint32_t) lane; j < m; j += 512u) ok &= upperWord(loadU64Unaligned(p + j), min(8u, m - j));   // (buffers are padded past their ends)
         const bool all = __ballot(!ok) == 0ull;
         if (lane == 0 && all) { a.flags[i] |= SEL_S2; a.keep[i] = 1u; }
     }
@@ -196,8 +189,8 @@ __global__ __launch_bounds__(256) void fastaWriteKernel(const char *data, const 
             const uint64_t cs = (uint64_t) __shfl((unsigned long long) src, s, 64), cd = (uint64_t) __shfl((unsigned long long) dst, s, 64);
             const char *from = data + cs; char *to = out + cd;
             for (uint32_t q = 8u * (uint32_t) lane; q < cl; q += 512u) {
-                const uint64_t x = loadU64U(from + q);                         // (sequence buffers are padded past their ends)
-                if (q + 8 <= cl) storeU64U(to + q, x); else storeTailU(to + q, x, cl - q);
+                const uint64_t x = loadU64Unaligned(from + q);                         // (sequence buffers are padded past their ends)
+                if (q + 8 <= cl) storeU64Unaligned(to + q, x); else storeTail(to + q, x, cl - q);
             }
         }
     }

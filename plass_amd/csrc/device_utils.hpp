@@ -86,6 +86,17 @@ __device__ __forceinline__ unsigned long long waveInclusiveScanU64(unsigned long
     return v;
 }
 
+// ---- 8 bytes at any address (gfx950 global loads / stores take unaligned addresses) ----
+__device__ __forceinline__ uint64_t loadU64Unaligned(const char *p) { uint64_t w; __builtin_memcpy(&w, p, 8); return w; }
+__device__ __forceinline__ void storeU64Unaligned(char *p, uint64_t w) { __builtin_memcpy(p, &w, 8); }
+// the last, partial word of a copy: the low r = 1-7 bytes of v as one 4-, 2- and 1-byte store each, never a byte beyond d + r
+// (byte by byte the tail was up to seven stores of the whole wavefront per copy: round 3, profiles/r03_pmc)
+__device__ __forceinline__ void storeTail(char *d, uint64_t v, unsigned r) {
+    if (r & 4u) { const uint32_t x = (uint32_t) v; __builtin_memcpy(d, &x, 4); d += 4; v >>= 32; }
+    if (r & 2u) { const uint16_t x = (uint16_t) v; __builtin_memcpy(d, &x, 2); d += 2; v >>= 16; }
+    if (r & 1u) *d = (char) v;
+}
+
 // ---- device-wide exclusive scan of uint32 counts into uint64 offsets ------------------------------
 // out[i] = sum_{j<i} in[j], out[n] = total.  Three-kernel scheme (reduce / scan partials / downsweep);
 // the partial array is scanned recursively.  Traffic 12 B/element read + 8 B written: negligible next

@@ -1,5 +1,5 @@
 // plasship: kmermatcher on gfx950, stage K5: assignGroup over hash buckets.  Product code; part of kmermatch.hip's translation unit (included there, inside
-// namespace plasship, after common.hpp / device_utils.hpp / linepart.hpp) — split out by stage in round 4, see kmermatch.hip for the
+// namespace plasship, after common.hpp / device_utils.hpp / linepart.hpp / ref_rules.hpp) — split out by stage in round 4, see kmermatch.hip for the
 // reference lines the stage reproduces and DESIGN.md section 4 for the kernels' bounds.
 // Kernels: groupKernel (24-byte records, sharded run), groupLinesKernel (16-byte records over the line store).
 #pragma once
@@ -21,18 +21,6 @@ struct GroupArgs {
     const unsigned long long *minKey;   // NUCL: K of the globally first run
     unsigned long long *maxRepTarget;   // max over emitted records of (rep << 32 | member): the last run of sort #2
 };
-
-__device__ __forceinline__ bool canBeCoveredK(float covThr, int covMode, float q, float t) {   // Util.cpp:533-550
-    switch (covMode) {
-        case 0: return (q / t >= covThr) && (t / q >= covThr);
-        case 1: return (q / t) >= covThr;     // COV_MODE_TARGET = 1, COV_MODE_QUERY = 2 (mm/commons/Parameters.h:246-251)
-        case 2: return (t / q) >= covThr;
-        case 3: return ((t / q) >= covThr) && (t / q) <= 1.0f;
-        case 4: return ((q / t) >= covThr) && (q / t) <= 1.0f;
-        case 5: return (fminf(t, q) / fmaxf(t, q)) >= covThr;
-        default: return true;
-    }
-}
 
 // Nucleotide strand ties of sort #2 (kmermatcher.h:98-130 compares rep, target and diagonal only; kmermatcher.cpp:866-893 reports the
 // strand of the LAST record of the best diagonal's run): the reference's ips4o leaves the records of one (rep, target, diagonal) triple
@@ -153,7 +141,7 @@ __global__ __launch_bounds__(GR_BLOCK) void groupKernel(GroupArgs a) {
                                     rId = qRev ? (rId & ~BIT63) : (rId | BIT63);
                                 }
                                 const bool canBeExtended = diagonal < 0 || (diagonal > (queryLen - mLen));
-                                const bool cov = canBeCoveredK(a.covThr, a.covMode, (float) queryLen, (float) mLen);
+                                const bool cov = canBeCovered(a.covThr, a.covMode, (float) queryLen, (float) mLen);
                                 keep = (!a.includeOnlyExtendable && cov) || (canBeExtended && a.includeOnlyExtendable);
                                 o.kmer = rId; o.id = r.id; o.len = r.len; o.pos = (decltype(o.pos)) diagonal;
                                 if (NUCL) embedOrd(o, r.kmer);
@@ -313,7 +301,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, WPE)
                             rId = qRev ? (rId & ~BIT63) : (rId | BIT63);
                         }
                         const bool canBeExtended = diagonal < 0 || (diagonal > (queryLen - mLen));
-                        const bool cov = canBeCoveredK(a.covThr, a.covMode, (float) queryLen, (float) mLen);
+                        const bool cov = canBeCovered(a.covThr, a.covMode, (float) queryLen, (float) mLen);
                         keep = (!a.includeOnlyExtendable && cov) || (canBeExtended && a.includeOnlyExtendable);
                         o.kmer = rId; o.id = r.id; o.len = r.len; o.pos = (int16_t) diagonal;
                         if (NUCL) embedOrd(o, r.kmer);

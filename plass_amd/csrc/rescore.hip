@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "host_util.hpp"
+#include "ref_rules.hpp"
 #include <algorithm>
 #include <memory>
 #include <cfloat>
@@ -50,40 +51,6 @@ struct RescoreArgs {
     int mode, lazySelf;
     const uint32_t *queryList; uint32_t nQueryList;
 };
-
-__device__ __forceinline__ bool canBeCoveredDev(float covThr, int covMode, float q, float t) {   // Util.cpp:533-550
-    switch (covMode) {
-        case 0: return (q / t >= covThr) && (t / q >= covThr);
-        case 1: return (q / t) >= covThr;     // COV_MODE_TARGET = 1, COV_MODE_QUERY = 2 (mm/commons/Parameters.h:246-251)
-        case 2: return (t / q) >= covThr;
-        case 3: return ((t / q) >= covThr) && (t / q) <= 1.0f;
-        case 4: return ((q / t) >= covThr) && (q / t) <= 1.0f;
-        case 5: return (fminf(t, q) / fmaxf(t, q)) >= covThr;
-        default: return true;
-    }
-}
-__device__ __forceinline__ bool hasCoverageDev(float covThr, int covMode, float qc, float tc) {  // Util.cpp:552-568
-    switch (covMode) {
-        case 0: return (qc >= covThr) && (tc >= covThr);
-        case 1: return tc >= covThr;
-        case 2: return qc >= covThr;
-        default: return true;
-    }
-}
-__device__ __forceinline__ float computeCovDev(unsigned s, unsigned e, unsigned len) {            // StripedSmithWaterman.cpp:1055-1057
-    return (float) (min(len, max(s, e)) - min(s, e) + 1) / (float) len;
-}
-// complement of an ASCII nucleotide exactly as rescorediagonal.cpp:175-178 builds the reverse query:
-// num2aa[reverse(aa2num[c])] with aa2num = NucleotideMatrix letter mapping (NucleotideMatrix.cpp:17-61)
-__device__ __forceinline__ char nuclRevCompChar(char c) {
-    switch (c & ~0x20) {
-        case 'A': return 'T';
-        case 'C': case 'M': case 'Y': case 'H': return 'G';
-        case 'T': case 'U': case 'W': return 'A';
-        case 'G': case 'K': case 'B': case 'D': case 'V': case 'R': case 'S': return 'C';
-        default: return 'X';
-    }
-}
 
 constexpr int RS_BLOCK = 256;
 // lanes per candidate pair: G = 1 (one thread per pair: short read overlaps, ~6 wave-instructions per pair)
@@ -230,7 +197,7 @@ __global__ __launch_bounds__(RS_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, W
     __shared__ signed char smat[123 * 128];              // row stride 128: the index of a column is (a << 7) | b
     __shared__ unsigned char sComp[256];                 // reverse-strand hits: complement of a stored letter (getRevFragment's mapping)
     for (int i = threadIdx.x; i < 123 * 128; i += RS_BLOCK) smat[i] = (i & 127) < 123 ? a.mat[(i >> 7) * 123 + (i & 127)] : (signed char) 0;
-    for (int i = threadIdx.x; i < 256; i += RS_BLOCK) sComp[i] = i ? (unsigned char) nuclRevCompChar((char) i) : (unsigned char) 0;
+    for (int i = threadIdx.x; i < 256; i += RS_BLOCK) sComp[i] = i ? nuclComplement((unsigned char) i) : (unsigned char) 0;
     __syncthreads();
     if (threadIdx.x == 0) smat[0] = 0;      // blanked columns (scoreDiagonal) look up [0][0]; no residue is byte 0
     __syncthreads();
@@ -308,7 +275,7 @@ __global__ __launch_bounds__(RS_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, W
         AlnRec rec; memset(&rec, 0, sizeof(rec));
         rec.query = qid; rec.target = tid;
         bool accepted = false;
-        if (canBeCoveredDev(a.covThr, a.covMode, (float) qLen, (float) tLen)) {
+        if (canBeCovered(a.covThr, a.covMode, (float) qLen, (float) tLen)) {
             // computeUngappedAlignment: best over all wraps (first the negative ones, then the positive ones; strictly better wins);
             // default LocalAlignment if none scores > 0.  A wrap whose diagonal misses the sequences scores 0 and is skipped.
             int bStart = -1, bEnd = -1, bDiag = 0, bIds = 0; unsigned bScore = 0, bDiagLen = 0, bDist = 0;
@@ -345,18 +312,11 @@ __global__ __launch_bounds__(RS_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, W
             int idCnt = bIds;
             if (bStart < 0) idCnt = isIdentity ? 1 : 0;
             float seqId = 0.0f;
-            if (hasEvalue || isIdentity) {
-                switch (a.seqIdMode) {                                                     // Util.cpp:588-598
-                    case 0: seqId = (float) idCnt / (float) alnLen; break;
-                    case 1: seqId = (float) idCnt / (float) min((int) qLen, (int) tLen); break;
-                    case 2: seqId = (float) idCnt / (float) max((int) qLen, (int) tLen); break;
-                    default: seqId = 0.0f;
-                }
-            }
-            const float queryCov = computeCovDev((unsigned) qS, (unsigned) qE, qLen);
-            const float targetCov = computeCovDev((unsigned) dS, (unsigned) dE, tLen);
+            if (hasEvalue || isIdentity) seqId = computeSeqId(a.seqIdMode, idCnt, (int) qLen, (int) tLen, alnLen);
+            const float queryCov = computeCov((unsigned) qS, (unsigned) qE, qLen);
+            const float targetCov = computeCov((unsigned) dS, (unsigned) dE, tLen);
             if (isReverse) { qS = (int) qLen - qS - 1; qE = (int) qLen - qE - 1; }
-            const bool hasCov = hasCoverageDev(a.covThr, a.covMode, queryCov, targetCov);
+            const bool hasCov = hasCoverage(a.covThr, a.covMode, queryCov, targetCov);
             const bool hasSeqId = (double) seqId >= (double) (a.seqIdThr - FLT_EPSILON);
             const bool hasAlnLen = alnLen >= a.alnLenThr;
             accepted = isIdentity || (hasAlnLen && hasCov && hasSeqId && hasEvalue);
@@ -384,23 +344,9 @@ __global__ __launch_bounds__(RS_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, W
 //  lock-step kernel.  The time grows linearly with the number of refill events per 64 pairs (~2.4 ms each) while the stepping part does not
 //  shrink with the fuller lanes: the kernel is bound by the round trips a pair consists of, not by vector issue — a refill exposes one per
 //  event for T pairs where the lock-step kernel exposes one per 64 — and the lanes-per-instruction figure does not measure that.  Removed.)
-// dense copy of a sparse list (host paths only since round 5): four lanes per 64-byte record, 16 bytes each, both sides coalesced
+// dense copy of a sparse list (host paths only since round 5): the accepted records' flags for compactCsr
 __global__ void acceptFlagsKernel(const AlnRec *__restrict__ recs, uint32_t *__restrict__ accept, uint64_t n) {
     for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) accept[i] = recs[i].accepted ? 1u : 0u;
-}
-__global__ void compactAlnKernel(const uint4 *__restrict__ in, const uint32_t *__restrict__ accept,
-                                 const uint64_t *__restrict__ pos, uint4 *__restrict__ out, uint64_t n) {
-    static_assert(sizeof(AlnRec) == 64, "four 16-byte pieces per record");
-    const uint64_t total = n * 4;
-    for (uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t) gridDim.x * blockDim.x) {
-        const uint64_t i = t >> 2;
-        if (accept[i]) out[pos[i] * 4 + (t & 3)] = in[t];
-    }
-}
-__global__ void gatherOffsetsKernel(const uint64_t *__restrict__ candQoff, const uint64_t *__restrict__ pos,
-                                    uint64_t *__restrict__ alnQoff, uint64_t nQ) {
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i <= nQ; i += (uint64_t) gridDim.x * blockDim.x)
-        alnQoff[i] = pos[candQoff[i]];
 }
 __global__ void markLengthsKernel(const uint32_t *__restrict__ len, uint32_t n, uint32_t *__restrict__ present, uint32_t cap) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -414,21 +360,11 @@ int denseAlnsCopy(plasship_ctx *ctx, const plasship_alns *a, DevBuf &qoffBuf, De
     *qoff = a->d_qoff.as<uint64_t>(); *recs = a->d_recs.as<AlnRec>();
     if (!a->sparse) return PLASSHIP_OK;
     const uint64_t n = a->nSlots;
-    DevBuf dAccept, dPos, dTmp;
-    const size_t tmpBytes = exclusiveScanTmpBytes(n);
-    if (dAccept.alloc(std::max<uint64_t>(n, 1) * 4) != hipSuccess || dPos.alloc((n + 1) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess ||
-        qoffBuf.alloc((a->nQueries + 1) * 8) != hipSuccess || recsBuf.alloc(std::max<uint64_t>(a->nLines, 1) * sizeof(AlnRec)) != hipSuccess) {
-        setError("alignment list: out of device memory for the dense copy"); return PLASSHIP_ERR_DEVICE;
-    }
+    DevBuf dAccept;
+    if (dAccept.alloc(std::max<uint64_t>(n, 1) * 4) != hipSuccess) { setError("alignment list: out of device memory for the dense copy"); return PLASSHIP_ERR_DEVICE; }
     if (n) hipLaunchKernelGGL(acceptFlagsKernel, dim3((unsigned) std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->numCU * 32)), dim3(256), 0, ctx->stream, a->d_recs.as<AlnRec>(), dAccept.as<uint32_t>(), n);
-    if (exclusiveScanU32(ctx->stream, dAccept.as<uint32_t>(), dPos.as<uint64_t>(), n, dTmp.p, tmpBytes)) { (void) plasship::streamSync(ctx->stream); setError("scan failed"); return PLASSHIP_ERR_DEVICE; }   // (the local buffers go with the function: their kernel must be through)
-    if (n) hipLaunchKernelGGL(compactAlnKernel, dim3((unsigned) std::min<uint64_t>((4 * n + 255) / 256, (uint64_t) ctx->numCU * 64)), dim3(256), 0, ctx->stream,
-                              a->d_recs.as<uint4>(), dAccept.as<uint32_t>(), dPos.as<uint64_t>(), recsBuf.as<uint4>(), n);
-    hipLaunchKernelGGL(gatherOffsetsKernel, dim3((unsigned) std::min<uint64_t>((a->nQueries + 256) / 256, 65535)), dim3(256), 0, ctx->stream,
-                       a->d_qoff.as<uint64_t>(), dPos.as<uint64_t>(), qoffBuf.as<uint64_t>(), (uint64_t) a->nQueries);
-    uint64_t nAcc = 0;
-    PH_COPY_SYNC(ctx->stream, &nAcc, dPos.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost);
-    if (nAcc != a->nLines) { setError("alignment list: the accepted records do not add up to the list's count"); return PLASSHIP_ERR_DEVICE; }
+    const int rc = compactCsr(ctx, "alignment list: the dense copy", a->d_qoff.as<uint64_t>(), a->nQueries, a->d_recs.p, sizeof(AlnRec), dAccept.as<uint32_t>(), n, a->nLines, qoffBuf, recsBuf);
+    if (rc) return rc;
     *qoff = qoffBuf.as<uint64_t>(); *recs = recsBuf.as<AlnRec>();
     return PLASSHIP_OK;
 }

@@ -7,7 +7,7 @@
 //   alignment/DistanceCalculator.h:57-91    computeUngappedWrappedAlignment: both alias loops in unsigned arithmetic, diagonalLen
 //   alignment/DistanceCalculator.h:93-175   computeUngappedAlignment / ungappedAlignmentByDiagonal: the walk without wrapping
 //   alignment/DistanceCalculator.h:276-295  computeInverseHammingDistance: the number of EQUAL bytes, case-sensitive
-//   commons/NucleotideMatrix.cpp:4-61       aa2num -> reverseResidue -> num2aa: the reverse strand's letters (nuclRevComp below)
+//   commons/NucleotideMatrix.cpp:4-61       aa2num -> reverseResidue -> num2aa: the reverse strand's letters (nuclComplement, ref_rules.hpp)
 //   prefiltering/QueryMatcher.h:114-126     the diagonal is written as a signed short
 //
 // Kernel design: ONE WAVEFRONT per candidate pair; a lane compares 16 residues per step (two unaligned 16-byte loads, one zero-byte test per
@@ -20,6 +20,7 @@
 // Algorithmic bytes per candidate: 12 (candidate) + 2 * diagonalLen * (aliases tried) + 12 (line written); see DESIGN.md.
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "ref_rules.hpp"
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -41,37 +42,6 @@ struct HammingArgs {
     unsigned long long *stats;   // [0] lines kept, [1] residues compared, [2] kept lines that are not an implicit self line, [3] ids out of range
 };
 
-__device__ __forceinline__ bool hammingCanBeCovered(float covThr, int covMode, float q, float t) {   // Util.cpp:533-550
-    switch (covMode) {
-        case 0: return (q / t >= covThr) && (t / q >= covThr);
-        case 1: return (q / t) >= covThr;     // COV_MODE_TARGET = 1, COV_MODE_QUERY = 2 (commons/Parameters.h:246-251)
-        case 2: return (t / q) >= covThr;
-        case 3: return ((t / q) >= covThr) && (t / q) <= 1.0f;
-        case 4: return ((q / t) >= covThr) && (q / t) <= 1.0f;
-        case 5: return (fminf(t, q) / fmaxf(t, q)) >= covThr;
-        default: return true;
-    }
-}
-__device__ __forceinline__ bool hammingHasCoverage(float covThr, int covMode, float qc, float tc) {  // Util.cpp:552-568
-    switch (covMode) {
-        case 0: return (qc >= covThr) && (tc >= covThr);
-        case 1: return tc >= covThr;
-        case 2: return qc >= covThr;
-        default: return true;
-    }
-}
-// num2aa[reverseResidue(aa2num[c])] (rescorediagonal.cpp:175-178): setupLetterMapping folds the case and the IUPAC codes onto A, C, G, T,
-// everything else onto X; the letter that comes back is always upper case
-__device__ __forceinline__ unsigned char nuclRevComp(unsigned c) {
-    if (c >= 'a' && c <= 'z') c -= 0x20;          // toupper in the C locale
-    switch (c) {
-        case 'A': return 'T';
-        case 'C': case 'M': case 'Y': case 'H': return 'G';
-        case 'T': case 'U': case 'W': return 'A';
-        case 'G': case 'K': case 'B': case 'D': case 'V': case 'R': case 'S': return 'C';
-        default: return 'X';
-    }
-}
 __device__ __forceinline__ int zeroBytes(uint32_t x) {      // exact: bit 7 of a byte of the mask is set iff the byte of x is 0
     return __popc(~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu));
 }
@@ -113,7 +83,7 @@ constexpr int HM_BLOCK = 256;
 
 __global__ __launch_bounds__(HM_BLOCK) void hammingKernel(HammingArgs a) {
     __shared__ unsigned char sComp[256];
-    for (int i = threadIdx.x; i < 256; i += HM_BLOCK) sComp[i] = nuclRevComp((unsigned) i);
+    for (int i = threadIdx.x; i < 256; i += HM_BLOCK) sComp[i] = nuclComplement((unsigned char) i);
     __syncthreads();
     const unsigned lane = (unsigned) laneId();
     const uint64_t wavesPerBlock = HM_BLOCK / WAVE;
@@ -132,7 +102,7 @@ __global__ __launch_bounds__(HM_BLOCK) void hammingKernel(HammingArgs a) {
         bool kept = false;
         int32_t outScore = 0; unsigned outDiag = 0;
         // (an empty target: the reference's first wrapped loop does not end, its division by dbLen is 0 / 0 — no line is written here)
-        if (dbLen > 0 && L > 0 && hammingCanBeCovered(a.covThr, a.covMode, (float) L, (float) dbLen) && !(a.wrapped && dbLen > L)) {
+        if (dbLen > 0 && L > 0 && canBeCovered(a.covThr, a.covMode, (float) L, (float) dbLen) && !(a.wrapped && dbLen > L)) {
             unsigned best = 0, diagLen = 0; int bestDiag = 0;
             // one alias: the equal bytes of two ranges of the (possibly reversed, possibly doubled) query against the target
             //   forward: query [q0, q0 + n0) against t [t0, ..), then query [0, n1) against t [t0 + n0, ..)
@@ -175,14 +145,8 @@ __global__ __launch_bounds__(HM_BLOCK) void hammingKernel(HammingArgs a) {
             // rescorediagonal.cpp:239-246,304-332
             const float targetCov = (float) diagLen / (float) dbLen, queryCov = (float) diagLen / (float) L;
             const int idCnt = (int) (float) best;
-            float seqId;
-            switch (a.seqIdMode) {                                                     // Util.cpp:588-598
-                case 0: seqId = (float) idCnt / (float) (int) diagLen; break;          // (0 / 0 = NaN when no alias scored)
-                case 1: seqId = (float) idCnt / (float) min((int) L, (int) dbLen); break;
-                case 2: seqId = (float) idCnt / (float) max((int) L, (int) dbLen); break;
-                default: seqId = 0.0f;
-            }
-            const bool hasCov = hammingHasCoverage(a.covThr, a.covMode, queryCov, targetCov);
+            const float seqId = computeSeqId(a.seqIdMode, idCnt, (int) L, (int) dbLen, (int) diagLen);      // (0 / 0 = NaN when no alias scored)
+            const bool hasCov = hasCoverage(a.covThr, a.covMode, queryCov, targetCov);
             const bool hasSeqId = (double) seqId >= (double) (a.seqIdThr - FLT_EPSILON);
             const bool hasAlnLen = (int) diagLen >= a.alnLenThr;
             kept = isIdentity || (hasAlnLen && hasCov && hasSeqId && a.hasEvalue);
@@ -207,17 +171,6 @@ __global__ __launch_bounds__(HM_BLOCK) void hammingKernel(HammingArgs a) {
     }
 }
 
-// the kept lines in input order, and the CSR over them
-__global__ void hammingCompactKernel(const CandHit *__restrict__ in, const uint32_t *__restrict__ keep, const uint64_t *__restrict__ pos,
-                                     CandHit *__restrict__ out, uint64_t n) {
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x)
-        if (keep[i]) out[pos[i]] = in[i];
-}
-__global__ void hammingOffsetsKernel(const uint64_t *__restrict__ candQoff, const uint64_t *__restrict__ pos, uint64_t *__restrict__ outQoff, uint64_t nQ) {
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i <= nQ; i += (uint64_t) gridDim.x * blockDim.x)
-        outQoff[i] = pos[candQoff[i]];
-}
-
 }  // namespace plasship
 using namespace plasship;
 
@@ -233,10 +186,9 @@ extern "C" int plasship_rescore_hamming(plasship_ctx *ctx, const plasship_seqdb 
     PH_ENTER(ctx);
     const uint64_t nHits = c->nHits;
     const size_t nQ = qdb->n;
-    DevBuf dKeep, dLines, dPos, dTmp, dStats;
-    const size_t tmpBytes = exclusiveScanTmpBytes(nHits);
+    DevBuf dKeep, dLines, dStats;
     if (dKeep.alloc(std::max<uint64_t>(nHits, 1) * 4) != hipSuccess || dLines.alloc(std::max<uint64_t>(nHits, 1) * sizeof(CandHit)) != hipSuccess ||
-        dPos.alloc((nHits + 1) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess || dStats.alloc(32) != hipSuccess) {
+        dStats.alloc(32) != hipSuccess) {
         setError("plasship_rescore_hamming: out of device memory"); return PLASSHIP_ERR_DEVICE;
     }
     PH_CHECK(hipMemsetAsync(dStats.p, 0, 32, ctx->stream));
@@ -253,7 +205,6 @@ extern "C" int plasship_rescore_hamming(plasship_ctx *ctx, const plasship_seqdb 
         hipLaunchKernelGGL(hammingKernel, dim3(grid), dim3(HM_BLOCK), 0, ctx->stream, a);
     }
     PH_CHECK(hipEventRecord(ctx->ev[1], ctx->stream));
-    if (exclusiveScanU32(ctx->stream, dKeep.as<uint32_t>(), dPos.as<uint64_t>(), nHits, dTmp.p, tmpBytes)) { (void) plasship::streamSync(ctx->stream); setError("scan failed"); return PLASSHIP_ERR_DEVICE; }
     unsigned long long hs[4] = {0, 0, 0, 0};
     PH_CHECK(hipMemcpyAsync(hs, dStats.p, 32, hipMemcpyDeviceToHost, ctx->stream));
     PH_CHECK(plasship::streamSync(ctx->stream));
@@ -263,15 +214,8 @@ extern "C" int plasship_rescore_hamming(plasship_ctx *ctx, const plasship_seqdb 
     std::unique_ptr<plasship_cands> holder(new plasship_cands());     // released to the caller on success only
     plasship_cands *o = holder.get();
     o->reverseCapable = c->reverseCapable; o->nQueries = nQ; o->nHits = nKept; o->nNonSelf = hs[2];
-    if (o->d_qoff.alloc((nQ + 1) * 8) != hipSuccess || o->d_hits.alloc(std::max<uint64_t>(nKept, 1) * sizeof(CandHit)) != hipSuccess) {
-        setError("plasship_rescore_hamming: out of device memory"); return PLASSHIP_ERR_DEVICE;
-    }
-    if (nHits) hipLaunchKernelGGL(hammingCompactKernel, dim3((unsigned) std::min<uint64_t>((nHits + 255) / 256, (uint64_t) ctx->numCU * 32)), dim3(256), 0, ctx->stream,
-                                  dLines.as<CandHit>(), dKeep.as<uint32_t>(), dPos.as<uint64_t>(), o->d_hits.as<CandHit>(), nHits);
-    hipLaunchKernelGGL(hammingOffsetsKernel, dim3((unsigned) std::min<uint64_t>((nQ + 256) / 256, 65535)), dim3(256), 0, ctx->stream,
-                       c->d_qoff.as<uint64_t>(), dPos.as<uint64_t>(), o->d_qoff.as<uint64_t>(), (uint64_t) nQ);
-    PH_CHECK(plasship::streamSync(ctx->stream));          // (the local buffers above are released with the function: their kernels must be through)
-    PH_CHECK(hipGetLastError());
+    // the kept lines in input order, and the CSR over them
+    if (const int rc = compactCsr(ctx, "plasship_rescore_hamming", c->d_qoff.as<uint64_t>(), nQ, dLines.p, sizeof(CandHit), dKeep.as<uint32_t>(), nHits, nKept, o->d_qoff, o->d_hits)) return rc;
     if (stats) {
         stats->n_scored = nHits; stats->n_accepted = nKept; stats->overlap_residues = hs[1];
         float ms = 0; (void) hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); stats->ms_kernel = ms;

@@ -1,5 +1,7 @@
-// Device-wide exclusive scan (see device_utils.hpp).  Product code.
+// Device-wide exclusive scan (see device_utils.hpp) and what every list filter does with one: compactCsr (common.hpp).  Product code.
+#include "common.hpp"
 #include "device_utils.hpp"
+#include <algorithm>
 
 namespace plasship {
 
@@ -87,6 +89,49 @@ int exclusiveScanU32(hipStream_t stream, const uint32_t *d_in, uint64_t *d_out, 
 int exclusiveScanU64(hipStream_t stream, const uint64_t *d_in, uint64_t *d_out, size_t n, void *d_tmp, size_t tmpBytes) {
     if (tmpBytes < exclusiveScanTmpBytes(n)) return -1;
     return scanImpl<uint64_t>(stream, d_in, d_out, n, (uint64_t *) d_tmp);
+}
+
+// ---- compactCsr: the flagged records of a CSR list, in input order ----
+// A record is PIECES pieces of 16 bytes and a lane moves one piece, so both sides are coalesced whatever the record size.  (Every record
+// array is the start of a poolMalloc block, and those are 256-byte aligned: core.hip, POOL_ALIGN — CandHit's own aligned(8) does not matter.)
+template <int PIECES>
+__global__ void compactRecsKernel(const uint4 *__restrict__ in, const uint32_t *__restrict__ keep, const uint64_t *__restrict__ pos,
+                                  uint4 *__restrict__ out, uint64_t n) {
+    const uint64_t total = n * PIECES;
+    for (uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t) gridDim.x * blockDim.x) {
+        const uint64_t i = t / PIECES;
+        if (keep[i]) out[pos[i] * PIECES + t % PIECES] = in[t];
+    }
+}
+__global__ void compactOffsetsKernel(const uint64_t *__restrict__ inQoff, const uint64_t *__restrict__ pos, uint64_t *__restrict__ outQoff, uint64_t nQ) {
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i <= nQ; i += (uint64_t) gridDim.x * blockDim.x)
+        outQoff[i] = pos[inQoff[i]];
+}
+
+int compactCsr(plasship_ctx *ctx, const char *what, const uint64_t *dInQoff, uint64_t nQ, const void *dRecs, size_t recBytes, const uint32_t *dKeep,
+               uint64_t nRecs, uint64_t nKept, DevBuf &outQoff, DevBuf &outRecs) {
+    // an early error return waits for the stream first: the caller's flag kernel may still be queued, and its flags are a local of the caller
+    auto fail = [&](const char *msg, int rc) { (void) streamSync(ctx->stream); setError(std::string(what) + ": " + msg); return rc; };
+    if (recBytes != 16 && recBytes != 64) return fail("internal error: records of 16 or 64 bytes only", PLASSHIP_ERR_ARG);
+    DevBuf dPos, dTmp;
+    const size_t tmpBytes = exclusiveScanTmpBytes(nRecs);
+    if (dPos.alloc((nRecs + 1) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess || outQoff.alloc((nQ + 1) * 8) != hipSuccess ||
+        outRecs.alloc(std::max<uint64_t>(nKept, 1) * recBytes) != hipSuccess) return fail("out of device memory", PLASSHIP_ERR_DEVICE);
+    if (exclusiveScanU32(ctx->stream, dKeep, dPos.as<uint64_t>(), nRecs, dTmp.p, tmpBytes)) return fail("scan failed", PLASSHIP_ERR_DEVICE);
+    if (nRecs) {
+        const uint64_t pieces = nRecs * (recBytes / 16);
+        const dim3 grid((unsigned) std::min<uint64_t>((pieces + 255) / 256, (uint64_t) ctx->numCU * 64));
+        if (recBytes == 16) hipLaunchKernelGGL(compactRecsKernel<1>, grid, dim3(256), 0, ctx->stream, (const uint4 *) dRecs, dKeep, dPos.as<uint64_t>(), outRecs.as<uint4>(), nRecs);
+        else hipLaunchKernelGGL(compactRecsKernel<4>, grid, dim3(256), 0, ctx->stream, (const uint4 *) dRecs, dKeep, dPos.as<uint64_t>(), outRecs.as<uint4>(), nRecs);
+    }
+    hipLaunchKernelGGL(compactOffsetsKernel, dim3((unsigned) std::min<uint64_t>((nQ + 256) / 256, 65535)), dim3(256), 0, ctx->stream, dInQoff, dPos.as<uint64_t>(),
+                       outQoff.as<uint64_t>(), nQ);
+    // the one wait: the scan's total, after which dPos and dTmp may go (their kernels are through)
+    uint64_t total = 0;
+    PH_COPY_SYNC(ctx->stream, &total, dPos.as<uint64_t>() + nRecs, 8, hipMemcpyDeviceToHost);
+    PH_CHECK(hipGetLastError());
+    if (total != nKept) { setError(std::string(what) + ": internal error: the kept records do not add up to the list's count"); return PLASSHIP_ERR_DEVICE; }
+    return PLASSHIP_OK;
 }
 
 }  // namespace plasship
