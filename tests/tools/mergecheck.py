@@ -61,12 +61,17 @@ def _pad(strs, width):
     return m
 
 
-def align_pairs(s1, q1, s2, q2):
-    """s2 / q2 already reverse-complemented / reversed.  -> (best offset or -1 per pair)"""
+def align_pairs(s1, q1, s2, q2, trace=None):
+    """s2 / q2 already reverse-complemented / reversed.  -> (best offset or -1 per pair).  `trace`: a list that receives one dict per pair
+    with pair_align's intermediate values: l1, l2, off = {offset: (overlap after the uncalled positions, mismatches, quality sum, density,
+    quality score)} for every offset scanned (the last two None where the overlap is no candidate), and bd, bq, bp = the best density,
+    its quality score and its offset BEFORE the threshold (1.1, 0, -1 where no offset is a candidate)"""
     n = len(s1)
     L1 = np.array([len(s) for s in s1], dtype=np.int64)
     L2 = np.array([len(s) for s in s2], dtype=np.int64)
     best = np.full(n, -1, dtype=np.int64)
+    if trace is not None:
+        trace[:] = [{"l1": int(L1[k]), "l2": int(L2[k]), "off": {}, "bd": np.float32(1.1), "bq": np.float32(0), "bp": -1} for k in range(n)]
     order = np.argsort(L1, kind="stable")
     CH = 2048
     for c0 in range(0, n, CH):
@@ -101,9 +106,15 @@ def align_pairs(s1, q1, s2, q2):
             sl[~ok] = 1
             q = qt.astype(np.float32) / sl
             d = cnt.astype(np.float32) / sl
+            if trace is not None:
+                for j, k in enumerate(idx[sel]):
+                    trace[k]["off"][i] = (int(ln[j]), int(cnt[j]), int(qt[j]), d[j] if ok[j] else None, q[j] if ok[j] else None)
             better = ok & ((d < bd[sel]) | ((d == bd[sel]) & (q < bq[sel])))
             s = sel[better]
             bd[s], bq[s], bp[s] = d[better], q[better], i
+        if trace is not None:
+            for j, k in enumerate(idx):
+                trace[k].update(bd=bd[j], bq=bq[j], bp=int(bp[j]))
         bp[bd > MAX_DENSITY] = -1
         best[idx] = bp
     return best
@@ -118,12 +129,12 @@ def combine(s1, q1, s2, q2, pos):
     return bytes(a[:pos]) + bytes(mid.astype(np.uint8)) + bytes(b[ov:])
 
 
-def merge_records(r1, r2):
-    """two lists of (name, seq, qual) -> (sequence entries, header entries, n_combined); entries without the '\\0'"""
+def merge_records(r1, r2, trace=None):
+    """two lists of (name, seq, qual) -> (sequence entries, header entries, n_combined); entries without the '\\0'.  `trace`: see align_pairs"""
     n = min(len(r1), len(r2))
     s1 = [r1[k][1] for k in range(n)]; q1 = [r1[k][2] for k in range(n)]
     s2 = [revcomp(r2[k][1]) for k in range(n)]; q2 = [r2[k][2][::-1] for k in range(n)]
-    pos = align_pairs(s1, q1, s2, q2)
+    pos = align_pairs(s1, q1, s2, q2, trace)
     seqs, hdrs = [], []
     for k in range(n):
         if pos[k] >= 0:
