@@ -10,8 +10,8 @@
 //   lib/mmseqs/src/alignment/Matcher.cpp:248-320  the text round trip the reference reads its input through:
 //       seqId has 3 truncated decimals ("1.00" for 1.0), alnLength = max(|qE-qS|,|tE-tS|)+1, score = bit score
 //
-// Kernel design: the queue of a query lives in registers, one alignment per lane — 16, 32 or 64 lanes per query by queue size
-// (assembleGroupKernel<16/32/64>; work lists by prefix sums after an exact pre-screen), a compacted queue in LDS for 65..256 alignments
+// Kernel design: the queue of a query lives in registers, one alignment per lane — 8, 16, 32 or 64 lanes per query by queue size
+// (assembleGroupKernel<8/16/32/64>; work lists by prefix sums after an exact pre-screen), a compacted queue in LDS for 65..256 alignments
 // (assembleQueueKernel<128/256>, one wavefront per query) and an HBM-resident queue above that (assembleBigKernel).  A ROUND of the reference's pop loop is computed from the queued set: the comparator
 // is a strict total order, so std::priority_queue's pop order is "max of what is in the queue", the best right-extendable and the
 // best left-extendable hit (two arg-max reductions on a packed priority) are the round's two extensions, and every other hit is
@@ -60,7 +60,8 @@ struct AsmArgs {
     uint32_t *dbgRounds; uint32_t *dbgCycles;   // PLASSHIP_DEBUG_ASMHIST: [n] rounds (| 1 << 31 if extended) and clock ticks of each big query, else nullptr
     uint32_t *midList; uint32_t nMid;   // 33..64 alignments: one wavefront per query
     uint32_t *mid32List; uint32_t nMid32;   // 17..32 alignments: half a wavefront per query
-    uint32_t *smallList; uint32_t nSmall;                         // <= 16 alignments: 16 lanes per query
+    uint32_t *smallList; uint32_t nSmall;                         // 9..16 alignments: 16 lanes per query (nucleotide variants: the thread-per-query list)
+    uint32_t *narrowList; uint32_t nNarrow;                       // <= 8 alignments: 8 lanes per query
     uint32_t *heap;                             // nucleotide variant: [3*nLines] index heap + deferral list + consumed targets per query
     // nucleotide variant: comparator decisions on a threshold come from a host-evaluated table (see nuclLess)
     const uint32_t *ambKeys; const uint8_t *ambVals; uint32_t ambMask;    // open addressing, 4 words per key, empty = alpha1 0
@@ -1219,23 +1220,24 @@ __global__ __launch_bounds__(NT_BLOCK, 4) void assembleNuclThreadKernel(AsmArgs 
 }
 
 // ---- the common cases: the whole queue of a query lives in registers, one alignment per lane.
-//      G = 16: four queries per wavefront (a read has a handful of overlaps); G = 64: one query per wavefront.
-//      Sixteen/four independent groups per block share the LDS score table; no block barriers in the loop. ----
-// reductions over a group: inside a row of 16 lanes on the VALU (DPP), across rows with shuffles
+//      G = 8: eight queries per wavefront (a read has a handful of overlaps: most queues of the <= 16 tier hold at most 8); G = 16: four;
+//      G = 64: one query per wavefront.  The 32 to 4 independent groups of a block share the LDS score table; no block barriers in the loop. ----
+// reductions over a group: inside a row of 16 lanes (G = 8: a half row) on the VALU (DPP), across rows with shuffles
 template <int G> __device__ __forceinline__ int groupSum(int v) {
-    v = rowSum16(v);
+    v = rowSum<(G < 16 ? G : 16)>(v);
 #pragma unroll
     for (int o = 16; o < G; o <<= 1) v += __shfl_xor(v, o, G);
     return v;
 }
 template <int G> __device__ __forceinline__ unsigned long long groupMax(unsigned long long v) {
-    v = rowMax16(v);
+    v = rowMax<(G < 16 ? G : 16)>(v);
 #pragma unroll
     for (int o = 16; o < G; o <<= 1) { const unsigned long long ok = __shfl_xor(v, o, G); v = (ok > v) ? ok : v; }
     return v;
 }
 // rank of `mine` among the group's values (number of strictly smaller ones)
 template <int G> __device__ __forceinline__ uint32_t groupRank(uint32_t mine) {
+    if (G == 8) return rowCountLess8(mine);
     uint32_t r = rowCountLess16(mine, mine, false);
 #pragma unroll
     for (int o = 16; o < G; o += 16) r += rowCountLess16((uint32_t) __shfl_xor((int) mine, o, G), mine, true);
@@ -1266,6 +1268,7 @@ __device__ __forceinline__ Rescored rescoreOnDiagonalG(const char *q, unsigned q
     return r;
 }
 
+constexpr int ASM8_WPE = 5;       // wavefronts per SIMD of the 8-lane kernel, and its workgroups per CU
 template <int G, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void assembleGroupKernel(AsmArgs a) {
     __shared__ signed char smat[123 * 123 + 7];
@@ -1273,14 +1276,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     __syncthreads();
     const int gl = threadIdx.x & (G - 1);                         // lane within the group
     const uint32_t groupsTotal = gridDim.x * (256 / G);
-    const uint32_t nWork = (G == 64) ? a.nMid : ((G == 32) ? a.nMid32 : a.nSmall);
+    const uint32_t nWork = (G == 64) ? a.nMid : ((G == 32) ? a.nMid32 : ((G == 16) ? a.nSmall : a.nNarrow));
     unsigned long long nExt = 0, nResc = 0, nRescRes = 0, nAln = 0, nQRes = 0;
     // Round 6: a query starts with a chain of dependent round trips — work list entry -> CSR offsets, arena offset, packed (offset, length), left capacity ->
     // alignment records -> the targets' metadata -> bytes — and the counters show the wavefronts parked 57-72 % of their cycles.  The first two links travel
     // ahead: the list entry two items ahead in every lane (one register), and the five per-query words of the next item ONE WORD PER LANE (lanes 0..4 of the
     // group, two registers; ten registers per lane went to scratch and cost more than the look-ahead saved: profiles/r06_ab_knobs.txt, call 21), handed round
     // with shuffles when the item's turn comes.
-    const uint32_t *workList = (G == 64) ? a.midList : ((G == 32) ? a.mid32List : a.smallList);      // work lists: arenaSizeKernel
+    const uint32_t *workList = (G == 64) ? a.midList : ((G == 32) ? a.mid32List : ((G == 16) ? a.smallList : a.narrowList));      // work lists: tierListKernel
     auto loadWord = [&](uint32_t pid) -> uint64_t {
         uint64_t v = 0;
         if (pid != 0xFFFFFFFFu) {
@@ -1455,7 +1458,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     nExt = waveReduceSumU64(nExt); nResc = waveReduceSumU64(nResc); nRescRes = waveReduceSumU64(nRescRes); nAln = waveReduceSumU64(nAln); nQRes = waveReduceSumU64(nQRes);
     if (laneId() == 0) {
         if (nExt) atomicAdd(&a.stats[0], nExt); if (nResc) atomicAdd(&a.stats[1], nResc); if (nRescRes) atomicAdd(&a.stats[2], nRescRes);
-        const int tier = (G == 16) ? 0 : 1;      // the 32- and 64-lane kernels share tier 1 in the statistics
+        const int tier = (G <= 16) ? 0 : 1;      // the 8- and 16-lane kernels are tier 0 of the statistics, the 32- and 64-lane kernels tier 1
         if (nAln) { atomicAdd(&a.stats[3 + 3 * tier], nAln); atomicAdd(&a.stats[4 + 3 * tier], nQRes); atomicAdd(&a.stats[5 + 3 * tier], nRescRes); }
     }
 }
@@ -1509,13 +1512,14 @@ __global__ __launch_bounds__(256) void arenaSumKernel(const AlnRec *__restrict__
     }
 }
 // arena sizing: query + all targets on either side (a hit is attached at most once, to one side)
-// ... and the tier of each query that passed the pre-screen, by queue size (<= 16, <= 32, <= 64, more), as flags packed
-// for two 64-bit prefix sums (tierA: tier 0 | tier 1 << 32, tierB: tier 2 | tier 3 << 32); listKernel turns the scanned
-// positions into the work lists of the extension kernels (id order, no atomics)
+// ... and the tier of each query that passed the pre-screen, by queue size (9..16, <= 32, <= 64, more, <= 8), one byte per query
+// (TIER_NONE: no work); tierCountKernel / tierListKernel turn the bytes into the work lists of the extension kernels (id order, no atomics)
+constexpr int N_TIERS = 5;
+constexpr uint8_t TIER_NARROW = 4, TIER_NONE = 0xFF;         // (tiers 0 and 1 are also the two lists of the nucleotide variants)
 __global__ void arenaSizeKernel(SeqView s, const uint64_t *__restrict__ qoff, const unsigned long long *__restrict__ qSum, const unsigned long long *__restrict__ qSumAa,
                                 const uint32_t *__restrict__ qCan, uint32_t *__restrict__ leftCap,
                                 uint64_t *__restrict__ bytes, int nuclTiers, uint64_t threadBytes,
-                                uint64_t *__restrict__ tierA, uint64_t *__restrict__ tierB,
+                                uint8_t *__restrict__ tierOf,
                                 const uint32_t *__restrict__ aaLen, uint32_t *__restrict__ aaLeftCap, uint64_t *__restrict__ aaBytes) {
     for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < s.n; id += gridDim.x * blockDim.x) {
         int tier = -1;
@@ -1528,20 +1532,69 @@ __global__ void arenaSizeKernel(SeqView s, const uint64_t *__restrict__ qoff, co
         // nucleotide variants: thread-per-query list (up to 256 hits AND an arena slice — query + twice the targets — of at most threadBytes:
         // a thread copies and re-scores byte ranges alone, and its wavefront waits for it; round 4: the contigs of the late iterations of
         // configs[4], 10-100 kb with a few dozen hits, kept their wavefronts for hundreds of ms), wave-per-query list for the rest
-        if (sum && can) { const uint64_t h = qoff[id + 1] - qoff[id]; tier = nuclTiers ? ((h <= 256 && slice <= threadBytes) ? 0 : 1) : (h <= 16 ? 0 : (h <= 32 ? 1 : (h <= 64 ? 2 : 3))); }
-        tierA[id] = (tier == 0) ? 1ull : ((tier == 1) ? (1ull << 32) : 0ull);
-        tierB[id] = (tier == 2) ? 1ull : ((tier == 3) ? (1ull << 32) : 0ull);
+        if (sum && can) { const uint64_t h = qoff[id + 1] - qoff[id]; tier = nuclTiers ? ((h <= 256 && slice <= threadBytes) ? 0 : 1) : (h <= 8 ? (int) TIER_NARROW : (h <= 16 ? 0 : (h <= 32 ? 1 : (h <= 64 ? 2 : 3)))); }
+        tierOf[id] = (tier < 0) ? TIER_NONE : (uint8_t) tier;
     }
 }
-__global__ void listKernel(uint32_t n, const uint64_t *__restrict__ tierA, const uint64_t *__restrict__ tierB, const uint64_t *__restrict__ posA,
-                           const uint64_t *__restrict__ posB, uint32_t *__restrict__ list0, uint32_t *__restrict__ list1, uint32_t *__restrict__ list2,
-                           uint32_t *__restrict__ list3) {
-    for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < n; id += gridDim.x * blockDim.x) {
-        const uint64_t a = tierA[id], b = tierB[id];
-        if (a & 0xFFFFFFFFull) list0[(uint32_t) posA[id]] = id;
-        else if (a) list1[(uint32_t) (posA[id] >> 32)] = id;
-        else if (b & 0xFFFFFFFFull) list2[(uint32_t) posB[id]] = id;
-        else if (b) list3[(uint32_t) (posB[id] >> 32)] = id;
+// The work lists from the tier bytes, as a scan that carries all N_TIERS counters at once: a tile of SCAN_TILE queries per workgroup, the five
+// counters of a thread, a wavefront and a tile packed into ONE 64-bit word of 12-bit fields (a field counts at most the SCAN_TILE = 2048 queries
+// of a tile, whatever N is; only the tiles' totals, one 64-bit word per tier and tile, are scanned device-wide).  Against two 64-bit flag
+// arrays, their two device-wide scans and a pass over flags and positions, a query costs two byte reads and its list entry.
+static_assert(SCAN_TILE < (1 << 12) && N_TIERS * 12 <= 64 && SCAN_BLOCK == 256, "tier counters of a tile: 12-bit fields of one 64-bit word");
+__device__ __forceinline__ unsigned long long tierField(uint8_t t) { return (t < N_TIERS) ? (1ull << (12 * t)) : 0ull; }
+// the tier bytes of the SCAN_ITEMS = 8 consecutive queries of a thread (the array is the start of a 256-byte aligned block)
+__device__ __forceinline__ uint64_t loadTierBytes(const uint8_t *__restrict__ tierOf, uint32_t n, uint64_t base) {
+    static_assert(SCAN_ITEMS == 8, "eight tier bytes per thread");
+    if (base + 8 <= n) return *reinterpret_cast<const uint64_t *>(tierOf + base);
+    uint64_t w = ~0ull;                                     // TIER_NONE past the end
+    for (int k = 0; k < 8; k++) if (base + k < n) w = (w & ~(0xFFull << (8 * k))) | ((uint64_t) tierOf[base + k] << (8 * k));
+    return w;
+}
+// partial[t * (nTiles + 1) + tile]: queries of tier t in the tile
+__global__ __launch_bounds__(SCAN_BLOCK) void tierCountKernel(const uint8_t *__restrict__ tierOf, uint32_t n, uint64_t *__restrict__ partial, uint32_t nTiles) {
+    __shared__ unsigned long long wsum[SCAN_BLOCK / WAVE];
+    const uint64_t w = loadTierBytes(tierOf, n, (uint64_t) blockIdx.x * SCAN_TILE + (uint64_t) threadIdx.x * SCAN_ITEMS);
+    unsigned long long s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) s += tierField((uint8_t) (w >> (8 * k)));
+    s = waveReduceSumU64(s);
+    if (laneId() == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x < N_TIERS) {
+        unsigned long long t = 0;
+        for (int j = 0; j < SCAN_BLOCK / WAVE; j++) t += wsum[j];
+        partial[(size_t) threadIdx.x * (nTiles + 1) + blockIdx.x] = (t >> (12 * threadIdx.x)) & 0xFFFull;
+    }
+}
+struct TierLists { uint32_t *list[N_TIERS]; };
+// tileOff: `partial` after ONE exclusive scan over all rows end to end (a tile's offset in its tier's list is its entry minus the row's first)
+__global__ __launch_bounds__(SCAN_BLOCK) void tierListKernel(const uint8_t *__restrict__ tierOf, uint32_t n, const uint64_t *__restrict__ tileOff, uint32_t nTiles,
+                                                             TierLists lists) {
+    __shared__ unsigned long long wsum[SCAN_BLOCK / WAVE];
+    const uint64_t base = (uint64_t) blockIdx.x * SCAN_TILE + (uint64_t) threadIdx.x * SCAN_ITEMS;
+    const uint64_t w = loadTierBytes(tierOf, n, base);
+    unsigned long long s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) s += tierField((uint8_t) (w >> (8 * k)));
+    const unsigned long long incl = waveInclusiveScanU64(s);
+    const int wv = threadIdx.x >> 6;
+    if (laneId() == 63) wsum[wv] = incl;
+    __syncthreads();
+    unsigned long long run = incl - s;
+#pragma unroll
+    for (int j = 0; j < SCAN_BLOCK / WAVE; j++) if (j < wv) run += wsum[j];
+    if (s == 0) return;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint8_t t = (uint8_t) (w >> (8 * k));
+        if (t < N_TIERS) {
+            const uint64_t *row = tileOff + (size_t) t * (nTiles + 1);
+            const uint32_t pos = (uint32_t) (row[blockIdx.x] - row[0]) + (uint32_t) ((run >> (12 * t)) & 0xFFFull);
+            // (a select, not lists.list[t]: indexing the by-value argument with a per-lane index would put the struct into scratch)
+            uint32_t *list = (t == 0) ? lists.list[0] : ((t == 1) ? lists.list[1] : ((t == 2) ? lists.list[2] : ((t == 3) ? lists.list[3] : lists.list[4])));
+            list[pos] = (uint32_t) (base + k);
+            run += 1ull << (12 * t);
+        }
     }
 }
 
@@ -1987,10 +2040,11 @@ static int mergeExtended(plasship_ctx *ctx, uint32_t N, bool guided, int keepTar
 }
 
 // PLASSHIP_DEBUG_ASMHIST=1 (debug only, off by default): per assembleresults call, the queries of more than 64 alignments by queue size h
-// (queries, extended, rounds, share of the kernels' clock ticks) and by rounds per query, on stderr.  It waits for the stream.
+// (queries, extended, rounds, share of the kernels' clock ticks) and by rounds per query, and the number of queries of each tier, on stderr.
+// Every protein call allocates two N-word buffers, copies offsets, rounds and ticks to the host and waits for the stream, also when no query has more than 64 alignments.
 static bool asmHistOn() { return getenv("PLASSHIP_DEBUG_ASMHIST") != nullptr; }
 static int asmHistRecord(hipStream_t st, uint32_t N, const uint64_t *dQoff, const uint32_t *dBigList, uint32_t nBig, const uint32_t *dRounds, const uint32_t *dCycles,
-                         uint32_t cap) {
+                         uint32_t cap, const uint32_t *tierQueries) {
     static int call = 0;
     std::vector<uint32_t> ids(nBig), rounds(N), cycles(N);
     std::vector<uint64_t> qoff((size_t) N + 1);
@@ -2017,6 +2071,8 @@ static int asmHistRecord(hipStream_t st, uint32_t N, const uint64_t *dQoff, cons
     }
     s += " | rounds 0,1,2,<=4,<=8,<=16,<=32,more:";
     for (int k = 0; k < NR; k++) s += " " + std::to_string(rq[k]);
+    s += " | tier queries <=8,<=16,<=32,<=64,more:";
+    for (int t = 0; t < 5; t++) s += " " + std::to_string(tierQueries[t]);
     fprintf(stderr, "%s\n", s.c_str());
     return PLASSHIP_OK;
 }
@@ -2051,14 +2107,15 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     { const int rcOL = ensureOffLen(ctx, db); if (rcOL) return rcOL; }          // the extension kernels look up random targets
     const SeqView sv = db->view();
     PH_CHECK(hipEventRecord(ctx->ev[0], st));
-    // work lists by queue size: [0] <= 16 alignments, [1] <= 32, [2] <= 64, [3] more (filled by arenaSizeKernel)
-    DevBuf dBigList, dMidList, dMid32List, dSmallList, dTierA, dTierB, dPosA, dPosB, dAaLeftCap, dAaBytes, dAaArenaOff, dAaArena, dAaNewLen, dAaNewStart;
+    // work lists by queue size: [0] 9..16 alignments, [1] <= 32, [2] <= 64, [3] more, [4] <= 8 (tiers: arenaSizeKernel; lists: tierListKernel)
+    const uint32_t nTiles = (uint32_t) (((size_t) N + SCAN_TILE - 1) / SCAN_TILE);
+    DevBuf dBigList, dMidList, dMid32List, dSmallList, dNarrowList, dTierOf, dTierPart, dAaLeftCap, dAaBytes, dAaArenaOff, dAaArena, dAaNewLen, dAaNewStart;
     if (guided && (dAaLeftCap.alloc(((size_t) N + 1) * 4) != hipSuccess || dAaBytes.alloc(((size_t) N + 1) * 8) != hipSuccess || dAaArenaOff.alloc(((size_t) N + 2) * 8) != hipSuccess ||
                    dAaNewLen.alloc(((size_t) N + 1) * 4) != hipSuccess || dAaNewStart.alloc(((size_t) N + 1) * 8) != hipSuccess)) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
     if (guided) PH_CHECK(hipMemsetAsync(dAaNewLen.p, 0, ((size_t) N + 1) * 4, st));
     if (dBigList.alloc(((size_t) N + 1) * 4) != hipSuccess || dMidList.alloc(((size_t) N + 1) * 4) != hipSuccess || dMid32List.alloc(((size_t) N + 1) * 4) != hipSuccess ||
-        dSmallList.alloc(((size_t) N + 1) * 4) != hipSuccess || dTierA.alloc(((size_t) N + 1) * 8) != hipSuccess || dTierB.alloc(((size_t) N + 1) * 8) != hipSuccess ||
-        dPosA.alloc(((size_t) N + 2) * 8) != hipSuccess || dPosB.alloc(((size_t) N + 2) * 8) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        dSmallList.alloc(((size_t) N + 1) * 4) != hipSuccess || (!nucl && dNarrowList.alloc(((size_t) N + 1) * 4) != hipSuccess) || dTierOf.alloc((size_t) N + 8) != hipSuccess ||
+        dTierPart.alloc(((size_t) N_TIERS * (nTiles + 1) + 1) * 8) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
     DevBuf dQSum, dQSumAa, dQCan;
     if (dQSum.alloc(((size_t) N + 1) * 8) != hipSuccess || dQCan.alloc(((size_t) N + 1) * 4) != hipSuccess || (guided && dQSumAa.alloc(((size_t) N + 1) * 8) != hipSuccess)) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
     PH_CHECK(hipMemsetAsync(dQSum.p, 0, ((size_t) N + 1) * 8, st));
@@ -2069,23 +2126,29 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
                                        (nucl && !guided) ? 1 : 0);
     if (N) hipLaunchKernelGGL(arenaSizeKernel, dim3(std::min<uint32_t>((N + 255) / 256, 8192)), dim3(256), 0, st, sv, al->d_qoff.as<uint64_t>(), (const unsigned long long *) dQSum.as<unsigned long long>(),
                               (const unsigned long long *) dQSumAa.as<unsigned long long>(), (const uint32_t *) dQCan.as<uint32_t>(), dLeftCap.as<uint32_t>(), dBytes.as<uint64_t>(), nucl ? 1 : 0, (uint64_t) 1 << 30,
-                              dTierA.as<uint64_t>(), dTierB.as<uint64_t>(),
+                              dTierOf.as<uint8_t>(),
                               guided ? aaDb->d_len.as<uint32_t>() : (const uint32_t *) nullptr, dAaLeftCap.as<uint32_t>(), guided ? dAaBytes.as<uint64_t>() : (uint64_t *) nullptr);
     if (guided && exclusiveScanU64(st, dAaBytes.as<uint64_t>(), dAaArenaOff.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
-    if (exclusiveScanU64(st, dTierA.as<uint64_t>(), dPosA.as<uint64_t>(), N, dTmp.p, tmpBytes) || exclusiveScanU64(st, dTierB.as<uint64_t>(), dPosB.as<uint64_t>(), N, dTmp.p, tmpBytes)) {
-        setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE;
+    PH_CHECK(hipMemsetAsync(dTierPart.p, 0, ((size_t) N_TIERS * (nTiles + 1) + 1) * 8, st));
+    if (nTiles) hipLaunchKernelGGL(tierCountKernel, dim3(nTiles), dim3(SCAN_BLOCK), 0, st, (const uint8_t *) dTierOf.as<uint8_t>(), N, dTierPart.as<uint64_t>(), nTiles);
+    // ONE scan over the five rows end to end, in place (entry [nTiles] of a row is 0): a row's entries minus its first one are the tiles' offsets in
+    // the tier's list, and the first entry of the next row minus its own is the tier's total
+    if (exclusiveScanU64(st, dTierPart.as<uint64_t>(), dTierPart.as<uint64_t>(), (size_t) N_TIERS * (nTiles + 1), dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
+    {
+        TierLists tl;
+        tl.list[0] = dSmallList.as<uint32_t>(); tl.list[1] = dMid32List.as<uint32_t>(); tl.list[2] = dMidList.as<uint32_t>(); tl.list[3] = dBigList.as<uint32_t>();
+        tl.list[TIER_NARROW] = dNarrowList.as<uint32_t>();              // (not allocated for a nucleotide DB, whose queries have tiers 0 and 1 only)
+        if (nTiles) hipLaunchKernelGGL(tierListKernel, dim3(nTiles), dim3(SCAN_BLOCK), 0, st, (const uint8_t *) dTierOf.as<uint8_t>(), N, (const uint64_t *) dTierPart.as<uint64_t>(), nTiles, tl);
     }
-    if (N) hipLaunchKernelGGL(listKernel, dim3(std::min<uint32_t>((N + 255) / 256, 8192)), dim3(256), 0, st, N, dTierA.as<uint64_t>(), dTierB.as<uint64_t>(), dPosA.as<uint64_t>(), dPosB.as<uint64_t>(),
-                              dSmallList.as<uint32_t>(), dMid32List.as<uint32_t>(), dMidList.as<uint32_t>(), dBigList.as<uint32_t>());
     if (exclusiveScanU64(st, dBytes.as<uint64_t>(), dArenaOff.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
     uint64_t arenaBytes = 0, aaArenaBytes = 0;
-    uint64_t totA = 0, totB = 0;
+    uint64_t rowStart[N_TIERS + 1] = {};
     if (guided) PH_CHECK(hipMemcpyAsync(&aaArenaBytes, dAaArenaOff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
     PH_CHECK(hipMemcpyAsync(&arenaBytes, dArenaOff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    PH_CHECK(hipMemcpyAsync(&totA, dPosA.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    PH_CHECK(hipMemcpyAsync(&totB, dPosB.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
+    PH_CHECK(hipMemcpy2DAsync(rowStart, 8, dTierPart.p, (size_t) (nTiles + 1) * 8, 8, N_TIERS + 1, hipMemcpyDeviceToHost, st));
     PH_CHECK(plasship::streamSync(st));
-    const uint32_t cnts[4] = {(uint32_t) totA, (uint32_t) (totA >> 32), (uint32_t) totB, (uint32_t) (totB >> 32)};
+    uint32_t cnts[N_TIERS];
+    for (int t = 0; t < N_TIERS; t++) cnts[t] = (uint32_t) (rowStart[t + 1] - rowStart[t]);
     if (dArena.alloc(arenaBytes + 64) != hipSuccess || (guided && dAaArena.alloc(aaArenaBytes + 64) != hipSuccess)) {
         size_t fr = 0, tt = 0; (void) hipMemGetInfo(&fr, &tt);
         setError("plasship_assemble: out of device memory for the extension arena (" + std::to_string(arenaBytes) + " bytes; device free " + std::to_string(fr) + " of " + std::to_string(tt) + ")"); return PLASSHIP_ERR_DEVICE;
@@ -2098,6 +2161,7 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     a.ownLaneMin = 6;      // swept 1 / 3 / 6 / 12 / never: 30.4 / 28.4 / 27.9 / 29.9 / 40.3 ms for the two wide tiers (profiles/r05_ab_knobs.txt, call 11)
     a.stats = dStats.as<unsigned long long>();
     a.smallList = dSmallList.as<uint32_t>(); a.nSmall = cnts[0];
+    a.narrowList = dNarrowList.as<uint32_t>(); a.nNarrow = cnts[TIER_NARROW];
     a.mid32List = dMid32List.as<uint32_t>(); a.nMid32 = cnts[1];
     a.midList = dMidList.as<uint32_t>(); a.nMid = cnts[2];
     a.bigList = dBigList.as<uint32_t>(); a.nBig = cnts[3];
@@ -2185,6 +2249,8 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     // (round 5: the four tiers — disjoint queries — launched side by side on four streams, so that one tier's tail of long queues lies under
     //  the next tier: 88.8 against 82.7 ms for the stage; the tiers' wavefronts evict each other's lines.  profiles/r05_ab_knobs.txt)
     PH_CHECK(hipEventRecord(ctx->ev[2], st));
+    // queues of at most 8 alignments, 8 lanes each: the same instruction serves twice the queries, and a wavefront keeps eight chains of round trips in flight
+    if (a.nNarrow) hipLaunchKernelGGL((assembleGroupKernel<8, ASM8_WPE>), dim3(std::min<uint32_t>((a.nNarrow + 31) / 32, (uint32_t) ctx->numCU * ASM8_WPE)), dim3(256), 0, st, a);
     if (a.nSmall) hipLaunchKernelGGL((assembleGroupKernel<16, 5>), g16, dim3(256), 0, st, a);
     PH_CHECK(hipEventRecord(ctx->ev[3], st));
     PH_CHECK(hipEventRecord(ctx->ev[4], st));
@@ -2193,7 +2259,8 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     PH_CHECK(hipEventRecord(ctx->ev[5], st));
     PH_CHECK(hipEventRecord(ctx->ev[6], st));
     DevBuf dDbgRounds, dDbgCycles;
-    const bool hist = asmHistOn() && a.nBig;
+    const bool hist = asmHistOn();
+    const uint32_t tierQ[5] = {a.nNarrow, a.nSmall, a.nMid32, a.nMid, a.nBig};
     if (hist) {
         if (dDbgRounds.alloc(((size_t) N + 1) * 4) != hipSuccess || dDbgCycles.alloc(((size_t) N + 1) * 4) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
         PH_CHECK(hipMemsetAsync(dDbgRounds.p, 0, ((size_t) N + 1) * 4, st));
@@ -2221,7 +2288,7 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
         hipLaunchKernelGGL(assembleBigKernel, gBig, dim3(256), 0, st, o);
     } else if (a.nBig) hipLaunchKernelGGL(assembleBigKernel, gBig, dim3(256), 0, st, a);
     PH_CHECK(hipEventRecord(ctx->ev[7], st));
-    if (hist) { const int rcH = asmHistRecord(st, N, a.qoff, a.bigList, a.nBig, a.dbgRounds, a.dbgCycles, onChip ? qCap : 64); if (rcH) return rcH; }
+    if (hist) { const int rcH = asmHistRecord(st, N, a.qoff, a.bigList, a.nBig, a.dbgRounds, a.dbgCycles, onChip ? qCap : 64, tierQ); if (rcH) return rcH; }
     }
     PH_TRACE(st, "assemble: extension kernels");
     // ---- output DB(s): extended queries + carried-over sequences, in key order ----

@@ -19,20 +19,26 @@ template <int CTRL> __device__ __forceinline__ unsigned long long dppMov64(unsig
     const uint32_t lo = dppMov<CTRL>((uint32_t) v), hi = dppMov<CTRL>((uint32_t) (v >> 32));
     return ((unsigned long long) hi << 32) | lo;
 }
-// all-reduce over each row of 16 lanes: xor 1, xor 2 (quad_perm), then mirror inside 8, mirror inside 16
-__device__ __forceinline__ int rowSum16(int v) {
+// all-reduce over each row of W = 16 lanes, or over each half row of W = 8: xor 1, xor 2 (quad_perm), mirror inside 8, then mirror inside 16
+// (the first three steps stay inside the aligned eight lanes, so the half-row forms are the row forms without their last step)
+template <int W> __device__ __forceinline__ int rowSum(int v) {
+    static_assert(W == 8 || W == 16, "a row of 16 lanes or half of one");
     v += (int) dppMov<0xB1>((uint32_t) v); v += (int) dppMov<0x4E>((uint32_t) v);
-    v += (int) dppMov<0x141>((uint32_t) v); v += (int) dppMov<0x140>((uint32_t) v);
+    v += (int) dppMov<0x141>((uint32_t) v);
+    if (W == 16) v += (int) dppMov<0x140>((uint32_t) v);
     return v;
 }
-__device__ __forceinline__ unsigned long long rowMax16(unsigned long long v) {
+template <int W> __device__ __forceinline__ unsigned long long rowMax(unsigned long long v) {
+    static_assert(W == 8 || W == 16, "a row of 16 lanes or half of one");
     unsigned long long o;
     o = dppMov64<0xB1>(v); v = o > v ? o : v;
     o = dppMov64<0x4E>(v); v = o > v ? o : v;
     o = dppMov64<0x141>(v); v = o > v ? o : v;
-    o = dppMov64<0x140>(v); v = o > v ? o : v;
+    if (W == 16) { o = dppMov64<0x140>(v); v = o > v ? o : v; }
     return v;
 }
+__device__ __forceinline__ int rowSum16(int v) { return rowSum<16>(v); }
+__device__ __forceinline__ unsigned long long rowMax16(unsigned long long v) { return rowMax<16>(v); }
 __device__ __forceinline__ uint32_t rowMin16U32(uint32_t v) {
     uint32_t o;
     o = dppMov<0xB1>(v); v = o < v ? o : v;
@@ -55,6 +61,14 @@ template <int N> struct RowCountLess {
 template <> struct RowCountLess<0> { static __device__ __forceinline__ uint32_t run(uint32_t, uint32_t) { return 0u; } };
 __device__ __forceinline__ uint32_t rowCountLess16(uint32_t other, uint32_t mine, bool includeUnrotated) {
     return RowCountLess<15>::run(other, mine) + ((includeUnrotated && other < mine) ? 1u : 0u);
+}
+
+// the same over a half row of 8 lanes (row_ror would cross into the other half): the three rotations of the own quad, then the other
+// quad by way of the half row's mirror image and its three rotations — seven compares
+__device__ __forceinline__ uint32_t rowCountLess8(uint32_t mine) {
+    const uint32_t far = dppMov<0x141>(mine);
+    return ((dppMov<0x39>(mine) < mine) ? 1u : 0u) + ((dppMov<0x4E>(mine) < mine) ? 1u : 0u) + ((dppMov<0x93>(mine) < mine) ? 1u : 0u) +
+           ((far < mine) ? 1u : 0u) + ((dppMov<0x39>(far) < mine) ? 1u : 0u) + ((dppMov<0x4E>(far) < mine) ? 1u : 0u) + ((dppMov<0x93>(far) < mine) ? 1u : 0u);
 }
 
 __device__ __forceinline__ int waveReduceSum(int v) {

@@ -29,7 +29,7 @@ st = {'km': 0, 'rs': 0, 'as': 0}
 for name, rr in t['kernels'].items():
     b = rr['hbm_bytes_per_launch'] * rr['launches'] / t.get('steps', 25)
     if re.search(r'synth|orfKernel|translate|concat|digest|rocclr|keysDiffer|nonZero|maxLen', name): continue
-    k = 'rs' if re.search(r'rescoreKernel|packOffLen|markLengths', name) else ('as' if re.search(r'assemble|arenaSum|arenaSize|listKernel|outLen|appendOut|writeOut|maxU32|bigNeed', name) else 'km')
+    k = 'rs' if re.search(r'rescoreKernel|packOffLen|markLengths', name) else ('as' if re.search(r'assemble|arenaSum|arenaSize|tierCount|tierList|outLen|appendOut|writeOut|maxU32|bigNeed', name) else 'km')
     st[k] += b
 print('stage traffic GB', {k: round(v / 1e9, 1) for k, v in st.items()})
 d5 = last('bench_c5.log'); print('c5 %.1f ms %.1f M/s verify %s' % (d5['ms_per_step'], d5['value'] / 1e6, d5['verify'].get('match'))); print({k: round(v, 1) for k, v in d5['roofline']['stage_ms_per_step'].items()}); print(d5['roofline'].get('furthest_below'))
