@@ -24,6 +24,7 @@
 #include "device_utils.hpp"
 #include "posterior_class.hpp"
 #include "ref_rules.hpp"
+#include "asm_rules.hpp"
 #include "host_util.hpp"
 #include <algorithm>
 #include <memory>
@@ -180,13 +181,10 @@ struct Rescored { int startPos, endPos; unsigned score, diagonalLen; int idExcl;
 __device__ __forceinline__ Rescored rescoreOnDiagonal(const char *q, unsigned qLen, const char *t, unsigned tLen, int diagonal,
                                                       const signed char *smat) {
     Rescored r; r.startPos = -1; r.endPos = -1; r.score = 0; r.diagonalLen = 0; r.idExcl = 0;
-    const unsigned dist = (unsigned) abs(diagonal);
-    unsigned qo, to, len;
-    if (diagonal >= 0 && dist < qLen) { qo = dist; to = 0; len = min(tLen, qLen - dist); }
-    else if (diagonal < 0 && dist < tLen) { qo = 0; to = dist; len = min(tLen - dist, qLen); }
-    else return r;
+    const DiagSpan sp = diagonalSpan(diagonal, qLen, tLen);
+    const unsigned qo = sp.qo, to = sp.to, len = sp.len;
     r.diagonalLen = len;
-    if (len == 0) return r;
+    if (!sp.hit || len == 0) return r;
     unsigned first, last;
     int s = 0, ids = 0;
     scoreColumnsG<64>(q + qo, t + to, len, smat, laneId(), first, last, s, ids);
@@ -198,6 +196,9 @@ __device__ __forceinline__ Rescored rescoreOnDiagonal(const char *q, unsigned qL
 __device__ __forceinline__ void waveMemSync() {   // make this wave's global stores visible to its own later loads
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+__device__ __forceinline__ unsigned long long queueKey(int score, uint32_t alnLength) {
+    return ((unsigned long long) ((uint32_t) score ^ 0x80000000u) << 32) | (unsigned long long) alnLength;
 }
 // Four wavefronts per workgroup share the 15 KB score table (one wavefront per workgroup let LDS cap the CU at 10 wavefronts); a
 // wavefront works on its own queries and orders its own memory operations with fences — there is no workgroup barrier in the loop.
@@ -226,15 +227,12 @@ __global__ __launch_bounds__(256) void assembleBigKernel(AsmArgs a) {
             const AlnRec r = a.recs[h0 + i];
             Item x;
             x.target = r.target;
-            const int aq = (r.qStart == -1) ? 0 : r.qStart, ad = (r.dbStart == -1) ? 0 : r.dbStart;
-            x.alnLength = (uint32_t) (max(abs(r.qEnd - aq), abs(r.dbEnd - ad)) + 1);           // Matcher::computeAlnLength
-            const int rawScore = (int) (fma((double) r.bitScore, a.ln2, a.logK) / a.lambda + 0.5);
-            const float scorePerCol = (float) rawScore / (float) ((double) x.alnLength + 0.5);
+            x.alnLength = (uint32_t) alnLengthOf(r.qStart, r.qEnd, r.dbStart, r.dbEnd);
             const float sid = r.fromText ? r.seqId : seqIdThroughText(r.seqId);
             const float alnLen = (float) x.alnLength;
             const float ids = sid * alnLen;
             x.seqId = (float) ((double) ids / ((double) alnLen + 0.5));
-            x.score = (int) (scorePerCol * 100);
+            x.score = scorePerCol100(rawScoreOfBits(r.bitScore, a.ln2, a.logK, a.lambda), x.alnLength);
             x.qStart = r.qStart; x.qEnd = r.qEnd; x.qLen = (uint32_t) r.qLen; x.dbStart = r.dbStart; x.dbEnd = r.dbEnd; x.dbLen = (uint32_t) r.dbLen;
             x.state = r.accepted ? 0u : 2u; x.pad = 0;                                    // a hole of a sparse list was never queued
             it[i] = x;
@@ -259,17 +257,13 @@ __global__ __launch_bounds__(256) void assembleBigKernel(AsmArgs a) {
                 if (x.state == 1) { it[i].state = 2; continue; }      // leftovers of the previous round
                 if (x.state != 0) continue;
                 // ranks inside the queue are not precomputed here: ties on (score, alnLength) are broken by the smaller target id
-                const unsigned long long key = ((unsigned long long) ((uint32_t) x.score ^ 0x80000000u) << 32) | (unsigned long long) x.alnLength;
-                const bool notBoth = !(x.dbStart == 0 && x.qStart == 0);
-                const bool rightStart = x.dbStart == 0 && (x.dbEnd != (int) x.dbLen - 1);
-                const bool leftStart = x.qStart == 0 && (x.qEnd != (int) x.qLen - 1);
-                if (!((rightStart || leftStart) && notBoth) || x.target == id) continue;
+                const unsigned long long key = queueKey(x.score, x.alnLength);
+                if (!isBranchType(x.qStart, x.qEnd, x.qLen, x.dbStart, x.dbEnd, x.dbLen) || x.target == id) continue;
                 const unsigned tLen = seqLen(a.s, x.target);
                 if (x.dbStart == 0) {
-                    const unsigned fragR = tLen - ((unsigned) x.dbEnd + 1);
-                    if (fragR > 0 && (unsigned) x.qEnd == (querySeqLen - 1) && (key > bestR || (key == bestR && x.target < it[idxR].target))) { bestR = key; idxR = i; }
+                    if (canExtendRight(rightFragLen(tLen, x.dbEnd), x.qEnd, querySeqLen) && (key > bestR || (key == bestR && x.target < it[idxR].target))) { bestR = key; idxR = i; }
                 } else if (x.qStart == 0) {
-                    if (x.dbStart > 0 && (unsigned) x.dbEnd == (tLen - 1) && (key > bestL || (key == bestL && x.target < it[idxL].target))) { bestL = key; idxL = i; }
+                    if (canExtendLeft(x.dbStart, x.dbEnd, tLen) && (key > bestL || (key == bestL && x.target < it[idxL].target))) { bestL = key; idxL = i; }
                 }
             }
             // wave arg-max with the target id as the final tie-break
@@ -313,19 +307,16 @@ __global__ __launch_bounds__(256) void assembleBigKernel(AsmArgs a) {
                 const Item x = it[i];
                 if (x.state != 0) continue;
                 if (brokeOut) {                                    // hits ranked below the left hit were never popped
-                    const unsigned long long key = ((unsigned long long) ((uint32_t) x.score ^ 0x80000000u) << 32) | (unsigned long long) x.alnLength;
+                    const unsigned long long key = queueKey(x.score, x.alnLength);
                     const bool below = key < bestL || (key == bestL && x.target > tgtL);
                     if (below) { still++; continue; }
                 }
                 uint32_t st = 2;
                 const bool used = (i == idxR && (rFirst || !brokeOut)) || i == idxL;
-                const bool notBoth = !(x.dbStart == 0 && x.qStart == 0);
-                const bool rightStart = x.dbStart == 0 && (x.dbEnd != (int) x.dbLen - 1);
-                const bool leftStart = x.qStart == 0 && (x.qEnd != (int) x.qLen - 1);
-                if (!used && (rightStart || leftStart) && notBoth && x.target != id) {
+                if (!used && isBranchType(x.qStart, x.qEnd, x.qLen, x.dbStart, x.dbEnd, x.dbLen) && x.target != id) {
                     const unsigned tLen = seqLen(a.s, x.target);
-                    if (x.dbStart == 0) { if ((tLen - ((unsigned) x.dbEnd + 1)) > rightOff && (unsigned) x.qEnd == (querySeqLen - 1) && rightOff > 0) st = 1; }
-                    else if (x.qStart == 0) { if (x.dbStart > (int) leftOff && (unsigned) x.dbEnd == (tLen - 1) && leftOff > 0) st = 1; }
+                    if (x.dbStart == 0) { if (deferredRight(rightFragLen(tLen, x.dbEnd), x.qEnd, querySeqLen, rightOff)) st = 1; }
+                    else if (x.qStart == 0) { if (deferredLeft(x.dbStart, x.dbEnd, tLen, leftOff)) st = 1; }
                 }
                 it[i].state = st;
             }
@@ -339,31 +330,23 @@ __global__ __launch_bounds__(256) void assembleBigKernel(AsmArgs a) {
             waveMemSync();
             // every lane re-scores its own deferred hits (32 residues per step), all hits of the round in parallel: a queue this long
             // defers dozens of hits per round, and a 50-150 residue overlap would leave most of a wavefront idle if the hits were
-            // taken one after the other (same arithmetic as the wide register queues of assembleGroupKernel)
+            // taken one after the other
             for (uint32_t i = lane; i < h; i += 64) {
                 Item x = it[i];
                 if (x.state != 1) continue;
                 const char *tSeq = a.s.data + seqOff(a.s, x.target);
                 const unsigned tLen = seqLen(a.s, x.target);
                 const int diag = (int) ((unsigned) x.qStart + leftOff) - x.dbStart;
-                const unsigned dist = (unsigned) abs(diag);
-                unsigned qo = 0, to = 0, len = 0; bool hit = true;
-                if (diag >= 0 && dist < querySeqLen) { qo = dist; to = 0; len = min(tLen, querySeqLen - dist); }
-                else if (diag < 0 && dist < tLen) { qo = 0; to = dist; len = min(tLen - dist, querySeqLen); }
-                else hit = false;
+                const DiagSpan sp = diagonalSpan(diag, querySeqLen, tLen);
                 unsigned first = 0, last = 0; int sc = 0, ids = 0; int startPos = -1, endPos = -1;
-                if (hit && len > 0) { scoreColumnsSerial(qs + qo, tSeq + to, len, smat, first, last, sc, ids); startPos = (int) first; endPos = (int) last; }
+                if (sp.hit && sp.len > 0) { scoreColumnsSerial(qs + sp.qo, tSeq + sp.to, sp.len, smat, first, last, sc, ids); startPos = (int) first; endPos = (int) last; }
                 const unsigned score = (unsigned) max(sc, 0);
-                nResc++; nRescRes += hit ? len : 0;
-                // updateAlignment
-                int qS, qE, dS, dE;
-                if (diag >= 0) { qS = startPos + (int) dist; qE = endPos + (int) dist; dS = startPos; dE = endPos; }
-                else { qS = startPos; qE = endPos; dS = startPos + (int) dist; dE = endPos + (int) dist; }
-                const float seqId = (float) ids / ((float) qE - (float) qS);
-                x.seqId = seqId; x.qLen = querySeqLen; x.dbLen = tLen; x.alnLength = hit ? len : 0u;
-                const float spc = (float) score / (float) ((double) x.alnLength + 0.5);
-                x.score = (int) (spc * 100);
-                x.qStart = qS; x.qEnd = qE; x.dbStart = dS; x.dbEnd = dE;
+                nResc++; nRescRes += sp.len;
+                const AlnCoords c = alnOnDiagonal(diag, startPos, endPos);                     // updateAlignment
+                const float seqId = rescoredSeqId(ids, c.qStart, c.qEnd);
+                x.seqId = seqId; x.qLen = querySeqLen; x.dbLen = tLen; x.alnLength = sp.len;
+                x.score = scorePerCol100(score, x.alnLength);
+                x.qStart = c.qStart; x.qEnd = c.qEnd; x.dbStart = c.dbStart; x.dbEnd = c.dbEnd;
                 x.state = (seqId >= a.seqIdThr) ? 0u : 2u;
                 it[i] = x;
             }
@@ -423,9 +406,6 @@ template <int CAP> __device__ __forceinline__ uint32_t qCompact(QueueLds<CAP> &q
 }
 // orders this wave's LDS accesses across its lanes (the compiler keeps them in program order; the LDS serves a wave's accesses in order)
 __device__ __forceinline__ void queueFence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-__device__ __forceinline__ unsigned long long queueKey(int score, uint32_t alnLength) {
-    return ((unsigned long long) ((uint32_t) score ^ 0x80000000u) << 32) | (unsigned long long) alnLength;
-}
 
 template <int CAP, int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void assembleQueueKernel(AsmArgs a) {
@@ -454,7 +434,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         unsigned querySeqLen = (unsigned) ((uint32_t) qOffLen & 0xFFFFFFu);
         nAln += h; nQRes += querySeqLen;
         const uint64_t t0 = a.dbgRounds ? (uint64_t) clock64() : 0; uint32_t rounds = 0;
-        // ---- queue fill (assembleresult.cpp:161-189), same arithmetic as assembleBigKernel ----
+        // ---- queue fill (assembleresult.cpp:161-189) ----
         uint32_t n = 0;
         for (uint32_t b = 0; b < h; b += 64) {
             const uint32_t i = b + (uint32_t) lane;
@@ -462,14 +442,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             if (i < h) {
                 const AlnRec r = a.recs[h0 + i];
                 x.target = r.target;
-                const int aq = (r.qStart == -1) ? 0 : r.qStart, ad = (r.dbStart == -1) ? 0 : r.dbStart;
-                const uint32_t alnLength = (uint32_t) (max(abs(r.qEnd - aq), abs(r.dbEnd - ad)) + 1);
-                const int rawScore = (int) (fma((double) r.bitScore, a.ln2, a.logK) / a.lambda + 0.5);
-                const float scorePerCol = (float) rawScore / (float) ((double) alnLength + 0.5);
-                x.key = queueKey((int) (scorePerCol * 100), alnLength);
+                const uint32_t alnLength = (uint32_t) alnLengthOf(r.qStart, r.qEnd, r.dbStart, r.dbEnd);
+                x.key = queueKey(scorePerCol100(rawScoreOfBits(r.bitScore, a.ln2, a.logK, a.lambda), alnLength), alnLength);
                 x.qStart = r.qStart; x.qEnd = r.qEnd; x.qLen = (uint32_t) r.qLen; x.dbStart = r.dbStart; x.dbEnd = r.dbEnd; x.dbLen = (uint32_t) r.dbLen;
                 keep = r.accepted != 0;                                                     // a hole of a sparse list was never queued
-                const bool branchType = ((x.dbStart == 0 && x.dbEnd != (int) x.dbLen - 1) || (x.qStart == 0 && x.qEnd != (int) x.qLen - 1)) && !(x.dbStart == 0 && x.qStart == 0);
+                const bool branchType = ((x.dbStart == 0 && x.dbEnd != (int) x.dbLen - 1) || (x.qStart == 0 && x.qEnd != (int) x.qLen - 1)) && !(x.dbStart == 0 && x.qStart == 0);      // isBranchType restated: through the call the fill loses the branch around the load below
                 x.offLen = (keep && branchType && x.target != id) ? a.s.offLen[x.target] : 0;
             }
             n += qCompact(q, n, keep, x);
@@ -484,20 +461,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             unsigned leftOff = 0, rightOff = 0;
             bool brokeOut = false;
             rounds++;
-            // ---- best right-extendable and best left-extendable hit (assembleBigKernel) ----
+            // ---- best right-extendable and best left-extendable hit ----
             unsigned long long bestR = 0, bestL = 0; uint32_t idxR = 0xFFFFFFFFu, idxL = 0xFFFFFFFFu, tgtR = 0xFFFFFFFFu, tgtL = 0xFFFFFFFFu;
             for (uint32_t i = lane; i < n; i += 64) {
                 const QItem x = qLoad(q, i);
-                const bool notBoth = !(x.dbStart == 0 && x.qStart == 0);
-                const bool rightStart = x.dbStart == 0 && (x.dbEnd != (int) x.dbLen - 1);
-                const bool leftStart = x.qStart == 0 && (x.qEnd != (int) x.qLen - 1);
-                if (!((rightStart || leftStart) && notBoth) || x.target == id) continue;
+                if (!isBranchType(x.qStart, x.qEnd, x.qLen, x.dbStart, x.dbEnd, x.dbLen) || x.target == id) continue;
                 const unsigned tLen = (uint32_t) x.offLen & 0xFFFFFFu;
                 if (x.dbStart == 0) {
-                    const unsigned fragR = tLen - ((unsigned) x.dbEnd + 1);
-                    if (fragR > 0 && (unsigned) x.qEnd == (querySeqLen - 1) && (x.key > bestR || (x.key == bestR && x.target < tgtR))) { bestR = x.key; idxR = i; tgtR = x.target; }
+                    if (canExtendRight(rightFragLen(tLen, x.dbEnd), x.qEnd, querySeqLen) && (x.key > bestR || (x.key == bestR && x.target < tgtR))) { bestR = x.key; idxR = i; tgtR = x.target; }
                 } else if (x.qStart == 0) {
-                    if (x.dbStart > 0 && (unsigned) x.dbEnd == (tLen - 1) && (x.key > bestL || (x.key == bestL && x.target < tgtL))) { bestL = x.key; idxL = i; tgtL = x.target; }
+                    if (canExtendLeft(x.dbStart, x.dbEnd, tLen) && (x.key > bestL || (x.key == bestL && x.target < tgtL))) { bestL = x.key; idxL = i; tgtL = x.target; }
                 }
             }
 #pragma unroll
@@ -546,13 +519,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
                 if (i < n) {
                     x = qLoad(q, i);
                     const bool used = (i == idxR && (rFirst || !brokeOut)) || i == idxL;
-                    const bool notBoth = !(x.dbStart == 0 && x.qStart == 0);
+                    const bool notBoth = !(x.dbStart == 0 && x.qStart == 0);      // isBranchType restated: through the call this loop tests in another order
                     const bool rightStart = x.dbStart == 0 && (x.dbEnd != (int) x.dbLen - 1);
                     const bool leftStart = x.qStart == 0 && (x.qEnd != (int) x.qLen - 1);
                     if (!used && (rightStart || leftStart) && notBoth && x.target != id) {
                         const unsigned tLen = (uint32_t) x.offLen & 0xFFFFFFu;
-                        if (x.dbStart == 0) deferred = (tLen - ((unsigned) x.dbEnd + 1)) > rightOff && (unsigned) x.qEnd == (querySeqLen - 1) && rightOff > 0;
-                        else if (x.qStart == 0) deferred = x.dbStart > (int) leftOff && (unsigned) x.dbEnd == (tLen - 1) && leftOff > 0;
+                        if (x.dbStart == 0) deferred = deferredRight(rightFragLen(tLen, x.dbEnd), x.qEnd, querySeqLen, rightOff);
+                        else if (x.qStart == 0) deferred = deferredLeft(x.dbStart, x.dbEnd, tLen, leftOff);
                     }
                 }
                 nd += qCompact(q, nd, deferred, x);
@@ -572,24 +545,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
                     const char *tSeq = a.s.data + (x.offLen >> 24);
                     const unsigned tLen = (uint32_t) x.offLen & 0xFFFFFFu;
                     const int diag = (int) ((unsigned) x.qStart + leftOff) - x.dbStart;
-                    const unsigned dist = (unsigned) abs(diag);
-                    unsigned qo = 0, to = 0, len = 0; bool hit = true;
-                    if (diag >= 0 && dist < querySeqLen) { qo = dist; to = 0; len = min(tLen, querySeqLen - dist); }
-                    else if (diag < 0 && dist < tLen) { qo = 0; to = dist; len = min(tLen - dist, querySeqLen); }
-                    else hit = false;
+                    const DiagSpan sp = diagonalSpan(diag, querySeqLen, tLen);
                     unsigned first = 0, last = 0; int sc = 0, ids = 0; int startPos = -1, endPos = -1;
-                    if (hit && len > 0) { scoreColumnsSerial(qs + qo, tSeq + to, len, smat, first, last, sc, ids); startPos = (int) first; endPos = (int) last; }
+                    if (sp.hit && sp.len > 0) { scoreColumnsSerial(qs + sp.qo, tSeq + sp.to, sp.len, smat, first, last, sc, ids); startPos = (int) first; endPos = (int) last; }
                     const unsigned score = (unsigned) max(sc, 0);
-                    nResc++; nRescRes += hit ? len : 0;
-                    // updateAlignment
-                    int qS, qE, dS, dE;
-                    if (diag >= 0) { qS = startPos + (int) dist; qE = endPos + (int) dist; dS = startPos; dE = endPos; }
-                    else { qS = startPos; qE = endPos; dS = startPos + (int) dist; dE = endPos + (int) dist; }
-                    const float seqId = (float) ids / ((float) qE - (float) qS);
-                    const uint32_t alnLength = hit ? len : 0u;
-                    const float spc = (float) score / (float) ((double) alnLength + 0.5);
-                    x.key = queueKey((int) (spc * 100), alnLength); x.qLen = querySeqLen; x.dbLen = tLen;
-                    x.qStart = qS; x.qEnd = qE; x.dbStart = dS; x.dbEnd = dE;
+                    nResc++; nRescRes += sp.len;
+                    const AlnCoords c = alnOnDiagonal(diag, startPos, endPos);                     // updateAlignment
+                    const float seqId = rescoredSeqId(ids, c.qStart, c.qEnd);
+                    x.key = queueKey(scorePerCol100(score, sp.len), sp.len); x.qLen = querySeqLen; x.dbLen = tLen;
+                    x.qStart = c.qStart; x.qEnd = c.qEnd; x.dbStart = c.dbStart; x.dbEnd = c.dbEnd;
                     keep = seqId >= a.seqIdThr;
                 }
                 nn += qCompact(q, nn, keep, x);
@@ -721,13 +685,10 @@ __device__ uint32_t heapPop(uint32_t *hp, uint32_t &n, const Item *it, NuclCmp &
 __device__ __forceinline__ Rescored rescoreOnDiagonalNucl(const char *q, unsigned qLen, const char *t, unsigned tLen, int diagonal,
                                                           const signed char *smat, bool rev) {
     Rescored r; r.startPos = -1; r.endPos = -1; r.score = 0; r.diagonalLen = 0; r.idExcl = 0;
-    const unsigned dist = (unsigned) abs(diagonal);
-    unsigned qo, to, len;
-    if (diagonal >= 0 && dist < qLen) { qo = dist; to = 0; len = min(tLen, qLen - dist); }
-    else if (diagonal < 0 && dist < tLen) { qo = 0; to = dist; len = min(tLen - dist, qLen); }
-    else return r;
+    const DiagSpan sp = diagonalSpan(diagonal, qLen, tLen);
+    const unsigned qo = sp.qo, to = sp.to, len = sp.len;
     r.diagonalLen = len;
-    if (len == 0) return r;
+    if (!sp.hit || len == 0) return r;
     auto T = [&](unsigned i) -> char { return rev ? nuclRevN(t[tLen - 1 - (to + i)]) : t[to + i]; };
     unsigned first = (q[qo] == '*' || T(0) == '*') ? 1u : 0u;
     unsigned last = len - 1;
@@ -780,20 +741,15 @@ __global__ __launch_bounds__(64) void assembleNuclKernel(AsmArgs a) {
             const AlnRec r = a.recs[h0 + i];
             Item x;
             x.target = r.target;
-            const int aq = (r.qStart == -1) ? 0 : r.qStart, ad = (r.dbStart == -1) ? 0 : r.dbStart;
-            x.alnLength = (uint32_t) (max(abs(r.qEnd - aq), abs(r.dbEnd - ad)) + 1);
-            const int rawScore = (int) (fma((double) r.bitScore, a.ln2, a.logK) / a.lambda + 0.5);
-            const float scorePerCol = (float) rawScore / (float) ((double) x.alnLength + 0.5);
+            x.alnLength = (uint32_t) alnLengthOf(r.qStart, r.qEnd, r.dbStart, r.dbEnd);
             x.seqId = r.fromText ? r.seqId : seqIdThroughText(r.seqId);
-            x.score = GUIDED ? r.bitScore : (int) (scorePerCol * 100);
+            x.score = GUIDED ? r.bitScore : scorePerCol100(rawScoreOfBits(r.bitScore, a.ln2, a.logK, a.lambda), x.alnLength);
             x.qStart = r.qStart; x.qEnd = r.qEnd; x.qLen = (uint32_t) r.qLen; x.dbStart = r.dbStart; x.dbEnd = r.dbEnd; x.dbLen = (uint32_t) r.dbLen;
             x.pad = 0;
             if (!GUIDED && x.qStart > x.qEnd) {
                 x.pad = 1;
-                const int t0 = x.qStart; x.qStart = x.qEnd; x.qEnd = t0;
-                const unsigned dbs = (unsigned) x.dbStart;
-                x.dbStart = (int) (x.dbLen - (unsigned) x.dbEnd - 1);
-                x.dbEnd = (int) (x.dbLen - dbs - 1);
+                const AlnCoords m = mirrorReverseHit(x.qStart, x.qEnd, x.dbStart, x.dbEnd, x.dbLen);
+                x.qStart = m.qStart; x.qEnd = m.qEnd; x.dbStart = m.dbStart; x.dbEnd = m.dbEnd;
             }
             x.state = (!r.accepted || (GUIDED && x.seqId < a.seqIdThr)) ? 2u : 0u;     // a hole of a sparse list; guided: re-evaluated on the nucleotide level, never queued
             it[i] = x;
@@ -838,16 +794,13 @@ __global__ __launch_bounds__(64) void assembleNuclKernel(AsmArgs a) {
                 const uint32_t bi = sPop;
                 const Item best = it[bi];
                 __syncthreads();
-                const bool notBoth = !(best.dbStart == 0 && best.qStart == 0);
-                const bool rightStart = best.dbStart == 0 && (best.dbEnd != (int) best.dbLen - 1);
-                const bool leftStart = best.qStart == 0 && (best.qEnd != (int) best.qLen - 1);
-                if (!((rightStart || leftStart) && notBoth && best.target != id)) continue;
+                if (!(isBranchType(best.qStart, best.qEnd, best.qLen, best.dbStart, best.dbEnd, best.dbLen) && best.target != id)) continue;
                 const char *tSeq = a.s.data + seqOff(a.s, best.target);
                 const unsigned tLen = seqLen(a.s, best.target);
                 const bool rev = best.pad != 0;
                 const char *aaT = nullptr; unsigned aaTLen = 0;
                 if (GUIDED) { aaT = a.aa.data + a.aa.off[best.target]; aaTLen = a.aa.len[best.target]; }
-                if (best.dbStart == 0) { if ((tLen - ((unsigned) best.dbEnd + 1)) <= rightOff || (GUIDED && (exclR || aaT[0] == '*'))) continue; }
+                if (best.dbStart == 0) { if (rightFragLen(tLen, best.dbEnd) <= rightOff || (GUIDED && (exclR || aaT[0] == '*'))) continue; }
                 else if (best.qStart == 0) { if (best.dbStart <= (int) leftOff || (GUIDED && (exclL || aaT[aaTLen - 1] == '*'))) continue; }
                 const unsigned dbStart = (unsigned) best.dbStart, dbEnd = (unsigned) best.dbEnd, qStart = (unsigned) best.qStart, qEnd = (unsigned) best.qEnd;
                 if (dbStart == 0 && qEnd == (querySeqLen - 1)) {            // right extension
@@ -899,15 +852,11 @@ __global__ __launch_bounds__(64) void assembleNuclKernel(AsmArgs a) {
                 const int diag = (int) ((unsigned) x.qStart + leftOff) - x.dbStart;
                 const Rescored rs = rescoreOnDiagonalNucl(qs, querySeqLen, tSeq, tLen, diag, smat, x.pad != 0);
                 qResc++; qRescRes += rs.diagonalLen;
-                const int dist = abs(diag);
-                int qS, qE, dS, dE;
-                if (diag >= 0) { qS = rs.startPos + dist; qE = rs.endPos + dist; dS = rs.startPos; dE = rs.endPos; }
-                else { qS = rs.startPos; qE = rs.endPos; dS = rs.startPos + dist; dE = rs.endPos + dist; }
-                const float seqId = (float) rs.idExcl / ((float) qE - (float) qS);
+                const AlnCoords c = alnOnDiagonal(diag, rs.startPos, rs.endPos);
+                const float seqId = rescoredSeqId(rs.idExcl, c.qStart, c.qEnd);
                 x.seqId = seqId; x.qLen = querySeqLen; x.dbLen = tLen; x.alnLength = rs.diagonalLen;
-                const float spc = (float) rs.score / (float) ((double) x.alnLength + 0.5);
-                x.score = (int) (spc * 100);
-                x.qStart = qS; x.qEnd = qE; x.dbStart = dS; x.dbEnd = dE;
+                x.score = scorePerCol100(rs.score, x.alnLength);
+                x.qStart = c.qStart; x.qEnd = c.qEnd; x.dbStart = c.dbStart; x.dbEnd = c.dbEnd;
                 const bool requeue = seqId >= a.seqIdThr;
                 __syncthreads();
                 if (lane == 0) { it[found] = x; if (requeue) { uint32_t n2 = nHeap; heapPush(hp, n2, found, it, cmp); if (cmp.abort) sAbort = 1; } }
@@ -1041,20 +990,15 @@ __global__ __launch_bounds__(NT_BLOCK, 4) void assembleNuclThreadKernel(AsmArgs 
             const AlnRec r = a.recs[h0 + i];
             Item x;
             x.target = r.target;
-            const int aq = (r.qStart == -1) ? 0 : r.qStart, ad = (r.dbStart == -1) ? 0 : r.dbStart;
-            x.alnLength = (uint32_t) (max(abs(r.qEnd - aq), abs(r.dbEnd - ad)) + 1);
-            const int rawScore = (int) (fma((double) r.bitScore, a.ln2, a.logK) / a.lambda + 0.5);
-            const float scorePerCol = (float) rawScore / (float) ((double) x.alnLength + 0.5);
+            x.alnLength = (uint32_t) alnLengthOf(r.qStart, r.qEnd, r.dbStart, r.dbEnd);
             x.seqId = r.fromText ? r.seqId : seqIdThroughText(r.seqId);
-            x.score = GUIDED ? r.bitScore : (int) (scorePerCol * 100);
+            x.score = GUIDED ? r.bitScore : scorePerCol100(rawScoreOfBits(r.bitScore, a.ln2, a.logK, a.lambda), x.alnLength);
             x.qStart = r.qStart; x.qEnd = r.qEnd; x.qLen = (uint32_t) r.qLen; x.dbStart = r.dbStart; x.dbEnd = r.dbEnd; x.dbLen = (uint32_t) r.dbLen;
             x.pad = 0;
             if (!GUIDED && x.qStart > x.qEnd) {
                 x.pad = 1;
-                const int t0 = x.qStart; x.qStart = x.qEnd; x.qEnd = t0;
-                const unsigned dbs = (unsigned) x.dbStart;
-                x.dbStart = (int) (x.dbLen - (unsigned) x.dbEnd - 1);
-                x.dbEnd = (int) (x.dbLen - dbs - 1);
+                const AlnCoords m = mirrorReverseHit(x.qStart, x.qEnd, x.dbStart, x.dbEnd, x.dbLen);
+                x.qStart = m.qStart; x.qEnd = m.qEnd; x.dbStart = m.dbStart; x.dbEnd = m.dbEnd;
             }
             x.state = (!r.accepted || (GUIDED && x.seqId < a.seqIdThr)) ? 2u : 0u;
             it[i] = x;
@@ -1088,16 +1032,13 @@ __global__ __launch_bounds__(NT_BLOCK, 4) void assembleNuclThreadKernel(AsmArgs 
                     const uint32_t bi = heapPop(hp, nHeap, it, cmp);
                     if (cmp.abort) break;
                     const Item best = it[bi];
-                    const bool notBoth = !(best.dbStart == 0 && best.qStart == 0);
-                    const bool rightStart = best.dbStart == 0 && (best.dbEnd != (int) best.dbLen - 1);
-                    const bool leftStart = best.qStart == 0 && (best.qEnd != (int) best.qLen - 1);
-                    if (!((rightStart || leftStart) && notBoth && best.target != id)) continue;
+                    if (!(isBranchType(best.qStart, best.qEnd, best.qLen, best.dbStart, best.dbEnd, best.dbLen) && best.target != id)) continue;
                     const char *tSeq = a.s.data + seqOff(a.s, best.target);
                     const unsigned tLen = seqLen(a.s, best.target);
                     const bool rev = best.pad != 0;
                     const char *aaT = nullptr; unsigned aaTLen = 0;
                     if (GUIDED) { aaT = a.aa.data + a.aa.off[best.target]; aaTLen = a.aa.len[best.target]; }
-                    if (best.dbStart == 0) { if ((tLen - ((unsigned) best.dbEnd + 1)) <= rightOff || (GUIDED && (exclR || aaT[0] == '*'))) continue; }
+                    if (best.dbStart == 0) { if (rightFragLen(tLen, best.dbEnd) <= rightOff || (GUIDED && (exclR || aaT[0] == '*'))) continue; }
                     else if (best.qStart == 0) { if (best.dbStart <= (int) leftOff || (GUIDED && (exclL || aaT[aaTLen - 1] == '*'))) continue; }
                     const unsigned dbStart = (unsigned) best.dbStart, dbEnd = (unsigned) best.dbEnd, qStart = (unsigned) best.qStart, qEnd = (unsigned) best.qEnd;
                     if (dbStart == 0 && qEnd == (querySeqLen - 1)) {            // right extension
@@ -1157,25 +1098,21 @@ __global__ __launch_bounds__(NT_BLOCK, 4) void assembleNuclThreadKernel(AsmArgs 
             for (uint32_t d = 0; d < maxDef; d++) {
                 const bool mine = d < myDef && !cmp.abort;
                 uint32_t found = 0; Item x; memset(&x, 0, sizeof(x));
-                const char *tSeq = nullptr; unsigned tLen = 0, qo = 0, to = 0, len = 0, dist = 0; int diag = 0; bool hit = false;
+                const char *tSeq = nullptr; unsigned tLen = 0; int diag = 0; DiagSpan sp;
                 if (mine) {
                     found = def[d];
                     x = it[found];
                     tSeq = a.s.data + seqOff(a.s, x.target);
                     tLen = seqLen(a.s, x.target);
                     diag = (int) ((unsigned) x.qStart + leftOff) - x.dbStart;
-                    dist = (unsigned) abs(diag);
-                    hit = true;
-                    if (diag >= 0 && dist < querySeqLen) { qo = dist; to = 0; len = min(tLen, querySeqLen - dist); }
-                    else if (diag < 0 && dist < tLen) { qo = 0; to = dist; len = min(tLen - dist, querySeqLen); }
-                    else hit = false;
+                    sp = diagonalSpan(diag, querySeqLen, tLen);
                 }
                 int startPos = -1, endPos = -1, sc = 0, ids = 0;
-                unsigned long long m = __ballot(mine && hit && len > 0);
+                unsigned long long m = __ballot(mine && sp.hit && sp.len > 0);
                 while (m) {
                     const int j = __ffsll((long long) m) - 1; m &= m - 1;
-                    const char *jq = bcast(qs + qo, j); const char *jt = bcast(tSeq, j);
-                    const unsigned jTo = bcast(to, j), jLen = bcast(len, j), jTLen = bcast(tLen, j), jRev = bcast((unsigned) x.pad, j);
+                    const char *jq = bcast(qs + sp.qo, j); const char *jt = bcast(tSeq, j);
+                    const unsigned jTo = bcast(sp.to, j), jLen = bcast(sp.len, j), jTLen = bcast(tLen, j), jRev = bcast((unsigned) x.pad, j);
                     unsigned first = 0, last = 0; int s = 0, idn = 0;
                     if (jRev) scoreColumnsRevWave(jq, jt, jTLen - 1 - jTo, jLen, smat, sComp, lane, first, last, s, idn);
                     else scoreColumnsG<64>(jq, jt + jTo, jLen, smat, lane, first, last, s, idn);
@@ -1184,15 +1121,12 @@ __global__ __launch_bounds__(NT_BLOCK, 4) void assembleNuclThreadKernel(AsmArgs 
                 }
                 if (mine) {
                     const unsigned score = (unsigned) max(sc, 0);
-                    qResc++; qRescRes += hit ? len : 0;
-                    int qS, qE, dS, dE;
-                    if (diag >= 0) { qS = startPos + (int) dist; qE = endPos + (int) dist; dS = startPos; dE = endPos; }
-                    else { qS = startPos; qE = endPos; dS = startPos + (int) dist; dE = endPos + (int) dist; }
-                    const float seqId = (float) ids / ((float) qE - (float) qS);
-                    x.seqId = seqId; x.qLen = querySeqLen; x.dbLen = tLen; x.alnLength = hit ? len : 0u;
-                    const float spc = (float) score / (float) ((double) x.alnLength + 0.5);
-                    x.score = (int) (spc * 100);
-                    x.qStart = qS; x.qEnd = qE; x.dbStart = dS; x.dbEnd = dE;
+                    qResc++; qRescRes += sp.len;
+                    const AlnCoords c = alnOnDiagonal(diag, startPos, endPos);
+                    const float seqId = rescoredSeqId(ids, c.qStart, c.qEnd);
+                    x.seqId = seqId; x.qLen = querySeqLen; x.dbLen = tLen; x.alnLength = sp.len;
+                    x.score = scorePerCol100(score, x.alnLength);
+                    x.qStart = c.qStart; x.qEnd = c.qEnd; x.dbStart = c.dbStart; x.dbEnd = c.dbEnd;
                     it[found] = x;
                     if (seqId >= a.seqIdThr) heapPush(hp, nHeap, found, it, cmp);
                 }
@@ -1253,7 +1187,7 @@ template <int G>
 __device__ __forceinline__ Rescored rescoreOnDiagonalG(const char *q, unsigned qLen, const char *t, unsigned tLen, int diagonal,
                                                        const signed char *smat, int gl) {
     Rescored r; r.startPos = -1; r.endPos = -1; r.score = 0; r.diagonalLen = 0; r.idExcl = 0;
-    const unsigned dist = (unsigned) abs(diagonal);
+    const unsigned dist = (unsigned) abs(diagonal);       // diagonalSpan restated: through the call assembleGroupKernel<32> gains seven spill stores and 4 % of its time
     unsigned qo, to, len;
     if (diagonal >= 0 && dist < qLen) { qo = dist; to = 0; len = min(tLen, qLen - dist); }
     else if (diagonal < 0 && dist < tLen) { qo = 0; to = dist; len = min(tLen - dist, qLen); }
@@ -1310,11 +1244,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         if ((uint32_t) gl < h) {
             const AlnRec r = a.recs[h0 + gl];
             xTarget = r.target;
-            const int aq = (r.qStart == -1) ? 0 : r.qStart, ad = (r.dbStart == -1) ? 0 : r.dbStart;
-            xAlnLen = (uint32_t) (max(abs(r.qEnd - aq), abs(r.dbEnd - ad)) + 1);
-            const int rawScore = (int) (fma((double) r.bitScore, a.ln2, a.logK) / a.lambda + 0.5);
-            const float scorePerCol = (float) rawScore / (float) ((double) xAlnLen + 0.5);
-            xScore = (int) (scorePerCol * 100);
+            xAlnLen = (uint32_t) alnLengthOf(r.qStart, r.qEnd, r.dbStart, r.dbEnd);
+            xScore = scorePerCol100(rawScoreOfBits(r.bitScore, a.ln2, a.logK, a.lambda), xAlnLen);
             xQStart = r.qStart; xQEnd = r.qEnd; xQLen = (uint32_t) r.qLen; xDbStart = r.dbStart; xDbEnd = r.dbEnd; xDbLen = (uint32_t) r.dbLen;
             // the self alignment is popped and discarded without any effect (selectFragmentToExtend: isNotIdentity):
             // it never enters the register queue
@@ -1322,7 +1253,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             // offset / length of the target, fetched up front (one memory round trip less per pop) — for the hits that can take one of the
             // two extension branches at all: the geometry tests below read them for nobody else, and a re-scored hit came through a branch
             // (round 5: a random 128-byte line of metadata per hit that is popped and dropped in its first round)
-            const bool branchType = ((xDbStart == 0 && xDbEnd != (int) xDbLen - 1) || (xQStart == 0 && xQEnd != (int) xQLen - 1)) && !(xDbStart == 0 && xQStart == 0);
+            const bool branchType = ((xDbStart == 0 && xDbEnd != (int) xDbLen - 1) || (xQStart == 0 && xQEnd != (int) xQLen - 1)) && !(xDbStart == 0 && xQStart == 0);      // isBranchType restated, for the same reason as in assembleQueueKernel's fill
             if (xState == 0 && branchType) { xTOff = seqOff(a.s, xTarget); xTLen = seqLen(a.s, xTarget); }
         }
         // tie-break of CompareResultByScore (smaller key wins) as a rank among the group's targets
@@ -1349,12 +1280,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             unsigned fragR = 0;
             if (xState == 0) {
                 key = ((unsigned long long) ((uint32_t) xScore ^ 0x80000000u) << 32) | ((unsigned long long) xAlnLen << 6) | (unsigned long long) (63u - tRank);
-                const bool notBoth = !(xDbStart == 0 && xQStart == 0);
-                const bool rightStart = xDbStart == 0 && (xDbEnd != (int) xDbLen - 1);
-                const bool leftStart = xQStart == 0 && (xQEnd != (int) xQLen - 1);
-                if ((rightStart || leftStart) && notBoth) {
-                    if (xDbStart == 0) { rBranch = true; fragR = xTLen - ((unsigned) xDbEnd + 1); rType = fragR > 0 && (unsigned) xQEnd == (querySeqLen - 1); }
-                    else if (xQStart == 0) { lBranch = true; lType = xDbStart > 0 && (unsigned) xDbEnd == (xTLen - 1); }
+                if (isBranchType(xQStart, xQEnd, xQLen, xDbStart, xDbEnd, xDbLen)) {
+                    if (xDbStart == 0) { rBranch = true; fragR = rightFragLen(xTLen, xDbEnd); rType = canExtendRight(fragR, xQEnd, querySeqLen); }
+                    else if (xQStart == 0) { lBranch = true; lType = canExtendLeft(xDbStart, xDbEnd, xTLen); }
                 }
             }
             const unsigned long long bestR = groupMax<G>(rType ? key : 0ULL), bestL = groupMax<G>(lType ? key : 0ULL);
@@ -1388,8 +1316,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             if (xState == 0 && (!brokeOut || key >= bestL)) {       // at the length cap the hits ranked below the left hit stay queued
                 uint32_t st = 2;
                 if (!(isR && (rFirst || !brokeOut)) && !isL) {
-                    if (rBranch) { if (fragR > rightOff && (unsigned) xQEnd == (querySeqLen - 1) && rightOff > 0) st = 1; }
-                    else if (lBranch) { if (xDbStart > (int) leftOff && (unsigned) xDbEnd == (xTLen - 1) && leftOff > 0) st = 1; }
+                    if (rBranch) { if (deferredRight(fragR, xQEnd, querySeqLen, rightOff)) st = 1; }
+                    else if (lBranch) { if (deferredLeft(xDbStart, xDbEnd, xTLen, leftOff)) st = 1; }
                 }
                 xState = st;
             }
@@ -1408,23 +1336,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
                 if (xState == 1) {
                     const char *tSeq = a.s.data + xTOff;
                     const int diag = (int) ((unsigned) xQStart + leftOff) - xDbStart;
-                    const unsigned dist = (unsigned) abs(diag);
-                    unsigned qo = 0, to = 0, len = 0; bool hit = true;
-                    if (diag >= 0 && dist < querySeqLen) { qo = dist; to = 0; len = min(xTLen, querySeqLen - dist); }
-                    else if (diag < 0 && dist < xTLen) { qo = 0; to = dist; len = min(xTLen - dist, querySeqLen); }
-                    else hit = false;
+                    const DiagSpan sp = diagonalSpan(diag, querySeqLen, xTLen);
                     unsigned first = 0, last = 0; int sc = 0, ids = 0; int startPos = -1, endPos = -1;
-                    if (hit && len > 0) { scoreColumnsSerial(qs + qo, tSeq + to, len, smat, first, last, sc, ids); startPos = (int) first; endPos = (int) last; }
+                    if (sp.hit && sp.len > 0) { scoreColumnsSerial(qs + sp.qo, tSeq + sp.to, sp.len, smat, first, last, sc, ids); startPos = (int) first; endPos = (int) last; }
                     const unsigned score = (unsigned) max(sc, 0);
-                    nResc += 1; nRescRes += hit ? len : 0;
-                    int qS, qE, dS, dE;
-                    if (diag >= 0) { qS = startPos + (int) dist; qE = endPos + (int) dist; dS = startPos; dE = endPos; }
-                    else { qS = startPos; qE = endPos; dS = startPos + (int) dist; dE = endPos + (int) dist; }
-                    const float seqId = (float) ids / ((float) qE - (float) qS);
-                    const float spc = (float) score / (float) ((double) (hit ? len : 0u) + 0.5);
-                    xQLen = querySeqLen; xDbLen = xTLen; xAlnLen = hit ? len : 0u; xScore = (int) (spc * 100);
-                    xQStart = qS; xQEnd = qE; xDbStart = dS; xDbEnd = dE;
-                    xState = (seqId >= a.seqIdThr) ? 0u : 2u;
+                    nResc += 1; nRescRes += sp.len;
+                    const AlnCoords c = alnOnDiagonal(diag, startPos, endPos);
+                    xQLen = querySeqLen; xDbLen = xTLen; xAlnLen = sp.len; xScore = scorePerCol100(score, sp.len);
+                    xQStart = c.qStart; xQEnd = c.qEnd; xDbStart = c.dbStart; xDbEnd = c.dbEnd;
+                    xState = (rescoredSeqId(ids, c.qStart, c.qEnd) >= a.seqIdThr) ? 0u : 2u;
                 }
                 deferred = 0;
             }
@@ -1437,15 +1357,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
                 const int diag = (int) ((unsigned) dqs + leftOff) - dds;
                 const Rescored rs = rescoreOnDiagonalG<G>(qs, querySeqLen, tSeq, tLen, diag, smat, gl);
                 nResc += (gl == 0); nRescRes += (gl == 0) ? rs.diagonalLen : 0;
-                const int dist = abs(diag);
-                int qS, qE, dS, dE;
-                if (diag >= 0) { qS = rs.startPos + dist; qE = rs.endPos + dist; dS = rs.startPos; dE = rs.endPos; }
-                else { qS = rs.startPos; qE = rs.endPos; dS = rs.startPos + dist; dE = rs.endPos + dist; }
-                const float seqId = (float) rs.idExcl / ((float) qE - (float) qS);
-                const float spc = (float) rs.score / (float) ((double) rs.diagonalLen + 0.5);
+                const AlnCoords c = alnOnDiagonal(diag, rs.startPos, rs.endPos);
+                const float seqId = rescoredSeqId(rs.idExcl, c.qStart, c.qEnd);
                 if (gl == dl) {
-                    xQLen = querySeqLen; xDbLen = tLen; xAlnLen = rs.diagonalLen; xScore = (int) (spc * 100);
-                    xQStart = qS; xQEnd = qE; xDbStart = dS; xDbEnd = dE;
+                    xQLen = querySeqLen; xDbLen = tLen; xAlnLen = rs.diagonalLen; xScore = scorePerCol100(rs.score, rs.diagonalLen);
+                    xQStart = c.qStart; xQEnd = c.qEnd; xDbStart = c.dbStart; xDbEnd = c.dbEnd;
                     xState = (seqId >= a.seqIdThr) ? 0u : 2u;
                 }
             }
@@ -1480,14 +1396,11 @@ __global__ __launch_bounds__(256) void arenaSumKernel(const AlnRec *__restrict__
             // exact pre-screen: the first extension of a query is decided by coordinates the alignment already
             // carries (selectFragmentToExtend + the two geometry tests, assembleresult.cpp:40-57,211-263); if no
             // alignment can start an extension the greedy loop drains its queue without changing anything.
-            int qS = r.qStart, qE = r.qEnd, dS = r.dbStart, dE = r.dbEnd;
-            if (mirror && qS > qE) { qS = r.qEnd; qE = r.qStart; dS = r.dbLen - r.dbEnd - 1; dE = r.dbLen - r.dbStart - 1; }
-            const bool notBoth = !(dS == 0 && qS == 0);
-            const bool rightStart = dS == 0 && (dE != r.dbLen - 1);
-            const bool leftStart = qS == 0 && (qE != r.qLen - 1);
-            if ((rightStart || leftStart) && notBoth) {
-                if (dS == 0) can = (qE == r.qLen - 1) && (r.dbLen - (dE + 1) > 0);
-                else if (qS == 0) can = (dE == r.dbLen - 1) && (dS > 0) && ((uint64_t) r.qLen + (uint64_t) dS < maxSeqLen);
+            AlnCoords c; c.qStart = r.qStart; c.qEnd = r.qEnd; c.dbStart = r.dbStart; c.dbEnd = r.dbEnd;
+            if (mirror && c.qStart > c.qEnd) c = mirrorReverseHit(r.qStart, r.qEnd, r.dbStart, r.dbEnd, (unsigned) r.dbLen);
+            if (isBranchType(c.qStart, c.qEnd, (unsigned) r.qLen, c.dbStart, c.dbEnd, (unsigned) r.dbLen)) {
+                if (c.dbStart == 0) can = canExtendRight(rightFragLen((unsigned) r.dbLen, c.dbEnd), c.qEnd, (unsigned) r.qLen);      // unsigned on purpose, as the kernels test it
+                else if (c.qStart == 0) can = canExtendLeft(c.dbStart, c.dbEnd, (unsigned) r.dbLen) && ((uint64_t) r.qLen + (uint64_t) c.dbStart < maxSeqLen);
             }
         }
         // (the lanes of a wavefront leave the loop together except in its last round, where the active ones are the low lanes)

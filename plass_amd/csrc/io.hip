@@ -4,6 +4,7 @@
 //   seqId text       truncated to 3 decimals, 1.0 printed as "1.00" (Util.cpp:278-307 + Matcher.cpp:329-330)
 #include "common.hpp"
 #include "host_util.hpp"
+#include "asm_rules.hpp"
 #include <algorithm>
 #include <atomic>
 #include <memory>
@@ -298,8 +299,7 @@ extern "C" int plasship_alns_read(plasship_ctx *ctx, const plasship_seqdb *db, c
             r.query = (uint32_t) q; r.target = (uint32_t) tid; r.bitScore = atoi(f[1]); r.rawScore = -1;
             r.seqId = (float) strtod(f[2], nullptr);
             r.qStart = atoi(f[4]); r.qEnd = atoi(f[5]); r.qLen = atoi(f[6]); r.dbStart = atoi(f[7]); r.dbEnd = atoi(f[8]); r.dbLen = atoi(f[9]);
-            int aq = r.qStart == -1 ? 0 : r.qStart, ad = r.dbStart == -1 ? 0 : r.dbStart;
-            r.alnLen = std::max(std::abs(r.qEnd - aq), std::abs(r.dbEnd - ad)) + 1;          // Matcher::computeAlnLength
+            r.alnLen = alnLengthOf(r.qStart, r.qEnd, r.dbStart, r.dbEnd);
             r.reversed = 0; r.accepted = 1; r.fromText = 1;
             if (nf >= 11) {     // backtrace column: "<alnLen>M" is what rescorediagonal -a 1 writes (DistanceCalculator: ungapped)
                 const char *b = f[10]; long v = 0; bool digits = false;

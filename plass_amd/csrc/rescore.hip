@@ -21,6 +21,7 @@
 #include "device_utils.hpp"
 #include "host_util.hpp"
 #include "ref_rules.hpp"
+#include "asm_rules.hpp"
 #include <algorithm>
 #include <memory>
 #include <cfloat>
@@ -72,11 +73,9 @@ template <bool REV, int G>
 __device__ __forceinline__ DiagScore scoreDiagonal(const char *__restrict__ q, unsigned qLen, const char *__restrict__ t,
                                                    unsigned tLen, int diagonal, const signed char *__restrict__ smat, const unsigned char *__restrict__ comp, int sl) {
     DiagScore r; r.valid = false; r.score = 0; r.first = -1; r.last = -1; r.diagLen = 0; r.idCnt = 0;
-    const unsigned dist = (unsigned) abs(diagonal);
-    unsigned qo, to, len;
-    if (diagonal >= 0 && dist < qLen) { qo = dist; to = 0; len = min(tLen, qLen - dist); }
-    else if (diagonal < 0 && dist < tLen) { qo = 0; to = dist; len = min(tLen - dist, qLen); }
-    else return r;
+    const DiagSpan sp = diagonalSpan(diagonal, qLen, tLen);
+    if (!sp.hit) return r;
+    const unsigned qo = sp.qo, to = sp.to, len = sp.len;
     r.valid = true; r.diagLen = len;
     if (len == 0) { r.first = 0; r.last = -1; return r; }   // empty sequence: reference reads out of bounds; unsupported
     // REV: the aligned query is the reverse complement of the stored one: qrev[i] = comp(q[qLen-1-i])

@@ -282,6 +282,106 @@ extern "C" double sweep(long n, long *classDiff) {
     assert worst < 0.25, "the two routes differ by %.2f of the band" % worst
 
 
+def test_asm_rules_agree_with_the_reference_lines(tmp_path):
+    """plass_amd/csrc/asm_rules.hpp: the per-alignment rules the extension kernels share, compiled with g++ as the kernels' build compiles them
+    (-ffp-contract=off).  Every expected value below is worked out by hand from the reference line the rule cites, none by a second copy of
+    the rule."""
+    import subprocess, ctypes, tarfile, math
+    src = tmp_path / "r.cpp"
+    src.write_text(r'''
+#include "asm_rules.hpp"
+using namespace plasship;
+extern "C" {
+int aln_len(int qs, int qe, int ds, int de) { return alnLengthOf(qs, qe, ds, de); }
+int raw_of_bits(int bits, double ln2, double logK, double lambda) { return rawScoreOfBits(bits, ln2, logK, lambda); }
+int spc_i(int score, unsigned alnLen) { return scorePerCol100(score, alnLen); }
+int spc_u(unsigned score, unsigned alnLen) { return scorePerCol100(score, alnLen); }
+void span(int diag, unsigned qLen, unsigned tLen, unsigned *o) { const DiagSpan s = diagonalSpan(diag, qLen, tLen); o[0] = s.hit; o[1] = s.qo; o[2] = s.to; o[3] = s.len; }
+void on_diag(int diag, int sp, int ep, int *o) { const AlnCoords c = alnOnDiagonal(diag, sp, ep); o[0] = c.qStart; o[1] = c.qEnd; o[2] = c.dbStart; o[3] = c.dbEnd; }
+float seq_id(int ids, int qs, int qe) { return rescoredSeqId(ids, qs, qe); }
+int kept(int ids, int qs, int qe, float thr) { return rescoredSeqId(ids, qs, qe) >= thr; }
+int branch_type(int qs, int qe, unsigned ql, int ds, int de, unsigned dl) { return isBranchType(qs, qe, ql, ds, de, dl); }
+unsigned right_frag(unsigned tLen, int de) { return rightFragLen(tLen, de); }
+int can_right(unsigned fragR, int qe, unsigned ql) { return canExtendRight(fragR, qe, ql); }
+int can_left(int ds, int de, unsigned tLen) { return canExtendLeft(ds, de, tLen); }
+int defer_right(unsigned fragR, int qe, unsigned ql, unsigned rightOff) { return deferredRight(fragR, qe, ql, rightOff); }
+int defer_left(int ds, int de, unsigned tLen, unsigned leftOff) { return deferredLeft(ds, de, tLen, leftOff); }
+void mirror(int qs, int qe, int ds, int de, unsigned dl, int *o) { const AlnCoords c = mirrorReverseHit(qs, qe, ds, de, dl); o[0] = c.qStart; o[1] = c.qEnd; o[2] = c.dbStart; o[3] = c.dbEnd; }
+}
+''')
+    so = tmp_path / "r.so"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "plass_amd", "csrc"), str(src), "-o", str(so)])
+    lib = ctypes.CDLL(str(so))
+    lib.raw_of_bits.argtypes = [ctypes.c_int] + [ctypes.c_double] * 3
+    lib.seq_id.restype = ctypes.c_float
+    lib.kept.argtypes = [ctypes.c_int] * 3 + [ctypes.c_float]
+    lib.right_frag.restype = ctypes.c_uint
+
+    def four(f, ctype, *args):
+        o = (ctype * 4)()
+        f(*args, o)
+        return tuple(o)
+
+    # Matcher.cpp:272-276 + 201-203: max(|qEnd - qStart|, |dbEnd - dbStart|) + 1 with a start of -1 counted as 0 (unclamped: 11 twice)
+    assert lib.aln_len(-1, 9, 0, 5) == 10 and lib.aln_len(0, 5, -1, 9) == 10
+    assert lib.aln_len(0, 49, 0, 49) == 50 and lib.aln_len(20, 49, 0, 29) == 30 and lib.aln_len(2, 9, 3, 20) == 18
+    # DistanceCalculator.h:119-125,148-150 on a query of 50 and a target of 30: (hit, query offset, target offset, columns)
+    for diag, qLen, tLen, want in ((49, 50, 30, (1, 49, 0, 1)),         # diag = qLen - 1: one column
+                                   (50, 50, 30, (0, 0, 0, 0)),          # diag = qLen: none
+                                   (-29, 50, 30, (1, 0, 29, 1)),        # diag = -(tLen - 1): one column
+                                   (-30, 50, 30, (0, 0, 0, 0)),         # diag = -tLen: none
+                                   (5, 50, 10, (1, 5, 0, 10)),          # tLen < qLen - dist: the target ends first
+                                   (5, 50, 45, (1, 5, 0, 45)), (5, 50, 46, (1, 5, 0, 45)),
+                                   (-4, 8, 30, (1, 0, 4, 8)),           # the query ends first
+                                   (0, 50, 30, (1, 0, 0, 30)),
+                                   (3, 50, 0, (1, 3, 0, 0)), (0, 50, 0, (1, 0, 0, 0)),      # tLen == 0: a hit of length 0 ...
+                                   (-1, 50, 0, (0, 0, 0, 0))):                               # ... but 1 < 0 is none
+        assert four(lib.span, ctypes.c_uint, diag, qLen, tLen) == want, (diag, qLen, tLen)
+    # assembleresult.cpp:73-87: (qStart, qEnd, dbStart, dbEnd)
+    assert four(lib.on_diag, ctypes.c_int, 5, 1, 20) == (6, 25, 1, 20)
+    assert four(lib.on_diag, ctypes.c_int, -5, 1, 20) == (1, 20, 6, 25)
+    assert four(lib.on_diag, ctypes.c_int, 0, 0, 9) == (0, 9, 0, 9)
+    assert four(lib.on_diag, ctypes.c_int, 7, -1, -1) == (6, 6, -1, -1) and four(lib.on_diag, ctypes.c_int, -7, -1, -1) == (-1, -1, 6, 6)
+    # assembleresult.cpp:93,311: identities over [qStart, qEnd) by qEnd - qStart in float; 0 / 0 is NaN and passes no threshold
+    assert lib.seq_id(19, 6, 25) == 1.0 and lib.seq_id(9, 0, 10) == 0.89999997615814208984375     # 15099494 / 2^24, the float next to 0.9
+    assert math.isnan(lib.seq_id(0, 6, 6)) and lib.kept(0, 6, 6, 0.0) == 0 and lib.kept(0, 6, 6, -1.0) == 0
+    assert lib.kept(9, 0, 10, 0.9) == 1 and lib.kept(8, 0, 10, 0.9) == 0
+    # assembleresult.cpp:100-101,164,169: (int) ((float) score / (float) (alnLen + 0.5) * 100)
+    assert lib.spc_u(0, 0) == 0 and lib.spc_u(5, 0) == 1000 and lib.spc_i(0, 0) == 0            # alnLen == 0: score / 0.5
+    assert lib.spc_i(139, 30) == 455 and lib.spc_u(250, 50) == 495 and lib.spc_i(-3, 1) == -200  # 4.5573.., 4.9504.., -2
+    # assembleresult.cpp:163 on the second record of query 0 of the reference's alignment DB (target 4025, 67 bits): (ln K + 67 ln 2) / lambda
+    # = (-1.97295 + 46.44086) / 0.320738 = 138.64, + 0.5 truncated = 139 — the raw score whose bit score is (lambda 139 - ln K) / ln 2 = 67.2;
+    # lambda and K of the reference's ungapped protein statistics (oracle/ref_tables.h), pinned by the oracle's known answers
+    with tarfile.open(os.path.join(ROOT, "tests", "golden", "example_aa.tar.gz")) as t:
+        rec = t.extractfile("aa/aln_0").read().split(b"\n")[1].split(b"\t")
+    assert (int(rec[0]), int(rec[1])) == (4025, 67)
+    lam, K = 0.32073781526040424, 0.13904657125294345
+    assert lib.raw_of_bits(int(rec[1]), math.log(2.0), math.log(K), lam) == 139
+    import __graft_entry__ as g
+    g.oracle_bin()
+    ora = ctypes.CDLL(os.path.join(ROOT, "oracle", "build", "liboracle.so"))
+    ora.oracle_raw_from_bit.restype = ctypes.c_double; ora.oracle_raw_from_bit.argtypes = [ctypes.c_int, ctypes.c_double]
+    assert int(ora.oracle_raw_from_bit(0, 67.0) + 0.5) == 139
+    # assembleresult.cpp:47-52 (qStart, qEnd, qLen, dbStart, dbEnd, dbLen), query of 50 and target of 40
+    assert lib.branch_type(20, 49, 50, 0, 29, 40) == 1          # starts the target, leaves 10 of it: right
+    assert lib.branch_type(0, 29, 50, 10, 39, 40) == 1          # starts the query, leaves 20 of it: left
+    assert lib.branch_type(0, 29, 50, 0, 29, 40) == 0           # dbStart == 0 && qStart == 0
+    assert lib.branch_type(20, 49, 50, 0, 39, 40) == 0          # dbEnd == dbLen - 1: the target is covered
+    assert lib.branch_type(0, 49, 50, 5, 39, 40) == 0           # qEnd == qLen - 1: the query is covered
+    assert lib.branch_type(3, 29, 50, 2, 28, 40) == 0
+    # assembleresult.cpp:212,226,234 / 216,250: the first hit of a round (offsets 0)
+    assert lib.right_frag(40, 29) == 10 and lib.right_frag(40, 39) == 0
+    assert lib.can_right(10, 49, 50) == 1 and lib.can_right(0, 49, 50) == 0 and lib.can_right(10, 48, 50) == 0
+    assert lib.can_left(10, 39, 40) == 1 and lib.can_left(0, 39, 40) == 0 and lib.can_left(10, 38, 40) == 0
+    # assembleresult.cpp:212,226-232 / 216,250-256: after an extension by 10; fragR == rightOff is dropped (<=), one more is deferred
+    assert lib.defer_right(10, 49, 50, 10) == 0 and lib.defer_right(11, 49, 50, 10) == 1
+    assert lib.defer_right(11, 49, 50, 0) == 0 and lib.defer_right(11, 48, 50, 10) == 0
+    assert lib.defer_left(10, 39, 40, 10) == 0 and lib.defer_left(11, 39, 40, 10) == 1
+    assert lib.defer_left(11, 39, 40, 0) == 0 and lib.defer_left(11, 38, 40, 10) == 0
+    # nuclassembleresult.cpp:207-216: query 49..20 on the reverse strand of target columns 0..29 of 40
+    assert four(lib.mirror, ctypes.c_int, 49, 20, 0, 29, 40) == (20, 49, 10, 39)
+
+
 def test_cli_exit_codes_separate_unsupported_from_failed():
     """plass-hip's exit-code contract (INTEGRATION.md section 1; no GPU needed with PLASSHIP_CLI_DRYRUN=1): 95 = the call is well-formed
     for the reference but outside the GPU path (the wrapper hands it to the reference binary: linclust's rescorediagonal at the end of
