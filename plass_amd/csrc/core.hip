@@ -202,7 +202,7 @@ int tuneInt(const char *name, int dflt) {
 // The switches of this build: each is set by a committed test or tool, or turns an optimisation off so that a wrong result can be bisected
 // to a stage or memory be capped (README.md, "Environment switches").  Any other PLASSHIP_TUNE_<x> in the environment is reported once.
 static const char *const TUNE_NAMES[] = {"AGGWAVE", "AGGWAVE_CAP", "ASMQ", "ASMQ_CAP", "ROWTIER", "KMCACHE", "FORCE_LONG", "CYC_PASSES", "CYCSKIP", "SHARD_EXTRACT",
-                                         "FASTA_CHUNK_MB", "DBHEAP", "DBHEAP_GB", "LAZY_SELF", "FASTQ_CHUNK_KB"};
+                                         "FASTA_CHUNK_MB", "DBHEAP", "DBHEAP_GB", "LAZY_SELF", "FASTQ_CHUNK_KB", "PART_BITS", "GROUP_SHAPE"};
 static void reportUnknownTunes() {
     static const char PREFIX[] = "PLASSHIP_TUNE_";
     for (char **e = environ; e && *e; e++) {

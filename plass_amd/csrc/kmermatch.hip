@@ -127,7 +127,10 @@ static LineGeo lineGeometry(uint64_t totalSlots, bool lng, int numCU, uint64_t s
     LineGeo g;
     const int maxBits = lng ? 9 : 10;                         // LDS: 2^bits open lines of RPL records
     const int lw = ceilLog2((uint64_t) std::max(W, 1));
-    const int totalBits = std::min(2 * maxBits, std::max(lw, std::max(0, ceilLog2(((slotsAll ? slotsAll : totalSlots) + 1535) / 1536))));   // ~1000-1500 records per final bucket
+    int totalBits = std::min(2 * maxBits, std::max(lw, std::max(0, ceilLog2(((slotsAll ? slotsAll : totalSlots) + 1535) / 1536))));   // ~1000-1500 records per final bucket
+    // PLASSHIP_TUNE_PART_BITS=n (tests): n bucket bits whatever the size — 0: one bucket holds everything; beyond maxBits: two levels on a tiny input;
+    // more buckets than the group kernel has workgroups: several buckets, most of them empty, per workgroup.  (0 is a value here: not tuneInt)
+    if (const char *pb = getenv("PLASSHIP_TUNE_PART_BITS")) { if (*pb) totalBits = std::min(2 * maxBits, std::max(lw, atoi(pb))); }
     g.b1 = totalBits <= maxBits ? totalBits : std::max((totalBits + 1) / 2, lw); g.b2 = totalBits - g.b1;
     g.nb1 = 1u << g.b1; g.nb2 = g.b2 ? 1u << g.b2 : 0u;
     g.totalLines = (totalSlots + RPL - 1) / RPL;
@@ -240,6 +243,61 @@ static int aggHistRecord(hipStream_t st, const uint32_t *dLineCnt, const uint32_
     s += " (mean " + std::to_string(nSort ? sr / nSort : 0) + ", max " + std::to_string(mr) + ") | distinct";
     for (int k = 0; k < NB; k++) s += " " + std::to_string(hd[k]);
     s += " (mean " + std::to_string(nSort ? sd / nSort : 0) + ", max " + std::to_string(md) + ", scratch " + std::to_string(big) + ")";
+    fprintf(stderr, "%s\n", s.c_str());
+    return PLASSHIP_OK;
+}
+
+// the two workgroup shapes of groupLinesKernel (16-byte records): 256 threads x 2048 slots, 512 x 4096
+constexpr int GW_BLOCK = 512; constexpr uint32_t GW_HT = 4096;
+// PLASSHIP_DEBUG_GROUPHIST=1 (debug only, off by default): one stderr line per group launch — which kernel runs over how many buckets, and which of
+// its branches the buckets reach: positions against the registers (regCap = GL_RMAX * BLOCK; 0: the 24-byte kernel keeps nothing in registers), distinct
+// k-mers against the sub-pass limit, the sub-passes the retry rule ends with (replayed here: the smallest power of two for which every class
+// (hash >> 40) % nSub holds at most maxKeys distinct k-mers), and the neighbouring buckets of one workgroup by class.  It waits for the stream.
+static bool groupHistOn() { return getenv("PLASSHIP_DEBUG_GROUPHIST") != nullptr; }
+template <bool NUCL, bool LONG>
+static int groupHistRecord(hipStream_t st, const char *kernel, uint32_t regCap, uint32_t maxKeys, uint32_t nBuckets, uint32_t bpb, const uint32_t *dFineBeg, const uint32_t *dFineCnt,
+                           const uint32_t *dList, const void *dRecs, uint64_t capLines) {
+    typedef Rec<LONG> R;
+    static int call = 0;
+    std::vector<uint32_t> beg(nBuckets), cnt(nBuckets);
+    if (nBuckets) { PH_COPY_SYNC(st, beg.data(), dFineBeg, (size_t) nBuckets * 4, hipMemcpyDeviceToHost); PH_COPY_SYNC(st, cnt.data(), dFineCnt, (size_t) nBuckets * 4, hipMemcpyDeviceToHost); }
+    uint64_t listEnd = 0;
+    for (uint32_t b = 0; b < nBuckets; b++) if (cnt[b]) listEnd = std::max<uint64_t>(listEnd, (uint64_t) beg[b] + cnt[b]);
+    if (listEnd > capLines) { setError("kmermatch: groupHist: a bucket's line list ends behind the list"); return PLASSHIP_ERR_DEVICE; }
+    std::vector<uint32_t> list(listEnd); std::vector<R> recs((size_t) capLines * RPL);
+    if (listEnd) PH_COPY_SYNC(st, list.data(), dList, (size_t) listEnd * 4, hipMemcpyDeviceToHost);
+    if (listEnd) PH_COPY_SYNC(st, recs.data(), dRecs, recs.size() * sizeof(R), hipMemcpyDeviceToHost);
+    enum { EMPTY = 0, REGS = 1, BIG = 2 };
+    static const char *const CLS[3] = {"empty", "regs", "big"};
+    auto cls = [&](uint32_t b) { const uint64_t n = (uint64_t) cnt[b] * RPL; return n == 0 ? EMPTY : (regCap == 0 || n <= regCap) ? REGS : BIG; };
+    uint64_t maxPos = 0, over = 0, maxDistinct = 0, maxSub = nBuckets ? 1 : 0, multiSub = 0, pairs[3][3] = {}, bigFirst = 0, bigLater = 0, records = 0;
+    std::vector<unsigned long long> keys, per;
+    for (uint32_t b = 0; b < nBuckets; b++) {
+        const uint64_t n = (uint64_t) cnt[b] * RPL;
+        maxPos = std::max(maxPos, n);
+        if (cls(b) == BIG) { over++; (b % bpb == 0 ? bigFirst : bigLater)++; }
+        if (b % bpb != 0) pairs[cls(b - 1)][cls(b)]++;
+        keys.clear();
+        for (uint32_t l = 0; l < cnt[b]; l++) {
+            const uint64_t line = list[beg[b] + l];
+            if (line >= capLines) { setError("kmermatch: groupHist: a line list entry is out of range"); return PLASSHIP_ERR_DEVICE; }
+            for (int i = 0; i < RPL; i++) { const R &r = recs[line * RPL + i]; if (!(r.kmer == ~0ULL && r.id == 0xFFFFFFFFu)) keys.push_back(NUCL ? (r.kmer | BIT63) : r.kmer); }
+        }
+        records += keys.size();
+        std::sort(keys.begin(), keys.end()); keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+        maxDistinct = std::max<uint64_t>(maxDistinct, keys.size());
+        uint32_t nSub = 1;
+        for (;; nSub *= 2) {
+            per.assign(nSub, 0);
+            for (const unsigned long long K : keys) per[(uint32_t) (((K * 0xD6E8FEB86659FD93ULL) >> 40) % nSub)]++;      // the kernels' sub-pass selector
+            if (*std::max_element(per.begin(), per.end()) <= maxKeys) break;
+        }
+        maxSub = std::max<uint64_t>(maxSub, nSub); multiSub += nSub > 1;
+    }
+    std::string s = "groupHist call " + std::to_string(call++) + " kernel " + kernel + " buckets " + std::to_string(nBuckets) + " bpb " + std::to_string(bpb) + " records " + std::to_string(records) +
+                    " | maxPos " + std::to_string(maxPos) + " regCap " + std::to_string(regCap) + " overRegs " + std::to_string(over) + " (first " + std::to_string(bigFirst) + ", later " + std::to_string(bigLater) + ")" +
+                    " | maxDistinct " + std::to_string(maxDistinct) + " maxKeys " + std::to_string(maxKeys) + " | maxSub " + std::to_string(maxSub) + " multiSub " + std::to_string(multiSub) + " | pairs";
+    for (int p = 0; p < 3; p++) for (int q = 0; q < 3; q++) s += std::string(" ") + CLS[p] + ">" + CLS[q] + " " + std::to_string(pairs[p][q]);
     fprintf(stderr, "%s\n", s.c_str());
     return PLASSHIP_OK;
 }
@@ -566,10 +624,18 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
     ga.includeOnlyExtendable = par->include_only_extendable; ga.covMode = par->cov_mode; ga.covThr = par->cov_thr; ga.minKey = NUCL ? dMinKey.as<unsigned long long>() : nullptr;
     // positions per bucket (sentinel padding included) decide the workgroup shape of the 16-byte-record kernel
     const uint64_t avgPos = finalCap * RPL / std::max<uint32_t>(nBuckets, 1);
-    const bool wideGroup = !LONG && avgPos > 1600;
+    // PLASSHIP_TUNE_GROUP_SHAPE (tests): 1 = the 256-thread shape, 2 = the 512-thread shape whatever the bucket size; nothing to choose in the 24-byte layout
+    const int shapeT = tuneInt("GROUP_SHAPE", 0);
+    const bool wideGroup = !LONG && (shapeT == 1 ? false : shapeT == 2 ? true : avgPos > 1600);
+    if (groupHistOn()) {
+        const int hrc = LONG ? groupHistRecord<NUCL, LONG>(st, "long", 0u, GR_MAXKEYS, nBuckets, bpb, ga.lineBeg, ga.lineCnt, finalList, finalRecs, finalCap)
+                      : wideGroup ? groupHistRecord<NUCL, LONG>(st, "wide", (uint32_t) GL_RMAX * GW_BLOCK, glMaxKeys(GW_HT), nBuckets, bpb, ga.lineBeg, ga.lineCnt, finalList, finalRecs, finalCap)
+                      : groupHistRecord<NUCL, LONG>(st, "narrow", (uint32_t) GL_RMAX * GR_BLOCK, glMaxKeys(GR_HT), nBuckets, bpb, ga.lineBeg, ga.lineCnt, finalList, finalRecs, finalCap);
+        if (hrc) return hrc;
+    }
     if (nBuckets == 0) PH_CHECK(hipMemsetAsync(dOutCnt.p, 0, (size_t) gGrid * 8, st));
     else if constexpr (LONG) hipLaunchKernelGGL((groupKernel<NUCL, LONG, true>), dim3(gGrid), dim3(GR_BLOCK), 0, st, ga);
-    else if (wideGroup) hipLaunchKernelGGL((groupLinesKernel<NUCL, 512, 4096, 4>), dim3(gGrid), dim3(512), 0, st, ga);
+    else if (wideGroup) hipLaunchKernelGGL((groupLinesKernel<NUCL, GW_BLOCK, GW_HT, 4>), dim3(gGrid), dim3(GW_BLOCK), 0, st, ga);
     else hipLaunchKernelGGL((groupLinesKernel<NUCL, GR_BLOCK, GR_HT, 3>), dim3(gGrid), dim3(GR_BLOCK), 0, st, ga);
     if (nBuckets) hipLaunchKernelGGL(arenaStartKernel, dim3(gridFor(gGrid, 256, 64)), dim3(256), 0, st, (const uint32_t *) dFineBeg.as<uint32_t>(), bpb, gGrid, nBuckets, dArenaStart.as<uint64_t>());
     else PH_CHECK(hipMemsetAsync(dArenaStart.p, 0, (size_t) gGrid * 8, st));

@@ -190,6 +190,7 @@ __global__ __launch_bounds__(GR_BLOCK) void groupKernel(GroupArgs a) {
 // 2^20 buckets two partition levels can make with ~4000 positions each, which 512 threads and 4096 slots take in one go (a
 // bucket beyond the registers would be read from HBM once per phase and sub-pass).  "At least two members" is one bit per slot.
 constexpr int GL_RMAX = 8;
+constexpr uint32_t glMaxKeys(uint32_t HT) { return HT / 4 * 3; }      // distinct k-mers per sub-pass before splitting further (the host's debug replay reads it too)
 // Look-ahead (round 6): the fetch of a bucket is two dependent round trips (line list entry, then the record), and the counters say the
 // wavefronts are parked two thirds of their cycles (SQ_WAIT_ANY 65 %, LDS pipe 10 %).  A second set of record registers does not fit (126 of 128 VGPRs:
 // profiles/r06_ab_knobs.txt), but the LIST ENTRIES of the next bucket do — one load per thread at the start of a bucket, parked in LDS behind its first
@@ -198,7 +199,7 @@ template <bool NUCL, int BLOCK, uint32_t HT, int WPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void groupLinesKernel(GroupArgs a) {
     __shared__ uint32_t sList[GL_RMAX * BLOCK / RPL];
     typedef Rec<false> R;
-    constexpr uint32_t MAXKEYS = HT / 4 * 3;                 // distinct k-mers per sub-pass before splitting further
+    constexpr uint32_t MAXKEYS = glMaxKeys(HT);
     __shared__ unsigned long long hKey[HT];
     __shared__ unsigned long long hBest[HT];
     __shared__ uint32_t hMulti[HT / 32];                     // bit = a second record met this slot's k-mer
