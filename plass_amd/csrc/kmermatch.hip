@@ -183,7 +183,12 @@ static int launchLinePart(plasship_ctx *ctx, const LinePartArgs &a, uint64_t nPi
     const bool big = lds > 72 * 1024;
     const unsigned grid = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(nPiecesBound, (uint64_t) ctx->numCU * (big ? 1u : 2u)));
     if (big) {
-        auto k = linePartKernel<NUCL, LONG, MODE, LIST, EXTRAS, 1024, 4, true>;
+        // the hash partition of the k-mer records (tools/linepart_stream_bench.hip, 3.4 G records, against a plain copy of the same bytes
+        // at 19.1 ms): the deferred store phase and streaming accesses, 2 records per lane on the dense input and 4 on the line lists,
+        // 19.7 / 19.4 ms per level where 1024 x 4 with a barrier round per store phase took 21.0 / 20.6.  The range partitions of the rep
+        // sort keep the geometry they were measured with.
+        constexpr bool HASH = MODE == KEY_HASH;
+        auto k = linePartKernel<NUCL, LONG, MODE, LIST, EXTRAS, 1024, (HASH && !LIST) ? 2 : 4, true, HASH, HASH>;
         const int rc = setDynLds(k, lds); if (rc) return rc;
         hipLaunchKernelGGL(k, dim3(grid), dim3(1024), lds, ctx->stream, a);
     } else {

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, WPE)
 #pragma unroll
             for (int j = 0; j < GL_RMAX; j++) {
                 const uint32_t i = (uint32_t) j * BLOCK + threadIdx.x;
-                const uint32_t le = fromLds ? sList[i / RPL] : a.list[lbNext + i / RPL];
+                const uint32_t le = (i < nNext) ? (fromLds ? sList[i / RPL] : a.list[lbNext + i / RPL]) : 0u;      // no read past the bucket's lines
                 rg[j] = (i < nNext) ? in[(uint64_t) le * RPL + (i % RPL)] : none;
             }
         }

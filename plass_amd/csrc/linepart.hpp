@@ -112,7 +112,34 @@ static inline size_t linePartLdsBytes(uint32_t nb, size_t recBytes, bool extras)
     return (size_t) nb * RPL * recBytes + (size_t) nb * 8 + (extras ? VH_BINS * 4 : 0) + (size_t) nb * 2 + (size_t) nb * 4 + 16;
 }
 
-template <bool NUCL, bool LONG, int MODE, bool LIST, bool EXTRAS, int LP_BLOCK, int LP_ITEMS, bool PREFETCH>
+// Streaming accesses of the records: every record is read once and written once per level, so neither access should keep a line in
+// L2 beside the tags, the line lists and the piece table (nontemporal loads and stores; 16-byte records go as one dwordx4).
+template <class R> __device__ __forceinline__ R streamLoad(const R *p) {
+    if constexpr (sizeof(R) == 16 && alignof(R) == 16) {
+        typedef uint32_t V __attribute__((ext_vector_type(4)));
+        const V v = __builtin_nontemporal_load(reinterpret_cast<const V *>(p));
+        R r; __builtin_memcpy(&r, &v, sizeof(R)); return r;
+    } else {
+        uint64_t w[sizeof(R) / 8];
+#pragma unroll
+        for (size_t k = 0; k < sizeof(R) / 8; k++) w[k] = __builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(p) + k);
+        R r; __builtin_memcpy(&r, w, sizeof(R)); return r;
+    }
+}
+template <class R> __device__ __forceinline__ void streamStore(R *p, const R &r) {
+    if constexpr (sizeof(R) == 16 && alignof(R) == 16) {
+        typedef uint32_t V __attribute__((ext_vector_type(4)));
+        V v; __builtin_memcpy(&v, &r, sizeof(R));
+        __builtin_nontemporal_store(v, reinterpret_cast<V *>(p));
+    } else {
+        uint64_t w[sizeof(R) / 8]; __builtin_memcpy(w, &r, sizeof(R));
+#pragma unroll
+        for (size_t k = 0; k < sizeof(R) / 8; k++) __builtin_nontemporal_store(w[k], reinterpret_cast<uint64_t *>(p) + k);
+    }
+}
+
+// DEFER: the rounds below end with a store phase instead of a barrier (see there).  NT: streamLoad / streamStore for the records.
+template <bool NUCL, bool LONG, int MODE, bool LIST, bool EXTRAS, int LP_BLOCK, int LP_ITEMS, bool PREFETCH, bool DEFER = false, bool NT = false>
 __global__ __launch_bounds__(LP_BLOCK) void linePartKernel(LinePartArgs a) {
     constexpr int LP_TILE = LP_BLOCK * LP_ITEMS;
     typedef Rec<LONG> R;
@@ -166,7 +193,7 @@ __global__ __launch_bounds__(LP_BLOCK) void linePartKernel(LinePartArgs a) {
                 const uint64_t i = t0 + (uint64_t) u * LP_BLOCK + tid;
                 if (i < nRec) {
                     const uint64_t line = LIST ? (uint64_t) lnNext[u] : pc.in0 + i / RPL;
-                    nxt[u] = in[line * RPL + (i % RPL)];
+                    nxt[u] = NT ? streamLoad(in + line * RPL + (i % RPL)) : in[line * RPL + (i % RPL)];
                 } else nxt[u] = sen;
             }
         };
@@ -245,35 +272,60 @@ __global__ __launch_bounds__(LP_BLOCK) void linePartKernel(LinePartArgs a) {
                 continue;
             }
             // rounds: a record joins the open line of its bucket when that line is the one it belongs to (its running number / 8);
-            // a round closes at most one line per bucket, the workgroup then writes the closed lines as one contiguous run
+            // a round closes at most one line per bucket, the workgroup then writes the closed lines as one contiguous run.
+            // DEFER: a tile's records span the open line of a bucket and, for about half the buckets, the line after it, so the
+            // rounds above took two store phases and four barriers for nearly every tile (six when some bucket got two lines' worth).
+            // Records of the line AFTER the last one flushed need no round of their own: once the flush is behind the barrier they
+            // go into the open line, and what they complete waits in the queue for the next tile's first flush.  The rounds go on
+            // only while some record lies two or more lines ahead.
             for (;;) {
                 const uint32_t par = round & 1u;
+                bool far = false;
 #pragma unroll
                 for (int u = 0; u < LP_ITEMS; u++) {
                     if ((pending >> u) & 1u) {
-                        const uint32_t b = bk[u];
-                        if (sq[u] / RPL == flushed[b]) {
+                        const uint32_t b = bk[u], f = flushed[b];
+                        if (sq[u] / RPL == f) {
                             buf[(size_t) b * RPL + (sq[u] % RPL)] = rec[u];
                             pending &= ~(1u << u);
                             if (sq[u] % RPL == RPL - 1) { const uint32_t q = atomicAdd(&sQ[par], 1u); queue[q] = (unsigned short) b; }
-                        }
+                        } else if (sq[u] / RPL > f + 1) far = true;
                     }
                 }
                 __syncthreads();
                 const uint32_t nQ = sQ[par];
-                for (uint32_t j = tid; j < nQ * RPL; j += LP_BLOCK) { const uint32_t b = queue[j / RPL]; out[(outLine + j / RPL) * RPL + (j % RPL)] = buf[(size_t) b * RPL + (j % RPL)]; }
+                for (uint32_t j = tid; j < nQ * RPL; j += LP_BLOCK) {
+                    const uint32_t b = queue[j / RPL];
+                    if (NT) streamStore(out + (outLine + j / RPL) * RPL + (j % RPL), buf[(size_t) b * RPL + (j % RPL)]);
+                    else out[(outLine + j / RPL) * RPL + (j % RPL)] = buf[(size_t) b * RPL + (j % RPL)];
+                }
                 for (uint32_t j = tid; j < nQ; j += LP_BLOCK) { const uint32_t b = queue[j]; a.tags[outLine + j] = pc.tagBase + b; flushed[b] += 1u; }
-                const int more = __syncthreads_or(pending != 0u);
+                const int more = __syncthreads_or(DEFER ? far : pending != 0u);
                 outLine += nQ;
                 if (tid == 0) sQ[par] = 0;                           // next used two rounds from now, behind the next round's barriers
                 round++;
                 if (!more) break;
+            }
+            if (DEFER) {                                             // every record left belongs to the line that is open now
+                const uint32_t par = round & 1u;                     // the queue of the next flush: the next tile's, or none at the piece's end
+#pragma unroll
+                for (int u = 0; u < LP_ITEMS; u++) {
+                    if ((pending >> u) & 1u) {
+                        const uint32_t b = bk[u];
+                        buf[(size_t) b * RPL + (sq[u] % RPL)] = rec[u];
+                        if (sq[u] % RPL == RPL - 1) { const uint32_t q = atomicAdd(&sQ[par], 1u); queue[q] = (unsigned short) b; }
+                    }
+                }
             }
         }
         // the open lines of the piece, padded with sentinels
         {
             const uint32_t par = round & 1u;
             __syncthreads();
+            if (DEFER) {                                             // lines the last tile completed are still queued: they leave with the open lines
+                if (tid == 0) sQ[par] = 0;
+                __syncthreads();
+            }
             auto openRecords = [&](uint32_t b) { return (MODE == KEY_RANGE && a.direct) ? cnt[b] % RPL : cnt[b] - flushed[b] * RPL; };
             for (uint32_t b = tid; b < nb; b += LP_BLOCK) if (openRecords(b)) { const uint32_t q = atomicAdd(&sQ[par], 1u); queue[q] = (unsigned short) b; }
             __syncthreads();
