@@ -16,6 +16,11 @@ def clust_lib_path():
     return os.path.join(os.path.dirname(lib_path()), "libplasship_clust.so")
 
 
+def linclust_lib_path():
+    """the extension library with linclust's ungapped alignment step (include/plasship_ext/linclust.h), beside the other two"""
+    return os.path.join(os.path.dirname(lib_path()), "libplasship_linclust.so")
+
+
 class PlasshipError(RuntimeError):
     pass
 
@@ -49,6 +54,11 @@ class RescoreStats(C.Structure):
 class _HammingParams(C.Structure):
     _fields_ = [("wrapped", C.c_int32), ("seq_id_thr", C.c_float), ("seq_id_mode", C.c_int32), ("cov_mode", C.c_int32),
                 ("cov_thr", C.c_float), ("min_aln_len", C.c_int32), ("eval_thr", C.c_double)]
+
+
+class _LocalParams(C.Structure):
+    _fields_ = [("eval_thr", C.c_double), ("seq_id_thr", C.c_float), ("seq_id_mode", C.c_int32), ("cov_thr", C.c_float), ("cov_mode", C.c_int32),
+                ("min_aln_len", C.c_int32), ("add_backtrace", C.c_int32), ("score_per_col_thr", C.c_float)]
 
 
 class ClustStats(C.Structure):
@@ -220,6 +230,17 @@ CLUST_SYMBOLS = [
     ("plasship_clusters_free", None, [P, P]),
     ("plasship_cands_filter", C.c_int, [P, P, P, C.POINTER(P)]),
 ]
+# include/plasship_ext/linclust.h (the extension library libplasship_linclust.so: linclust's ungapped alignment step)
+LINCLUST_SYMBOLS = [
+    ("plasship_rescore_local", C.c_int, [P, P, P, C.POINTER(_LocalParams), C.POINTER(P), C.POINTER(RescoreStats)]),
+    ("plasship_rescore_local_subset", C.c_int, [P, P, P, P, C.POINTER(_LocalParams), C.POINTER(P), C.POINTER(RescoreStats)]),
+    ("plasship_clusters_merge", C.c_int, [P, P, P, P, C.POINTER(P)]),
+    ("plasship_merged_count", C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("plasship_merged_download", C.c_int, [P, P, P, P, P]),
+    ("plasship_merged_write", C.c_int, [P, P, P, C.c_char_p]),
+    ("plasship_merged_free", None, [P, P]),
+    ("plasship_clusters_read", C.c_int, [P, P, C.c_char_p, C.POINTER(P)]),
+]
 # include/plasship_rccl.h (native RCCL communicator of a sharded run)
 RCCL_SYMBOLS = [
     ("plasship_rccl_get_unique_id", C.c_int, [P]),
@@ -260,6 +281,24 @@ def load_library():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def load_linclust_library():
+    """the extension library with linclust's ungapped alignment step, loaded when it is first asked for (Context.rescore_local), so that
+    callers of the other two libraries do not depend on it: its entry points are then reached as load_library().linclust.<name>.  A missing
+    library is an error, there is no fall-back."""
+    lib = load_library()
+    if getattr(lib, "linclust", None) is None:
+        lpath = linclust_lib_path()
+        if not os.path.exists(lpath):
+            raise PlasshipError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`" % lpath)
+        ext = C.CDLL(lpath)
+        for name, res, args in LINCLUST_SYMBOLS:
+            fn = getattr(ext, name)
+            fn.restype = res
+            fn.argtypes = args
+        lib.linclust = ext
+    return lib.linclust
 
 
 def resume_point(dir, num_iterations, name="assembly_"):
@@ -462,6 +501,20 @@ class Context:
         _check(self.lib.plasship_rescore_hamming(self.h, qdb.h, tdb.h, cands.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore_hamming")
         return Candidates(self, h, qdb, tdb), st
 
+    def rescore_local(self, db, cands, min_seq_id=0.0, seq_id_mode=0, cov_mode=0, c=0.0, min_aln_len=0, e=1e-3, a=False, score_per_col_thr=None, subset=None):
+        """`rescorediagonal --rescore-mode 2` (the best-scoring ungapped local segment on the diagonal: linclust's alignment step with
+        --alignment-mode 4) on a candidate list made on `db` -> (Alignments, RescoreStats).  Defaults = the reference module's.
+        score_per_col_thr: None is --filter-hits 0; a number is --filter-hits 1 with that score-per-column threshold (the reference reads
+        it from a table in its binary; 0.0 is its "no row found" case).  subset: a Clusters of `db` — the call is linclust's, on the subset DB
+        of its representatives (`cands` is filter_cands' list): the E-value's database size is the representatives' residue count"""
+        h = P(); st = RescoreStats()
+        cp = _LocalParams(e, min_seq_id, seq_id_mode, c, cov_mode, min_aln_len, int(bool(a)), float("nan") if score_per_col_thr is None else score_per_col_thr)
+        if subset is not None:
+            _check(load_linclust_library().plasship_rescore_local_subset(self.h, db.h, cands.h, subset.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore_local_subset")
+            return Alignments(self, h, db, db), st
+        _check(load_linclust_library().plasship_rescore_local(self.h, db.h, cands.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore_local")
+        return Alignments(self, h, db, db), st
+
     def clust_greedy(self, db, cands_or_alns):
         """`clust --cluster-mode 2 | 3` (greedy incremental clustering: the longest sequence that lists a sequence represents it) on a
         candidate list or an alignment list made on `db` -> (Clusters, ClustStats)"""
@@ -471,6 +524,19 @@ class Context:
         else:
             _check(self.lib.clust.plasship_clust_greedy_cands(self.h, db.h, cands_or_alns.h, C.byref(h), C.byref(st)), "plasship_clust_greedy_cands")
         return Clusters(self, h, db), st
+
+    def read_clusters(self, db, path):
+        """a cluster DB (dbtype 6) from disk as a clustering of `db`, by key; a sequence the DB does not list is its own cluster (a
+        clustering made on a subset DB, as linclust's second one) -> Clusters"""
+        h = P()
+        _check(load_linclust_library().plasship_clusters_read(self.h, db.h, os.fsencode(path), C.byref(h)), "plasship_clusters_read")
+        return Clusters(self, h, db)
+
+    def merge_clusters(self, db, first, second):
+        """`mergeclusters` with two clusterings of `db`: the second clusters the first one's representatives again -> MergedClusters"""
+        h = P()
+        _check(load_linclust_library().plasship_clusters_merge(self.h, db.h, first.h, second.h, C.byref(h)), "plasship_clusters_merge")
+        return MergedClusters(self, h, db)
 
     def filter_cands(self, cands, clusters):
         """what linclust's createsubdb + filterdb leave of a candidate list: the representatives' entries, and in them the lines whose
@@ -780,6 +846,33 @@ class Clusters:
     def free(self):
         if self.h:
             self.ctx.lib.clust.plasship_clusters_free(self.ctx.h, self.h); self.h = P()
+
+
+class MergedClusters:
+    """what mergeclusters makes of two clusterings of a DB, device resident: the members in the merged DB's order"""
+    def __init__(self, ctx, h, db):
+        self.ctx, self.h, self.db = ctx, h, db      # keeps the DB alive (ids -> keys)
+
+    def count(self):
+        """(members = DB size, clusters)"""
+        n = C.c_uint64(); k = C.c_uint64()
+        _check(load_linclust_library().plasship_merged_count(self.h, C.byref(n), C.byref(k)), "plasship_merged_count")
+        return n.value, k.value
+
+    def download(self):
+        """(representative keys, member keys) in the merged DB's order"""
+        import numpy as np
+        n = self.count()[0]
+        rep = np.zeros(n, dtype=np.uint32); mem = np.zeros(n, dtype=np.uint32)
+        _check(load_linclust_library().plasship_merged_download(self.ctx.h, self.h, self.db.h, rep.ctypes.data, mem.ctypes.data), "plasship_merged_download")
+        return rep, mem
+
+    def write(self, path):
+        _check(load_linclust_library().plasship_merged_write(self.ctx.h, self.h, self.db.h, os.fsencode(path)), "plasship_merged_write")
+
+    def free(self):
+        if self.h:
+            load_linclust_library().plasship_merged_free(self.ctx.h, self.h); self.h = P()
 
 
 class Alignments:

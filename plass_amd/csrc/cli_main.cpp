@@ -11,10 +11,12 @@
 // (another substitution matrix, spaced k-mers, masking, automatic k …) fail loudly like Debug(Debug::ERROR) + EXIT(EXIT_FAILURE).
 #include "../../include/plasship.h"
 #include "../../include/plasship_ext/clust.h"
+#include "../../include/plasship_ext/linclust.h"
 #include <chrono>
 #include <unistd.h>
 #include <cstdarg>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,6 +73,7 @@ struct Flags {
     int singleEnd = 0, shuffle = 1, dbtypeArg = 0, createdbMode = 0, writeLookup = 1; unsigned long long idOffset = 0;
     std::string dbOut, nuclAssemblyOut; int dbMode = 0, numIterationsNucl = 5, kNucl = 22, minAlnLenNucl = 0;
     int clusterMode = 0;                 // clust: Parameters::SET_COVER (not one of kMembers: the dump's lines are pinned as they are)
+    float scorePerColThr = 0.0f;         // rescorediagonal-local --score-per-col-thr (our own flag; not one of kMembers either)
     std::set<std::string> seen;
 };
 
@@ -164,7 +167,7 @@ template <class T, void (*Free)(plasship_ctx *, T *)> struct Handle {
 };
 typedef Handle<plasship_seqdb, plasship_seqdb_free> SeqDb; typedef Handle<plasship_orfhdr, plasship_orfhdr_free> OrfHdr;
 typedef Handle<plasship_cands, plasship_cands_free> Cands; typedef Handle<plasship_alns, plasship_alns_free> Alns;
-typedef Handle<plasship_clusters, plasship_clusters_free> Clusters;
+typedef Handle<plasship_clusters, plasship_clusters_free> Clusters; typedef Handle<plasship_merged, plasship_merged_free> Merged;
 
 // ---- the modules: one bit each, so that a flag states its owners as a mask ----
 enum : unsigned {
@@ -172,10 +175,12 @@ enum : unsigned {
     FINDASSEMBLYSTART = 1u << 6, CYCLECHECK = 1u << 7, EXTRACTORFS = 1u << 8, TRANSLATENUCS = 1u << 9, CONCATDBS = 1u << 10, ASSEMBLE_CHAIN = 1u << 11,
     NUCLASSEMBLE_CHAIN = 1u << 12, GUIDEDASSEMBLE_CHAIN = 1u << 13, CREATEDB_READS = 1u << 14, MERGEREADS = 1u << 15, RESCOREDIAGONAL_HAMMING = 1u << 16,
     ANY_ASSEMBLERESULTS = ASSEMBLERESULTS | NUCLASSEMBLERESULTS | GUIDEDASSEMBLERESULTS, CHAINS = ASSEMBLE_CHAIN | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN,
-    CLUST_GREEDY = 1u << 17, LINCLUST_PRE = 1u << 18,
-    // (rescorediagonal-hamming takes rescorediagonal's flag set, clust-greedy clust's; linclust-pre the union of its three steps')
-    ANY_KMERMATCHER = KMERMATCHER | LINCLUST_PRE, ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING | LINCLUST_PRE, ANY_CLUST = CLUST_GREEDY | LINCLUST_PRE,
-    ALL = 0x7FFFFu
+    CLUST_GREEDY = 1u << 17, LINCLUST_PRE = 1u << 18, RESCOREDIAGONAL_LOCAL = 1u << 19, MERGECLUSTERS_GREEDY = 1u << 20, LINCLUST_UNGAPPED = 1u << 21,
+    // (rescorediagonal-hamming and rescorediagonal-local take rescorediagonal's flag set, clust-greedy clust's; linclust-pre the union of its three steps',
+    //  linclust-ungapped the union of linclust-pre's and rescorediagonal-local's; mergeclusters-greedy has the reference's: --threads, --compressed, -v)
+    ANY_KMERMATCHER = KMERMATCHER | LINCLUST_PRE | LINCLUST_UNGAPPED, ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING | RESCOREDIAGONAL_LOCAL | LINCLUST_PRE | LINCLUST_UNGAPPED,
+    ANY_CLUST = CLUST_GREEDY | LINCLUST_PRE | LINCLUST_UNGAPPED,
+    ALL = 0x3FFFFFu
 };
 
 // ---- the flags: each once, with the modules that own it (its parameter vector in the reference; for the fused drivers the workflow's own),
@@ -232,6 +237,7 @@ static const Flag kFlags[] = {
     {"--mask-lower-case", ANY_KMERMATCHER, ZERO}, {"--split-memory-limit", ANY_KMERMATCHER, IGNORED}, {"--include-only-extendable", ANY_KMERMATCHER, BOOL, M(onlyExt)},
     {"--wrapped-scoring", ANY_RESCOREDIAGONAL, BOOL, M(wrapped)}, {"--filter-hits", ANY_RESCOREDIAGONAL, BOOL, M(filterHits)}, {"-a", ANY_RESCOREDIAGONAL, BOOL, M(addBt)},
     {"--add-self-matches", ANY_RESCOREDIAGONAL, BOOL, M(addSelf)}, {"--sort-results", ANY_RESCOREDIAGONAL, VALUE, M(sortResults)}, {"--db-load-mode", ANY_RESCOREDIAGONAL, IGNORED},
+    {"--score-per-col-thr", RESCOREDIAGONAL_LOCAL | LINCLUST_UNGAPPED, VALUE, M(scorePerColThr)},
     {"--cluster-mode", ANY_CLUST, VALUE, M(clusterMode)}, {"--max-iterations", ANY_CLUST, IGNORED}, {"--similarity-type", ANY_CLUST, IGNORED},
     {"--gap-open", PROTEINALN2NUCL, NUCL, M(gapOpenNucl)}, {"--gap-extend", PROTEINALN2NUCL, NUCL, M(gapExtendNucl)},
     {"--min-length", EXTRACTORFS, VALUE, M(orfMin)}, {"--max-length", EXTRACTORFS, VALUE, M(orfMax)}, {"--max-gaps", EXTRACTORFS, VALUE, M(orfGaps)},
@@ -295,6 +301,12 @@ static plasship_rescore_params rescoreParams(const Flags &f) {
 static plasship_hamming_params hammingParams(const Flags &f) {
     plasship_hamming_params p = {};
     p.wrapped = f.wrapped; p.seq_id_thr = f.seqIdThr; p.seq_id_mode = f.seqIdMode; p.cov_mode = f.covMode; p.cov_thr = f.covThr; p.min_aln_len = f.minAlnLen; p.eval_thr = f.evalThr;
+    return p;
+}
+static plasship_local_params localParams(const Flags &f) {
+    plasship_local_params p = {};
+    p.eval_thr = f.evalThr; p.seq_id_thr = f.seqIdThr; p.seq_id_mode = f.seqIdMode; p.cov_thr = f.covThr; p.cov_mode = f.covMode; p.min_aln_len = f.minAlnLen;
+    p.add_backtrace = f.addBt; p.score_per_col_thr = f.filterHits ? f.scorePerColThr : NAN;
     return p;
 }
 static plasship_assemble_params assembleParams(const Flags &f) {
@@ -519,6 +531,16 @@ static int validateRescoreHamming(Call &c) {
     if (c.f.rescoreMode != 0) return unsupported("plass-hip rescorediagonal-hamming: --rescore-mode %d is not this module's (0, the Hamming score, only)\n", c.f.rescoreMode);
     return c.pos.size() == 4 && c.pos[0] != c.pos[1] ? unsupported("plass-hip rescorediagonal-hamming: separate query and target DBs are not part of the GPU path (linclust uses one DB)\n") : 0;
 }
+// rescorediagonal-local (our own name: `rescorediagonal --rescore-mode 2` keeps its answer): linclust's alignment step with --alignment-mode 4,
+// lib/mmseqs/src/workflow/Linclust.cpp:86-129.  --filter-hits 1 compares the score per column with a threshold the reference reads from a table in
+// its binary (rescorediagonal.cpp:20-43,95-105); that table is not part of this build, so the threshold comes with our own --score-per-col-thr
+static int validateRescoreLocal(Call &c) {
+    if (c.f.rescoreMode != 2) return unsupported("plass-hip rescorediagonal-local: --rescore-mode %d is not this module's (2, the local ungapped alignment, only)\n", c.f.rescoreMode);
+    if (c.f.wrapped || c.f.sortResults > 0) return unsupported("plass-hip rescorediagonal-local: --wrapped-scoring 1 / --sort-results are not part of the GPU path\n");
+    if (c.f.filterHits && !c.f.seen.count("--score-per-col-thr"))
+        return unsupported("plass-hip rescorediagonal-local: --filter-hits 1 needs --score-per-col-thr X (the reference's threshold table is not part of this build)\n");
+    return c.pos.size() == 4 && c.pos[0] != c.pos[1] ? unsupported("plass-hip rescorediagonal-local: separate query and target DBs are not part of the GPU path (linclust uses one DB)\n") : 0;
+}
 // clust-greedy (our own name: `clust` stays with the reference): clust's greedy modes, Parameters::GREEDY = 2 and GREEDY_MEM = 3, which both run
 // greedyIncrementalLowMem (Clustering.cpp:42-47).  The module's default is set cover: a call without --cluster-mode is the reference's.
 static int validateClustMode(Call &c) {
@@ -537,6 +559,26 @@ static int validateLinclustPre(Call &c) {
     if (const int rc = validateClustMode(c)) return rc;
     if (const int rc = validateKmermatcher(c)) return rc;
     return validateRescoreHamming(c);
+}
+// mergeclusters-greedy (our own name: `mergeclusters` stays with the reference): the reference merges any number of clusterings, linclust passes two
+static int validateMergeclusters(Call &c) {
+    return c.pos.size() >= 3 && c.pos.size() != 4 ? unsupported("plass-hip mergeclusters-greedy: %zu clusterings are not part of the GPU path (exactly two, as linclust passes them)\n", c.pos.size() - 2) : 0;
+}
+// linclust-ungapped: the whole of linclust.sh with --alignment-mode 4 on a nucleotide DB, from the sequence DB to the merged clustering.  The workflow
+// sets --rescore-mode for its steps itself (0, then 2) and runs the alignment with --filter-hits 1 (workflow/Linclust.cpp:103-127: filterHits is set for step 3
+// and stays set), so the threshold has to come with --score-per-col-thr unless --filter-hits 0 is given.  A protein DB has the workflow's extra
+// filter step 3 (linclust.sh:59-68), which is not built
+static int validateLinclustUngapped(Call &c) {
+    if (const int rc = validateClustMode(c)) return rc;
+    if (const int rc = validateKmermatcher(c)) return rc;
+    if (c.f.seen.count("--rescore-mode") && c.f.rescoreMode != 2) return unsupported("plass-hip linclust-ungapped: --rescore-mode %d is not this driver's (its alignment step is mode 2)\n", c.f.rescoreMode);
+    // (the reference's mode 2 ends with "wrapped scoring is only allowed with RESCORE_MODE_HAMMING", and the workflow passes one flag set to both steps)
+    if (c.f.wrapped || c.f.sortResults > 0) return unsupported("plass-hip linclust-ungapped: --wrapped-scoring 1 / --sort-results are not part of the GPU path\n");
+    if (c.f.filterHits && !c.f.seen.count("--score-per-col-thr"))
+        return unsupported("plass-hip linclust-ungapped: the workflow's alignment step runs with --filter-hits 1, which needs --score-per-col-thr X (the reference's threshold table is not part of this build); or give --filter-hits 0\n");
+    if (c.pos.size() == 2 && probeDbtype(c.pos[0]) == PLASSHIP_DBTYPE_AMINO_ACIDS)
+        return unsupported("plass-hip linclust-ungapped: a protein DB is not part of the GPU path (nucleotide DBs only: the protein workflow has a filter step more)\n");
+    return 0;
 }
 // Requests that are valid for the reference and lie outside the GPU path are all refused in validate(), before the dry-run exit and before anything
 // is read or written (data/nuclassemble.sh:41,145 calls `concatdbs ... --preserve-keys` whenever circular contigs exist; with exit
@@ -655,6 +697,15 @@ static int runRescoreHamming(Call &c) {           // (query and target are one D
     fprintf(stdout, "scored: %llu kept: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_scored, (unsigned long long) st.n_accepted, st.ms_kernel);
     return KW(plasship_cands_write(ctx, kept, db, pos[3].c_str())) ? fail("rescorediagonal-hamming") : EXIT_SUCCESS;
 }
+static int runRescoreLocal(Call &c) {             // (query and target are one DB: validateRescoreLocal)
+    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
+    SeqDb db(ctx); Cands cands(ctx); Alns al(ctx);
+    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out())) || K(plasship_cands_read(ctx, db, db, pos[2].c_str(), cands.out()))) return fail("rescorediagonal-local");
+    const plasship_local_params p = localParams(c.f); plasship_rescore_stats st = {};
+    if (K(plasship_rescore_local(ctx, db, cands, &p, al.out(), &st))) return fail("rescorediagonal-local");
+    fprintf(stdout, "scored: %llu kept: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_scored, (unsigned long long) st.n_accepted, st.ms_kernel);
+    return KW(plasship_alns_write(ctx, al, pos[3].c_str())) ? fail("rescorediagonal-local") : EXIT_SUCCESS;
+}
 static long indexLines(const std::string &db) {       // entries of a DB on disk; -1: no index
     FILE *fi = fopen((db + ".index").c_str(), "rb"); if (!fi) return -1;
     long n = 0; char buf[65536]; size_t got;
@@ -695,6 +746,38 @@ static int runLinclustPre(Call &c) {              // kmermatcher -> rescorediago
             (unsigned long long) rs.n_accepted, rs.ms_kernel);
     printClustStats(st);
     return KW(plasship_clusters_write(ctx, cl, db, c.pos[1].c_str())) || KW(plasship_cands_write(ctx, filtered, db, c.pos[2].c_str())) ? fail("linclust-pre") : EXIT_SUCCESS;
+}
+static int runMergeclusters(Call &c) {            // (exactly two clusterings: validateMergeclusters)
+    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
+    SeqDb db(ctx); Clusters first(ctx), second(ctx); Merged mg(ctx);
+    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out()))) return fail("mergeclusters-greedy");
+    // (a clustering the reader cannot take — a key listed twice, a representative listed under another one — is left to the reference: nothing has been written)
+    if (K(plasship_clusters_read(ctx, db, pos[2].c_str(), first.out())) || K(plasship_clusters_read(ctx, db, pos[3].c_str(), second.out())) ||
+        K(plasship_clusters_merge(ctx, db, first, second, mg.out())))
+        return g_lastRc == PLASSHIP_ERR_ARG ? unsupported("plass-hip mergeclusters-greedy: %s\n", plasship_last_error()) : fail("mergeclusters-greedy");
+    uint64_t n = 0, nC = 0; plasship_merged_count(mg, &n, &nC);
+    fprintf(stdout, "sequences: %llu clusters: %llu\n", (unsigned long long) n, (unsigned long long) nC);
+    return KW(plasship_merged_write(ctx, mg, db, pos[1].c_str())) ? fail("mergeclusters-greedy") : EXIT_SUCCESS;
+}
+static int runLinclustUngapped(Call &c) {         // linclust-pre's chain, then mode 2 on the representatives -> clust -> mergeclusters, on handles
+    plasship_ctx *ctx = c.ctx; const Flags &f = c.f;
+    SeqDb db(ctx); Cands pref(ctx), rescored(ctx), filtered(ctx); Clusters pre(ctx), cl(ctx); Alns al(ctx); Merged mg(ctx);
+    if (K(plasship_seqdb_read(ctx, c.pos[0].c_str(), db.out()))) return fail("linclust-ungapped");
+    if (dbtypeOf(db) != PLASSHIP_DBTYPE_NUCLEOTIDES) return unsupported("plass-hip linclust-ungapped: nucleotide DBs only\n");
+    const plasship_kmermatch_params kp = kmermatchParams(f, f.scaleNucl); plasship_kmermatch_stats ks = {};
+    plasship_hamming_params hp = hammingParams(f);      // Linclust.cpp:106-111: the Hamming step never goes below 0.5 in seq. id. and coverage
+    hp.seq_id_thr = std::max(0.5f, f.seqIdThr); hp.cov_thr = std::max(0.5f, f.covThr);
+    const plasship_local_params lp = localParams(f); plasship_rescore_stats rs = {}, ls = {}; plasship_clust_stats st = {}, st2 = {};
+    if (K(plasship_kmermatch(ctx, db, &kp, pref.out(), &ks)) || K(plasship_rescore_hamming(ctx, db, db, pref, &hp, rescored.out(), &rs)) ||
+        K(plasship_clust_greedy_cands(ctx, db, rescored, pre.out(), &st)) || K(plasship_cands_filter(ctx, pref, pre, filtered.out())) ||
+        K(plasship_rescore_local_subset(ctx, db, filtered, pre, &lp, al.out(), &ls)) || K(plasship_clust_greedy_alns(ctx, db, al, cl.out(), &st2)) ||
+        K(plasship_clusters_merge(ctx, db, pre, cl, mg.out()))) return fail("linclust-ungapped");
+    fprintf(stdout, "candidates: %llu scored: %llu kept: %llu | aligned: %llu kept: %llu | kernel ms: hamming %.3f local %.3f\n", (unsigned long long) ks.n_candidates,
+            (unsigned long long) rs.n_scored, (unsigned long long) rs.n_accepted, (unsigned long long) ls.n_scored, (unsigned long long) ls.n_accepted, rs.ms_kernel, ls.ms_kernel);
+    printClustStats(st);
+    uint64_t n = 0, nC = 0; plasship_merged_count(mg, &n, &nC);
+    fprintf(stdout, "sequences: %llu clusters: %llu\n", (unsigned long long) n, (unsigned long long) nC);
+    return KW(plasship_merged_write(ctx, mg, db, c.pos[1].c_str())) ? fail("linclust-ungapped") : EXIT_SUCCESS;
 }
 static int runAssembleresults(Call &c) {          // assembleresults and nuclassembleresults
     plasship_ctx *ctx = c.ctx; SeqDb db(ctx); Alns al(ctx); SeqDb o(ctx);
@@ -959,9 +1042,12 @@ static const Module kModules[] = {
     {"kmermatcher", KMERMATCHER, 2, "kmermatcher <i:sequenceDB> <o:prefDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; }, validateKmermatcher, runKmermatcher},
     {"rescorediagonal", RESCOREDIAGONAL, 4, "rescorediagonal <i:queryDB> <i:targetDB> <i:prefDB> <o:alnDB>", nullptr, validateRescorediagonal, runRescorediagonal},
     {"rescorediagonal-hamming", RESCOREDIAGONAL_HAMMING, 4, "rescorediagonal-hamming <i:queryDB> <i:targetDB> <i:prefDB> <o:prefDB>", nullptr, validateRescoreHamming, runRescoreHamming},
+    {"rescorediagonal-local", RESCOREDIAGONAL_LOCAL, 4, "rescorediagonal-local <i:queryDB> <i:targetDB> <i:prefDB> <o:alnDB>", nullptr, validateRescoreLocal, runRescoreLocal},
     // linclust's greedy `clust` and its whole pre-cluster stage, lib/mmseqs/data/workflow/linclust.sh:21-57 (our own names: `clust` and `linclust` stay with the reference)
     {"clust-greedy", CLUST_GREEDY, 3, "clust-greedy <i:sequenceDB> <i:resultDB> <o:clusterDB>", nullptr, validateClustGreedy, runClustGreedy},
     {"linclust-pre", LINCLUST_PRE, 3, "linclust-pre <i:sequenceDB> <o:preClusterDB> <o:prefilterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; }, validateLinclustPre, runLinclustPre},
+    {"mergeclusters-greedy", MERGECLUSTERS_GREEDY, 4, "mergeclusters-greedy <i:sequenceDB> <o:clusterDB> <i:clusterDB1> <i:clusterDB2>", nullptr, validateMergeclusters, runMergeclusters},
+    {"linclust-ungapped", LINCLUST_UNGAPPED, 2, "linclust-ungapped <i:sequenceDB> <o:clusterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; f.filterHits = 1; }, validateLinclustUngapped, runLinclustUngapped},
     {"assembleresults", ASSEMBLERESULTS, 3, "assembleresults <i:sequenceDB> <i:alnResult> <o:reprSeqDB>", nullptr, nullptr, runAssembleresults},
     {"nuclassembleresults", NUCLASSEMBLERESULTS, 3, "nuclassembleresults <i:sequenceDB> <i:alnResult> <o:reprSeqDB>", nullptr, nullptr, runAssembleresults},
     {"guidedassembleresults", GUIDEDASSEMBLERESULTS, 5, "guidedassembleresults <i:nuclSequenceDB> <i:aaSequenceDB> <i:nuclAlnResult> <o:nuclAssembly> <o:aaAssembly>", nullptr, nullptr, runGuidedassembleresults},
