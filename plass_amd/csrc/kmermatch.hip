@@ -199,15 +199,53 @@ static int launchLinePart(plasship_ctx *ctx, const LinePartArgs &a, uint64_t nPi
     return PLASSHIP_OK;
 }
 
+// PLASSHIP_DEBUG_LINELIST=1 (debug only, off by default): one stderr line per line-list build — the caller (hash partition or rep sort), the
+// level, its buckets, the output lines the kernel walks, the lines listed, the chunk size and the number of chunks, the regions (level 2: also
+// the pieces they were written in), and the largest bucket in lines.  It waits for the stream.
+static bool lineListDebugOn() { return getenv("PLASSHIP_DEBUG_LINELIST") != nullptr; }
+
 // line lists of one partition level over `capLines` output lines: list[start[b] .. start[b + 1]) = lines of bucket b
-static int buildLineLists(plasship_ctx *ctx, const uint32_t *dTags, uint64_t capLines, uint32_t nb, uint32_t *dCount, uint32_t *dStart, uint32_t *dCursor, uint32_t *dList) {
+static int buildLineLists(plasship_ctx *ctx, const char *who, const uint32_t *dTags, uint64_t capLines, uint32_t nb, uint32_t *dCount, uint32_t *dStart, uint32_t *dCursor, uint32_t *dList) {
     hipStream_t st = ctx->stream;
     PH_CHECK(hipMemsetAsync(dCount, 0, (size_t) nb * 4, st));
     const unsigned g = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((capLines + 4095) / 4096, (uint64_t) ctx->numCU * 8));
-    const unsigned gs = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((capLines + TS_CHUNK - 1) / TS_CHUNK, (uint64_t) ctx->numCU * 2));
+    const size_t lds = listRunsLdsBytes(LR_CHUNK, false);
+    const unsigned gs = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((capLines + LR_CHUNK - 1) / LR_CHUNK, (uint64_t) ctx->numCU));      // 136 KB of LDS: one workgroup per CU
+    auto k = tagScatterRunsKernel<LR_BLOCK, LR_CHUNK>;
+    const int rc = setDynLds(k, lds); if (rc) return rc;
     hipLaunchKernelGGL(tagHistKernel, dim3(g), dim3(256), 0, st, dTags, capLines, nb, dCount);
     hipLaunchKernelGGL(tagScanKernel, dim3(1), dim3(1024), 0, st, (const uint32_t *) dCount, nb, dStart, dCursor);
-    hipLaunchKernelGGL(tagScatterKernel, dim3(gs), dim3(TS_BLOCK), 0, st, dTags, capLines, nb, dCursor, dList);
+    hipLaunchKernelGGL(k, dim3(gs), dim3(LR_BLOCK), lds, st, dTags, capLines, nb, dCursor, dList);
+    if (lineListDebugOn()) {
+        std::vector<uint32_t> s((size_t) nb + 1);
+        PH_COPY_SYNC(st, s.data(), dStart, s.size() * 4, hipMemcpyDeviceToHost);
+        uint32_t mx = 0; for (uint32_t b = 0; b < nb; b++) mx = std::max(mx, s[b + 1] - s[b]);
+        fprintf(stderr, "lineList %s level 1 buckets %u lines %llu listed %u chunk %d chunks %llu regions 0 maxBucket %u\n", who, nb, (unsigned long long) capLines, s[nb], LR_CHUNK,
+                (unsigned long long) ((capLines + LR_CHUNK - 1) / LR_CHUNK), mx);
+    }
+    return PLASSHIP_OK;
+}
+// level 2: the list of every region (the output range of one level-1 bucket) and the (begin, count) of its nb2 fine buckets
+static int buildRegionLists(plasship_ctx *ctx, const char *who, const uint32_t *dTags, const uint32_t *dNPieces, const uint64_t *dRegBeg, const uint64_t *dRegEnd, uint32_t nRegions, uint32_t nb2, uint32_t *dList, uint32_t *dFineBeg, uint32_t *dFineCnt) {
+    hipStream_t st = ctx->stream;
+    const size_t lds = listRunsLdsBytes(LR2_CHUNK, true);
+    auto k = tagSortRegionRunsKernel<LR2_BLOCK, LR2_CHUNK>;
+    const int rc = setDynLds(k, lds); if (rc) return rc;
+    hipLaunchKernelGGL(k, dim3(std::max<uint32_t>(1, std::min<uint32_t>(nRegions, (uint32_t) ctx->numCU))), dim3(LR2_BLOCK), lds, st, dTags, dRegBeg, dRegEnd, nRegions, nb2, dList, dFineBeg, dFineCnt);
+    if (lineListDebugOn()) {
+        std::vector<uint64_t> rb(nRegions), re(nRegions); std::vector<uint32_t> fc((size_t) nRegions * nb2);
+        PH_COPY_SYNC(st, rb.data(), dRegBeg, rb.size() * 8, hipMemcpyDeviceToHost); PH_COPY_SYNC(st, re.data(), dRegEnd, re.size() * 8, hipMemcpyDeviceToHost);
+        PH_COPY_SYNC(st, fc.data(), dFineCnt, fc.size() * 4, hipMemcpyDeviceToHost);
+        uint32_t nPieces = 0; PH_COPY_SYNC(st, &nPieces, dNPieces, 4, hipMemcpyDeviceToHost);
+        uint64_t lines = 0, listed = 0, chunks = 0, maxRegion = 0; uint32_t mx = 0, emptyRegions = 0;
+        for (uint32_t g = 0; g < nRegions; g++) {
+            const uint64_t len = re[g] - rb[g]; lines += len; chunks += (len + LR2_CHUNK - 1) / LR2_CHUNK;
+            uint64_t in = 0; for (uint32_t f = 0; f < nb2; f++) { const uint32_t c = fc[(size_t) g * nb2 + f]; in += c; mx = std::max(mx, c); }
+            listed += in; maxRegion = std::max(maxRegion, in); emptyRegions += in == 0;
+        }
+        fprintf(stderr, "lineList %s level 2 buckets %u lines %llu listed %llu chunk %d chunks %llu regions %u maxBucket %u emptyRegions %u maxRegion %llu pieces %u\n", who, nb2, (unsigned long long) lines,
+                (unsigned long long) listed, LR2_CHUNK, (unsigned long long) chunks, nRegions, mx, emptyRegions, (unsigned long long) maxRegion, nPieces);
+    }
     return PLASSHIP_OK;
 }
 
@@ -370,7 +408,7 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
         rc = launchLinePart<NUCL, PL, KEY_RANGE, false, false>(ctx, a, std::max<uint32_t>(nPR1, 1)); if (rc) return rc;
     }
     if (nPR1 && !hpPinned) PH_CHECK(plasship::streamSync(st));   // hp goes out of use (async copy of a pageable host vector)
-    rc = buildLineLists(ctx, dRTag1.as<uint32_t>(), capR1, nS1, dRCnt1.as<uint32_t>(), dRStart1.as<uint32_t>(), dRCur1.as<uint32_t>(), dRList1.as<uint32_t>()); if (rc) return rc;
+    rc = buildLineLists(ctx, "repsort", dRTag1.as<uint32_t>(), capR1, nS1, dRCnt1.as<uint32_t>(), dRStart1.as<uint32_t>(), dRCur1.as<uint32_t>(), dRList1.as<uint32_t>()); if (rc) return rc;
     inputConsumed();                                        // the caller's input buffer is dead (stream order): it may release it
     const void *sortRecs = dR1.p; const uint32_t *sortList = dRList1.as<uint32_t>(); uint64_t sortCap = capR1;
     if (s2) {
@@ -383,8 +421,7 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
         a.direct = 1;
         a.key = rkey; a.key.shift = 64 - s1 - s2;
         rc = launchLinePart<NUCL, PL, KEY_RANGE, true, false>(ctx, a, maxPR2); if (rc) return rc;
-        hipLaunchKernelGGL(tagSortRegionKernel, dim3(std::min<uint32_t>(nS1, (uint32_t) numCU * 4)), dim3(512), 0, st, (const uint32_t *) dRTag2.as<uint32_t>(), (const uint64_t *) dRRegBeg.as<uint64_t>(),
-                           (const uint64_t *) dRRegEnd.as<uint64_t>(), nS1, nS2, dRList2.as<uint32_t>(), dSortBeg.as<uint32_t>(), dSortCnt.as<uint32_t>());
+        rc = buildRegionLists(ctx, "repsort", dRTag2.as<uint32_t>(), dRNP2.as<uint32_t>(), dRRegBeg.as<uint64_t>(), dRRegEnd.as<uint64_t>(), nS1, nS2, dRList2.as<uint32_t>(), dSortBeg.as<uint32_t>(), dSortCnt.as<uint32_t>()); if (rc) return rc;
         sortRecs = dR2.p; sortList = dRList2.as<uint32_t>(); sortCap = capR2;
     } else {
         hipLaunchKernelGGL(listRangesKernel, dim3(4), dim3(256), 0, st, (const uint32_t *) dRStart1.as<uint32_t>(), nS1, dSortBeg.as<uint32_t>(), dSortCnt.as<uint32_t>());
@@ -507,7 +544,7 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
         const int rc = launchLinePart<NUCL, LONG, KEY_HASH, false, true>(ctx, a, geo.nP1); if (rc) return rc;
         PH_CHECK(hipEventRecord(ctx->ev[9], st));
     }
-    int rc = buildLineLists(ctx, dTag1.as<uint32_t>(), geo.cap1, geo.nb1, dCnt1.as<uint32_t>(), dStart1.as<uint32_t>(), dCur1.as<uint32_t>(), dList1.as<uint32_t>()); if (rc) return rc;
+    int rc = buildLineLists(ctx, "hash", dTag1.as<uint32_t>(), geo.cap1, geo.nb1, dCnt1.as<uint32_t>(), dStart1.as<uint32_t>(), dCur1.as<uint32_t>(), dList1.as<uint32_t>()); if (rc) return rc;
     // what level 2 (or, with a single level, the group kernel) reads: records, their line list, the list offsets of the nbL buckets
     void *l1Recs = dB.p; const uint32_t *l1List = dList1.as<uint32_t>(); const uint32_t *l1Start = dStart1.as<uint32_t>() + bLo; uint64_t l1Lines = geo.cap1;
     const uint32_t *l1Tags = dTag1.as<uint32_t>();
@@ -595,8 +632,7 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
         PH_CHECK(hipEventRecord(ctx->ev[10], st));
         rc = launchLinePart<NUCL, LONG, KEY_HASH, true, false>(ctx, a, geo.maxP2); if (rc) return rc;
         PH_CHECK(hipEventRecord(ctx->ev[11], st));
-        hipLaunchKernelGGL(tagSortRegionKernel, dim3(std::min<uint32_t>(nbL, (uint32_t) numCU * 4)), dim3(512), 0, st, (const uint32_t *) dTag2.as<uint32_t>(), (const uint64_t *) dRegBeg.as<uint64_t>(),
-                           (const uint64_t *) dRegEnd.as<uint64_t>(), nbL, geo.nb2, dList2.as<uint32_t>(), dFineBeg.as<uint32_t>(), dFineCnt.as<uint32_t>());
+        rc = buildRegionLists(ctx, "hash", dTag2.as<uint32_t>(), dNP2.as<uint32_t>(), dRegBeg.as<uint64_t>(), dRegEnd.as<uint64_t>(), nbL, geo.nb2, dList2.as<uint32_t>(), dFineBeg.as<uint32_t>(), dFineCnt.as<uint32_t>()); if (rc) return rc;
         finalRecs = l2Out; finalTags = dTag2.as<uint32_t>(); finalList = dList2.as<uint32_t>(); finalCap = cap2;
         res.nPart = 2;
     } else {

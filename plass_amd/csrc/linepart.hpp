@@ -357,6 +357,16 @@ __global__ __launch_bounds__(LP_BLOCK) void linePartKernel(LinePartArgs a) {
 // =====================================================================================================
 // line lists: counting sort of the tags
 // =====================================================================================================
+// What a consumer may rely on: a bucket's list range holds each of its lines once, in any order.
+//   level 1: tagHistKernel (one read of the tags) -> tagScanKernel -> tagScatterRunsKernel;
+//   level 2: tagSortRegionRunsKernel, one workgroup per region: count, scan, then the same chunk routine.
+// Both write the list as RUNS: a chunk of 32 768 tags is put in bucket order in LDS (128 KB, one workgroup per CU) and consecutive lanes
+// write consecutive list entries (listChunkRuns).  Measured reason (profiles/linelist_pmc.txt, linelist_stream_bench.txt): one 4-byte
+// store per tag is one L2 request per tag and 6.4 bytes written per byte of list, and the wavefronts wait for those stores, not for the
+// per-chunk atomic; a run of a whole chunk is a 128-byte line per bucket on average, shorter runs of smaller chunks lose
+// (profiles/linelist_ab_knobs.txt, which also names what keeps the kernels at 1.9 x / 2.4 x a copy of the same bytes).
+// tagScatterKernel and tagSortRegionKernel (a store per tag; rows of 8 entries) are launched by tools/ only, as the baselines of
+// linelist_bench.hip, linepart_bench.hip and linepart_stream_bench.hip.
 // (a) whole tag array -> per-bucket line lists (level 1, or the only level)
 __global__ __launch_bounds__(256) void tagHistKernel(const uint32_t *__restrict__ tags, uint64_t nLines, uint32_t nb, uint32_t *__restrict__ count) {
     __shared__ uint32_t sh[LP_MAXB];
@@ -408,6 +418,69 @@ __global__ __launch_bounds__(TS_BLOCK) void tagScatterKernel(const uint32_t *__r
         __syncthreads();
     }
 }
+// ---- lists written as runs ----
+// One chunk of tags -> list entries, by the whole workgroup.  Every tag takes ONE returning LDS atomic (its rank among the chunk's tags of
+// its bucket), the chunk's per-bucket counts are scanned, the entries are put in bucket order in LDS (`stage`, 4 bytes each: bucket << 16 |
+// line - c0) and leave as runs: consecutive lanes write consecutive list entries, so a wavefront's store touches the two or three 128-byte
+// lines its 64 entries lie in where a store per tag touched 64.  `reserve(b, c)` returns where in the list the c entries of bucket b go.
+// cnt[LP_MAXB] is zero on entry and on exit; delta[LP_MAXB] and sWave[BLOCK / 64] are scratch.  A list entry is any order within its bucket.
+template <int BLOCK, int CHUNK, class Reserve>
+__device__ __forceinline__ void listChunkRuns(const uint32_t (&t)[CHUNK / BLOCK], uint64_t c0, uint32_t tagBase, uint32_t *__restrict__ list,
+                                              uint32_t *stage, uint32_t *cnt, uint32_t *delta, uint32_t *sWave, Reserve reserve) {
+    constexpr int PER = CHUNK / BLOCK, PERB = LP_MAXB / BLOCK;
+    static_assert(CHUNK <= 65536 && CHUNK % BLOCK == 0 && LP_MAXB % BLOCK == 0 && BLOCK % 64 == 0, "listChunkRuns: geometry");
+    const uint32_t tid = threadIdx.x;
+    uint32_t pk[PER];                                               // bucket << 16 | rank in the chunk
+#pragma unroll
+    for (int u = 0; u < PER; u++) {
+        pk[u] = TAG_NONE;
+        if (t[u] != TAG_NONE) { const uint32_t b = t[u] - tagBase; pk[u] = (b << 16) | atomicAdd(&cnt[b], 1u); }
+    }
+    __syncthreads();
+    uint32_t c[PERB], g[PERB], sum = 0;
+#pragma unroll
+    for (int k = 0; k < PERB; k++) { const uint32_t b = tid * PERB + k; c[k] = cnt[b]; g[k] = c[k] ? reserve(b, c[k]) : 0u; sum += c[k]; }
+    const uint32_t incl = waveInclusiveScan(sum);
+    if (laneId() == 63) sWave[tid >> 6] = incl;
+    __syncthreads();
+    uint32_t run = incl - sum, total = 0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; w++) { const uint32_t v = sWave[w]; if (w < (int) (tid >> 6)) run += v; total += v; }
+#pragma unroll
+    for (int k = 0; k < PERB; k++) { const uint32_t b = tid * PERB + k; cnt[b] = run; delta[b] = g[k] - run; run += c[k]; }     // cnt: where the bucket begins in `stage`
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < PER; u++) if (pk[u] != TAG_NONE) stage[cnt[pk[u] >> 16] + (pk[u] & 0xFFFFu)] = (pk[u] & 0xFFFF0000u) | (uint32_t) (u * BLOCK + tid);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PERB; k++) cnt[tid * PERB + k] = 0;
+    for (uint32_t j = tid; j < total; j += BLOCK) { const uint32_t v = stage[j]; list[delta[v >> 16] + j] = (uint32_t) c0 + (v & 0xFFFFu); }
+    __syncthreads();
+}
+static inline size_t listRunsLdsBytes(int chunk, bool region) { return (size_t) chunk * 4 + (size_t) LP_MAXB * 4 * (region ? 3 : 2); }
+// the geometry kmermatch.hip launches at level 1 and at level 2: the largest chunk that fits a CU's LDS measured best at both
+// (profiles/linelist_ab_knobs.txt: a bucket's run of one chunk is 32 entries = one 128-byte line on average at 1024 buckets)
+constexpr int LR_BLOCK = 1024, LR_CHUNK = 32768, LR2_BLOCK = LR_BLOCK, LR2_CHUNK = LR_CHUNK;
+
+// (a') level 1 as runs: as tagScatterKernel, a bucket's entries of one chunk are reserved with one atomic on the bucket's cursor
+template <int BLOCK, int CHUNK>
+__global__ __launch_bounds__(BLOCK) void tagScatterRunsKernel(const uint32_t *__restrict__ tags, uint64_t nLines, uint32_t nb, uint32_t *__restrict__ cursor, uint32_t *__restrict__ list) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lrDyn[];
+    uint32_t *stage = reinterpret_cast<uint32_t *>(lrDyn), *cnt = stage + CHUNK, *delta = cnt + LP_MAXB;
+    __shared__ uint32_t sWave[BLOCK / 64];
+    for (uint32_t i = threadIdx.x; i < LP_MAXB; i += BLOCK) cnt[i] = 0;
+    __syncthreads();
+    for (uint64_t c0 = (uint64_t) blockIdx.x * CHUNK; c0 < nLines; c0 += (uint64_t) gridDim.x * CHUNK) {
+        uint32_t t[CHUNK / BLOCK];
+#pragma unroll
+        for (int u = 0; u < CHUNK / BLOCK; u++) {
+            const uint64_t i = c0 + (uint64_t) u * BLOCK + threadIdx.x;
+            t[u] = (i < nLines) ? __builtin_nontemporal_load(tags + i) : TAG_NONE;
+        }
+        listChunkRuns<BLOCK, CHUNK>(t, c0, 0u, list, stage, cnt, delta, sWave, [&](uint32_t b, uint32_t c) { return atomicAdd(&cursor[b], c); });
+    }
+}
+
 // bucket b of a single-level partition: its lines are list[beg[b] .. beg[b] + cnt[b])
 __global__ void listRangesKernel(const uint32_t *__restrict__ start, uint32_t nb, uint32_t *__restrict__ beg, uint32_t *__restrict__ cnt) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nb; i += gridDim.x * blockDim.x) { beg[i] = start[i]; cnt[i] = start[i + 1] - start[i]; }
@@ -482,6 +555,56 @@ __global__ __launch_bounds__(512) void tagSortRegionKernel(const uint32_t *__res
             sCnt[b] = 0;
         }
         __syncthreads();
+    }
+}
+// (b') level 2 as runs: the counting pass and the scan of tagSortRegionKernel, then the region's tags go through listChunkRuns chunk by chunk;
+// a fine bucket's running list position is kept by the thread that owns the bucket (no atomics beyond the ranks)
+template <int BLOCK, int CHUNK>
+__global__ __launch_bounds__(BLOCK) void tagSortRegionRunsKernel(const uint32_t *__restrict__ tags, const uint64_t *__restrict__ regionBeg, const uint64_t *__restrict__ regionEnd,
+                                                                 uint32_t nRegions, uint32_t nb2, uint32_t *__restrict__ list, uint32_t *__restrict__ fineBeg, uint32_t *__restrict__ fineCnt) {
+    constexpr int PER = CHUNK / BLOCK, PERB = LP_MAXB / BLOCK;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lrDyn[];
+    uint32_t *stage = reinterpret_cast<uint32_t *>(lrDyn), *cnt = stage + CHUNK, *delta = cnt + LP_MAXB, *pos = delta + LP_MAXB;
+    __shared__ uint32_t sWave[BLOCK / 64];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < LP_MAXB; i += BLOCK) cnt[i] = 0;
+    for (uint32_t g = blockIdx.x; g < nRegions; g += gridDim.x) {
+        const uint64_t r0 = regionBeg[g], r1 = regionEnd[g];
+        const uint32_t base = g * nb2;
+        for (uint32_t i = tid; i < LP_MAXB; i += BLOCK) pos[i] = 0;
+        __syncthreads();
+        for (uint64_t i = r0 + tid; i < r1; i += 4 * BLOCK) {
+            uint32_t t[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) t[u] = (i + (uint64_t) BLOCK * u < r1) ? tags[i + (uint64_t) BLOCK * u] : TAG_NONE;
+#pragma unroll
+            for (int u = 0; u < 4; u++) if (t[u] != TAG_NONE) atomicAdd(&pos[t[u] - base], 1u);
+        }
+        __syncthreads();
+        uint32_t c[PERB], sum = 0;
+#pragma unroll
+        for (int k = 0; k < PERB; k++) { c[k] = pos[tid * PERB + k]; sum += c[k]; }
+        const uint32_t incl = waveInclusiveScan(sum);
+        if (laneId() == 63) sWave[tid >> 6] = incl;
+        __syncthreads();
+        uint32_t ex = (uint32_t) r0 + incl - sum;                       // list positions are output line numbers: a region's list lies in its own range
+        for (uint32_t w = 0; w < (tid >> 6); w++) ex += sWave[w];
+#pragma unroll
+        for (int k = 0; k < PERB; k++) {
+            const uint32_t b = tid * PERB + k;
+            if (b < nb2) { fineBeg[base + b] = ex; fineCnt[base + b] = c[k]; }
+            pos[b] = ex; ex += c[k];
+        }
+        __syncthreads();
+        for (uint64_t c0 = r0; c0 < r1; c0 += CHUNK) {
+            uint32_t t[PER];
+#pragma unroll
+            for (int u = 0; u < PER; u++) {
+                const uint64_t i = c0 + (uint64_t) u * BLOCK + tid;
+                t[u] = (i < r1) ? tags[i] : TAG_NONE;
+            }
+            listChunkRuns<BLOCK, CHUNK>(t, c0, base, list, stage, cnt, delta, sWave, [&](uint32_t b, uint32_t n) { const uint32_t p = pos[b]; pos[b] = p + n; return p; });
+        }
     }
 }
 
