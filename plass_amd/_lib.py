@@ -21,6 +21,12 @@ def linclust_lib_path():
     return os.path.join(os.path.dirname(lib_path()), "libplasship_linclust.so")
 
 
+def subst_lib_path():
+    """the extension library with linclust's diagonal filter (rescorediagonal --rescore-mode 1) and result2repseq (include/plasship_ext/subst.h),
+    beside the other three"""
+    return os.path.join(os.path.dirname(lib_path()), "libplasship_subst.so")
+
+
 class PlasshipError(RuntimeError):
     pass
 
@@ -54,6 +60,11 @@ class RescoreStats(C.Structure):
 class _HammingParams(C.Structure):
     _fields_ = [("wrapped", C.c_int32), ("seq_id_thr", C.c_float), ("seq_id_mode", C.c_int32), ("cov_mode", C.c_int32),
                 ("cov_thr", C.c_float), ("min_aln_len", C.c_int32), ("eval_thr", C.c_double)]
+
+
+class _SubstParams(C.Structure):
+    _fields_ = [("eval_thr", C.c_double), ("seq_id_thr", C.c_float), ("cov_thr", C.c_float), ("cov_mode", C.c_int32), ("min_aln_len", C.c_int32),
+                ("score_per_col_thr", C.c_float)]
 
 
 class _LocalParams(C.Structure):
@@ -241,6 +252,13 @@ LINCLUST_SYMBOLS = [
     ("plasship_merged_free", None, [P, P]),
     ("plasship_clusters_read", C.c_int, [P, P, C.c_char_p, C.POINTER(P)]),
 ]
+# include/plasship_ext/subst.h (the extension library libplasship_subst.so: linclust's diagonal filter of the protein workflow, result2repseq)
+SUBST_SYMBOLS = [
+    ("plasship_rescore_subst", C.c_int, [P, P, P, C.POINTER(_SubstParams), C.POINTER(P), C.POINTER(RescoreStats)]),
+    ("plasship_rescore_subst_subset", C.c_int, [P, P, P, P, C.POINTER(_SubstParams), C.POINTER(P), C.POINTER(RescoreStats)]),
+    ("plasship_clusters_repseqs", C.c_int, [P, P, P, C.POINTER(P)]),
+    ("plasship_merged_repseqs", C.c_int, [P, P, P, C.POINTER(P)]),
+]
 # include/plasship_rccl.h (native RCCL communicator of a sharded run)
 RCCL_SYMBOLS = [
     ("plasship_rccl_get_unique_id", C.c_int, [P]),
@@ -299,6 +317,25 @@ def load_linclust_library():
             fn.argtypes = args
         lib.linclust = ext
     return lib.linclust
+
+
+def load_subst_library():
+    """the extension library with linclust's diagonal filter and result2repseq, loaded when it is first asked for (Context.rescore_subst,
+    Context.repseqs) behind the other three: its entry points are then reached as load_library().subst.<name>.  A missing library is an
+    error, there is no fall-back."""
+    lib = load_library()
+    if getattr(lib, "subst", None) is None:
+        load_linclust_library()
+        spath = subst_lib_path()
+        if not os.path.exists(spath):
+            raise PlasshipError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`" % spath)
+        ext = C.CDLL(spath)
+        for name, res, args in SUBST_SYMBOLS:
+            fn = getattr(ext, name)
+            fn.restype = res
+            fn.argtypes = args
+        lib.subst = ext
+    return lib.subst
 
 
 def resume_point(dir, num_iterations, name="assembly_"):
@@ -514,6 +551,28 @@ class Context:
             return Alignments(self, h, db, db), st
         _check(load_linclust_library().plasship_rescore_local(self.h, db.h, cands.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore_local")
         return Alignments(self, h, db, db), st
+
+    def rescore_subst(self, db, cands, min_seq_id=0.0, cov_mode=0, c=0.0, min_aln_len=0, e=1e-3, score_per_col_thr=None, subset=None):
+        """`rescorediagonal --rescore-mode 1` (the best local score on the diagonal, no positions: the filter step linclust runs on amino-acid
+        DBs) on a candidate list made on `db` -> (the kept lines as Candidates, RescoreStats).  Defaults = the reference module's.
+        score_per_col_thr and subset: as in rescore_local"""
+        h = P(); st = RescoreStats()
+        cp = _SubstParams(e, min_seq_id, c, cov_mode, min_aln_len, float("nan") if score_per_col_thr is None else score_per_col_thr)
+        if subset is not None:
+            _check(load_subst_library().plasship_rescore_subst_subset(self.h, db.h, cands.h, subset.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore_subst_subset")
+        else:
+            _check(load_subst_library().plasship_rescore_subst(self.h, db.h, cands.h, C.byref(cp), C.byref(h), C.byref(st)), "plasship_rescore_subst")
+        return Candidates(self, h, db, db), st
+
+    def repseqs(self, clusters, db=None):
+        """`result2repseq`: the representatives' sequences of a Clusters or MergedClusters of `db`, under their keys -> SeqDB"""
+        h = P()
+        db = db or clusters.db
+        if isinstance(clusters, MergedClusters):
+            _check(load_subst_library().plasship_merged_repseqs(self.h, clusters.h, db.h, C.byref(h)), "plasship_merged_repseqs")
+        else:
+            _check(load_subst_library().plasship_clusters_repseqs(self.h, clusters.h, db.h, C.byref(h)), "plasship_clusters_repseqs")
+        return SeqDB(self, h)
 
     def clust_greedy(self, db, cands_or_alns):
         """`clust --cluster-mode 2 | 3` (greedy incremental clustering: the longest sequence that lists a sequence represents it) on a

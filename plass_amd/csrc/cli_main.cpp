@@ -12,6 +12,7 @@
 #include "../../include/plasship.h"
 #include "../../include/plasship_ext/clust.h"
 #include "../../include/plasship_ext/linclust.h"
+#include "../../include/plasship_ext/subst.h"
 #include <chrono>
 #include <unistd.h>
 #include <cstdarg>
@@ -74,6 +75,7 @@ struct Flags {
     std::string dbOut, nuclAssemblyOut; int dbMode = 0, numIterationsNucl = 5, kNucl = 22, minAlnLenNucl = 0;
     int clusterMode = 0;                 // clust: Parameters::SET_COVER (not one of kMembers: the dump's lines are pinned as they are)
     float scorePerColThr = 0.0f;         // rescorediagonal-local --score-per-col-thr (our own flag; not one of kMembers either)
+    std::string repOut;                  // linclust-ungapped[-prot] --rep-out DB: the representatives' sequence DB (our own flag; not one of kMembers either)
     std::set<std::string> seen;
 };
 
@@ -176,11 +178,15 @@ enum : unsigned {
     NUCLASSEMBLE_CHAIN = 1u << 12, GUIDEDASSEMBLE_CHAIN = 1u << 13, CREATEDB_READS = 1u << 14, MERGEREADS = 1u << 15, RESCOREDIAGONAL_HAMMING = 1u << 16,
     ANY_ASSEMBLERESULTS = ASSEMBLERESULTS | NUCLASSEMBLERESULTS | GUIDEDASSEMBLERESULTS, CHAINS = ASSEMBLE_CHAIN | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN,
     CLUST_GREEDY = 1u << 17, LINCLUST_PRE = 1u << 18, RESCOREDIAGONAL_LOCAL = 1u << 19, MERGECLUSTERS_GREEDY = 1u << 20, LINCLUST_UNGAPPED = 1u << 21,
-    // (rescorediagonal-hamming and rescorediagonal-local take rescorediagonal's flag set, clust-greedy clust's; linclust-pre the union of its three steps',
-    //  linclust-ungapped the union of linclust-pre's and rescorediagonal-local's; mergeclusters-greedy has the reference's: --threads, --compressed, -v)
-    ANY_KMERMATCHER = KMERMATCHER | LINCLUST_PRE | LINCLUST_UNGAPPED, ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING | RESCOREDIAGONAL_LOCAL | LINCLUST_PRE | LINCLUST_UNGAPPED,
-    ANY_CLUST = CLUST_GREEDY | LINCLUST_PRE | LINCLUST_UNGAPPED,
-    ALL = 0x3FFFFFu
+    RESCOREDIAGONAL_SUBST = 1u << 22, LINCLUST_UNGAPPED_PROT = 1u << 23, CLUST_REPSEQ = 1u << 24,
+    // (rescorediagonal-hamming, rescorediagonal-local and rescorediagonal-subst take rescorediagonal's flag set, clust-greedy clust's; linclust-pre the union of its three steps',
+    //  linclust-ungapped the union of linclust-pre's and rescorediagonal-local's; mergeclusters-greedy has the reference's: --threads, --compressed, -v;
+    //  linclust-ungapped-prot has linclust-ungapped's set, clust-repseq result2repseq's: --db-load-mode, --compressed, --threads, -v)
+    ANY_LINCLUST_UNGAPPED = LINCLUST_UNGAPPED | LINCLUST_UNGAPPED_PROT,
+    ANY_KMERMATCHER = KMERMATCHER | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
+    ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING | RESCOREDIAGONAL_LOCAL | RESCOREDIAGONAL_SUBST | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
+    ANY_CLUST = CLUST_GREEDY | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
+    ALL = 0x1FFFFFFu
 };
 
 // ---- the flags: each once, with the modules that own it (its parameter vector in the reference; for the fused drivers the workflow's own),
@@ -236,8 +242,8 @@ static const Flag kFlags[] = {
     {"--spaced-kmer-mode", ANY_KMERMATCHER, ZERO}, {"--spaced-kmer-pattern", ANY_KMERMATCHER, EMPTY}, {"--adjust-kmer-len", ANY_KMERMATCHER, ZERO_BOOL}, {"--mask", ANY_KMERMATCHER, ZERO},
     {"--mask-lower-case", ANY_KMERMATCHER, ZERO}, {"--split-memory-limit", ANY_KMERMATCHER, IGNORED}, {"--include-only-extendable", ANY_KMERMATCHER, BOOL, M(onlyExt)},
     {"--wrapped-scoring", ANY_RESCOREDIAGONAL, BOOL, M(wrapped)}, {"--filter-hits", ANY_RESCOREDIAGONAL, BOOL, M(filterHits)}, {"-a", ANY_RESCOREDIAGONAL, BOOL, M(addBt)},
-    {"--add-self-matches", ANY_RESCOREDIAGONAL, BOOL, M(addSelf)}, {"--sort-results", ANY_RESCOREDIAGONAL, VALUE, M(sortResults)}, {"--db-load-mode", ANY_RESCOREDIAGONAL, IGNORED},
-    {"--score-per-col-thr", RESCOREDIAGONAL_LOCAL | LINCLUST_UNGAPPED, VALUE, M(scorePerColThr)},
+    {"--add-self-matches", ANY_RESCOREDIAGONAL, BOOL, M(addSelf)}, {"--sort-results", ANY_RESCOREDIAGONAL, VALUE, M(sortResults)}, {"--db-load-mode", ANY_RESCOREDIAGONAL | CLUST_REPSEQ, IGNORED},
+    {"--score-per-col-thr", RESCOREDIAGONAL_LOCAL | RESCOREDIAGONAL_SUBST | ANY_LINCLUST_UNGAPPED, VALUE, M(scorePerColThr)}, {"--rep-out", ANY_LINCLUST_UNGAPPED, VALUE, M(repOut)},
     {"--cluster-mode", ANY_CLUST, VALUE, M(clusterMode)}, {"--max-iterations", ANY_CLUST, IGNORED}, {"--similarity-type", ANY_CLUST, IGNORED},
     {"--gap-open", PROTEINALN2NUCL, NUCL, M(gapOpenNucl)}, {"--gap-extend", PROTEINALN2NUCL, NUCL, M(gapExtendNucl)},
     {"--min-length", EXTRACTORFS, VALUE, M(orfMin)}, {"--max-length", EXTRACTORFS, VALUE, M(orfMax)}, {"--max-gaps", EXTRACTORFS, VALUE, M(orfGaps)},
@@ -307,6 +313,12 @@ static plasship_local_params localParams(const Flags &f) {
     plasship_local_params p = {};
     p.eval_thr = f.evalThr; p.seq_id_thr = f.seqIdThr; p.seq_id_mode = f.seqIdMode; p.cov_thr = f.covThr; p.cov_mode = f.covMode; p.min_aln_len = f.minAlnLen;
     p.add_backtrace = f.addBt; p.score_per_col_thr = f.filterHits ? f.scorePerColThr : NAN;
+    return p;
+}
+static plasship_subst_params substParams(const Flags &f) {
+    plasship_subst_params p = {};
+    p.eval_thr = f.evalThr; p.seq_id_thr = f.seqIdThr; p.cov_thr = f.covThr; p.cov_mode = f.covMode; p.min_aln_len = f.minAlnLen;
+    p.score_per_col_thr = f.filterHits ? f.scorePerColThr : NAN;
     return p;
 }
 static plasship_assemble_params assembleParams(const Flags &f) {
@@ -541,6 +553,16 @@ static int validateRescoreLocal(Call &c) {
         return unsupported("plass-hip rescorediagonal-local: --filter-hits 1 needs --score-per-col-thr X (the reference's threshold table is not part of this build)\n");
     return c.pos.size() == 4 && c.pos[0] != c.pos[1] ? unsupported("plass-hip rescorediagonal-local: separate query and target DBs are not part of the GPU path (linclust uses one DB)\n") : 0;
 }
+// rescorediagonal-subst (our own name: `rescorediagonal --rescore-mode 1` keeps its answer): the filter step linclust runs on amino-acid DBs,
+// lib/mmseqs/data/workflow/linclust.sh:59-68.  --rescore-mode 0 --filter-hits 1 is the reference's own way into mode 1 (rescorediagonal.cpp:95-99, with
+// a warning): left to the reference.  The threshold of --filter-hits 1 comes with our own --score-per-col-thr, as for rescorediagonal-local
+static int validateRescoreSubst(Call &c) {
+    if (c.f.rescoreMode != 1) return unsupported("plass-hip rescorediagonal-subst: --rescore-mode %d is not this module's (1, the substitution score, only)\n", c.f.rescoreMode);
+    if (c.f.wrapped || c.f.sortResults > 0) return unsupported("plass-hip rescorediagonal-subst: --wrapped-scoring 1 / --sort-results are not part of the GPU path\n");
+    if (c.f.filterHits && !c.f.seen.count("--score-per-col-thr"))
+        return unsupported("plass-hip rescorediagonal-subst: --filter-hits 1 needs --score-per-col-thr X (the reference's threshold table is not part of this build)\n");
+    return c.pos.size() == 4 && c.pos[0] != c.pos[1] ? unsupported("plass-hip rescorediagonal-subst: separate query and target DBs are not part of the GPU path (linclust uses one DB)\n") : 0;
+}
 // clust-greedy (our own name: `clust` stays with the reference): clust's greedy modes, Parameters::GREEDY = 2 and GREEDY_MEM = 3, which both run
 // greedyIncrementalLowMem (Clustering.cpp:42-47).  The module's default is set cover: a call without --cluster-mode is the reference's.
 static int validateClustMode(Call &c) {
@@ -577,8 +599,22 @@ static int validateLinclustUngapped(Call &c) {
     if (c.f.filterHits && !c.f.seen.count("--score-per-col-thr"))
         return unsupported("plass-hip linclust-ungapped: the workflow's alignment step runs with --filter-hits 1, which needs --score-per-col-thr X (the reference's threshold table is not part of this build); or give --filter-hits 0\n");
     if (c.pos.size() == 2 && probeDbtype(c.pos[0]) == PLASSHIP_DBTYPE_AMINO_ACIDS)
-        return unsupported("plass-hip linclust-ungapped: a protein DB is not part of the GPU path (nucleotide DBs only: the protein workflow has a filter step more)\n");
-    return 0;
+        return unsupported("plass-hip linclust-ungapped: a protein DB is not part of the GPU path (nucleotide DBs only: the protein workflow has a filter step more, see linclust-ungapped-prot)\n");
+    return !c.f.repOut.empty() && existsAlready(c.f.repOut) ? EXIT_FAILURE : 0;
+}
+// linclust-ungapped-prot: linclust.sh with --alignment-mode 4 and FILTER=1 (amino-acid DBs, Linclust.cpp:95): the mode 1 filter step between the
+// subset of the prefilter list and the alignment.  Both rescore steps run with --filter-hits 1 and look their threshold up with the same
+// --min-seq-id, -c and --cov-mode (Linclust.cpp:116-127), so one --score-per-col-thr serves both
+static int validateLinclustUngappedProt(Call &c) {
+    if (const int rc = validateClustMode(c)) return rc;
+    if (const int rc = validateKmermatcher(c)) return rc;
+    if (c.f.seen.count("--rescore-mode") && c.f.rescoreMode != 2) return unsupported("plass-hip linclust-ungapped-prot: --rescore-mode %d is not this driver's (its alignment step is mode 2)\n", c.f.rescoreMode);
+    if (c.f.wrapped || c.f.sortResults > 0) return unsupported("plass-hip linclust-ungapped-prot: --wrapped-scoring 1 / --sort-results are not part of the GPU path\n");
+    if (c.f.filterHits && !c.f.seen.count("--score-per-col-thr"))
+        return unsupported("plass-hip linclust-ungapped-prot: the workflow's filter and alignment steps run with --filter-hits 1, which needs --score-per-col-thr X (the reference's threshold table is not part of this build); or give --filter-hits 0\n");
+    if (c.pos.size() == 2 && probeDbtype(c.pos[0]) == PLASSHIP_DBTYPE_NUCLEOTIDES)
+        return unsupported("plass-hip linclust-ungapped-prot: a nucleotide DB is not this driver's (the nucleotide workflow has no filter step: linclust-ungapped)\n");
+    return !c.f.repOut.empty() && existsAlready(c.f.repOut) ? EXIT_FAILURE : 0;
 }
 // Requests that are valid for the reference and lie outside the GPU path are all refused in validate(), before the dry-run exit and before anything
 // is read or written (data/nuclassemble.sh:41,145 calls `concatdbs ... --preserve-keys` whenever circular contigs exist; with exit
@@ -706,6 +742,61 @@ static int runRescoreLocal(Call &c) {             // (query and target are one D
     fprintf(stdout, "scored: %llu kept: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_scored, (unsigned long long) st.n_accepted, st.ms_kernel);
     return KW(plasship_alns_write(ctx, al, pos[3].c_str())) ? fail("rescorediagonal-local") : EXIT_SUCCESS;
 }
+static int runRescoreSubst(Call &c) {             // (query and target are one DB: validateRescoreSubst)
+    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
+    SeqDb db(ctx); Cands cands(ctx), kept(ctx);
+    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out())) || K(plasship_cands_read(ctx, db, db, pos[2].c_str(), cands.out()))) return fail("rescorediagonal-subst");
+    const plasship_subst_params p = substParams(c.f); plasship_rescore_stats st = {};
+    if (K(plasship_rescore_subst(ctx, db, cands, &p, kept.out(), &st))) return fail("rescorediagonal-subst");
+    fprintf(stdout, "scored: %llu kept: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_scored, (unsigned long long) st.n_accepted, st.ms_kernel);
+    return KW(plasship_cands_write(ctx, kept, db, pos[3].c_str())) ? fail("rescorediagonal-subst") : EXIT_SUCCESS;
+}
+// DBReader::softlinkDb(seqDB, outDB, SEQUENCE_ANCILLARY) (result2repseq.cpp:54, DBReader.cpp:1089-1154): absolute soft links to the sequence DB's header,
+// lookup, source and taxonomy files where those exist
+static int linkAncillary(const std::string &seqDb, const std::string &outDb) {
+    for (const char *sfx : {"_h", "_h.index", "_h.dbtype", ".lookup", ".source", "_mapping", "_names.dmp", "_nodes.dmp", "_merged.dmp", "_taxonomy"}) {
+        const std::string file = seqDb + sfx, link = outDb + sfx;
+        struct stat st;
+        if (stat(file.c_str(), &st) != 0) continue;
+        char *t = realpath(file.c_str(), nullptr);
+        if (!t) { fprintf(stdout, "Could not get realpath of %s!\n", file.c_str()); return EXIT_FAILURE; }
+        if (lstat(link.c_str(), &st) == 0) unlink(link.c_str());
+        const bool ok = symlink(t, link.c_str()) == 0;
+        free(t);
+        if (!ok) { fprintf(stdout, "Could not create symlink of %s!\n", file.c_str()); return EXIT_FAILURE; }
+    }
+    return 0;
+}
+// every entry of a cluster DB on disk starts with its own key (what Clustering::writeData and mergeclusters write; result2repseq takes the FIRST key,
+// plasship_clusters_repseqs the entry's) and none is empty (the reference writes no sequence for one): 1, 0 if not, -1 if the files cannot be read
+static int clusterListsStartWithOwnKey(const std::string &clu) {
+    FILE *fi = fopen((clu + ".index").c_str(), "rb"), *fd = fopen(clu.c_str(), "rb");
+    int ok = fi && fd ? 1 : -1;
+    unsigned long long key, off, len;
+    while (ok == 1 && fscanf(fi, "%llu %llu %llu", &key, &off, &len) == 3) {
+        char buf[32] = {0};
+        if (len <= 1 || fseeko(fd, (off_t) off, SEEK_SET) != 0 || fread(buf, 1, std::min<size_t>(sizeof(buf) - 1, (size_t) len), fd) == 0) { ok = 0; break; }
+        char *end = nullptr; const unsigned long long first = strtoull(buf, &end, 10);
+        if (end == buf || first != key) ok = 0;
+    }
+    if (fi) fclose(fi);
+    if (fd) fclose(fd);
+    return ok;
+}
+static int runClustRepseq(Call &c) {              // result2repseq: <seqDB> <cluDB> <outDB>
+    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
+    SeqDb db(ctx), rep(ctx); Clusters cl(ctx);
+    if (clusterListsStartWithOwnKey(pos[1]) == 0) return unsupported("plass-hip clust-repseq: %s has an empty entry or a list that does not start with its own key\n", pos[1].c_str());
+    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out()))) return fail("clust-repseq");
+    // (a cluster DB the reader cannot take — a key listed twice, a list that does not start with its own key — is left to the reference: nothing has been written)
+    if (K(plasship_clusters_read(ctx, db, pos[1].c_str(), cl.out())))
+        return g_lastRc == PLASSHIP_ERR_ARG ? unsupported("plass-hip clust-repseq: %s\n", plasship_last_error()) : fail("clust-repseq");
+    if (K(plasship_clusters_repseqs(ctx, cl, db, rep.out()))) return fail("clust-repseq");
+    size_t n = 0; plasship_seqdb_info(rep, &n, nullptr, nullptr, nullptr, nullptr);
+    fprintf(stdout, "representatives: %zu\n", n);
+    if (KW(plasship_seqdb_write(ctx, rep, pos[2].c_str()))) return fail("clust-repseq");
+    return linkAncillary(pos[0], pos[2]);
+}
 static long indexLines(const std::string &db) {       // entries of a DB on disk; -1: no index
     FILE *fi = fopen((db + ".index").c_str(), "rb"); if (!fi) return -1;
     long n = 0; char buf[65536]; size_t got;
@@ -759,25 +850,40 @@ static int runMergeclusters(Call &c) {            // (exactly two clusterings: v
     fprintf(stdout, "sequences: %llu clusters: %llu\n", (unsigned long long) n, (unsigned long long) nC);
     return KW(plasship_merged_write(ctx, mg, db, pos[1].c_str())) ? fail("mergeclusters-greedy") : EXIT_SUCCESS;
 }
-static int runLinclustUngapped(Call &c) {         // linclust-pre's chain, then mode 2 on the representatives -> clust -> mergeclusters, on handles
-    plasship_ctx *ctx = c.ctx; const Flags &f = c.f;
+// linclust-pre's chain, then (linclust-ungapped-prot: the mode 1 filter on the representatives, then) mode 2 on the representatives -> clust -> mergeclusters, on handles
+static int runLinclustUngapped(Call &c) {
+    plasship_ctx *ctx = c.ctx; const Flags &f = c.f; const char *name = c.m->name; const bool prot = c.m->id == LINCLUST_UNGAPPED_PROT;
     SeqDb db(ctx); Cands pref(ctx), rescored(ctx), filtered(ctx); Clusters pre(ctx), cl(ctx); Alns al(ctx); Merged mg(ctx);
-    if (K(plasship_seqdb_read(ctx, c.pos[0].c_str(), db.out()))) return fail("linclust-ungapped");
-    if (dbtypeOf(db) != PLASSHIP_DBTYPE_NUCLEOTIDES) return unsupported("plass-hip linclust-ungapped: nucleotide DBs only\n");
-    const plasship_kmermatch_params kp = kmermatchParams(f, f.scaleNucl); plasship_kmermatch_stats ks = {};
+    if (K(plasship_seqdb_read(ctx, c.pos[0].c_str(), db.out()))) return fail(name);
+    if (!prot && dbtypeOf(db) != PLASSHIP_DBTYPE_NUCLEOTIDES) return unsupported("plass-hip linclust-ungapped: nucleotide DBs only\n");
+    if (prot && dbtypeOf(db) != PLASSHIP_DBTYPE_AMINO_ACIDS) return unsupported("plass-hip linclust-ungapped-prot: amino-acid DBs only\n");
+    const plasship_kmermatch_params kp = kmermatchParams(f, prot ? f.scaleAA : f.scaleNucl); plasship_kmermatch_stats ks = {};
     plasship_hamming_params hp = hammingParams(f);      // Linclust.cpp:106-111: the Hamming step never goes below 0.5 in seq. id. and coverage
     hp.seq_id_thr = std::max(0.5f, f.seqIdThr); hp.cov_thr = std::max(0.5f, f.covThr);
-    const plasship_local_params lp = localParams(f); plasship_rescore_stats rs = {}, ls = {}; plasship_clust_stats st = {}, st2 = {};
+    const plasship_local_params lp = localParams(f); const plasship_subst_params sp = substParams(f);
+    plasship_rescore_stats rs = {}, fs = {}, ls = {}; plasship_clust_stats st = {}, st2 = {};
     if (K(plasship_kmermatch(ctx, db, &kp, pref.out(), &ks)) || K(plasship_rescore_hamming(ctx, db, db, pref, &hp, rescored.out(), &rs)) ||
-        K(plasship_clust_greedy_cands(ctx, db, rescored, pre.out(), &st)) || K(plasship_cands_filter(ctx, pref, pre, filtered.out())) ||
-        K(plasship_rescore_local_subset(ctx, db, filtered, pre, &lp, al.out(), &ls)) || K(plasship_clust_greedy_alns(ctx, db, al, cl.out(), &st2)) ||
-        K(plasship_clusters_merge(ctx, db, pre, cl, mg.out()))) return fail("linclust-ungapped");
+        K(plasship_clust_greedy_cands(ctx, db, rescored, pre.out(), &st)) || K(plasship_cands_filter(ctx, pref, pre, filtered.out()))) return fail(name);
+    if (prot) {                                   // linclust.sh:59-68: pref_filter2 -> pref_rescore2
+        Cands passed(ctx);
+        if (K(plasship_rescore_subst_subset(ctx, db, filtered, pre, &sp, passed.out(), &fs))) return fail(name);
+        filtered = std::move(passed);
+    }
+    if (K(plasship_rescore_local_subset(ctx, db, filtered, pre, &lp, al.out(), &ls)) || K(plasship_clust_greedy_alns(ctx, db, al, cl.out(), &st2)) ||
+        K(plasship_clusters_merge(ctx, db, pre, cl, mg.out()))) return fail(name);
     fprintf(stdout, "candidates: %llu scored: %llu kept: %llu | aligned: %llu kept: %llu | kernel ms: hamming %.3f local %.3f\n", (unsigned long long) ks.n_candidates,
             (unsigned long long) rs.n_scored, (unsigned long long) rs.n_accepted, (unsigned long long) ls.n_scored, (unsigned long long) ls.n_accepted, rs.ms_kernel, ls.ms_kernel);
+    if (prot) fprintf(stdout, "filtered: %llu kept: %llu | kernel ms: subst %.3f\n", (unsigned long long) fs.n_scored, (unsigned long long) fs.n_accepted, fs.ms_kernel);
     printClustStats(st);
     uint64_t n = 0, nC = 0; plasship_merged_count(mg, &n, &nC);
     fprintf(stdout, "sequences: %llu clusters: %llu\n", (unsigned long long) n, (unsigned long long) nC);
-    return KW(plasship_merged_write(ctx, mg, db, c.pos[1].c_str())) ? fail("linclust-ungapped") : EXIT_SUCCESS;
+    if (KW(plasship_merged_write(ctx, mg, db, c.pos[1].c_str()))) return fail(name);
+    if (!f.repOut.empty()) {                      // result2repseq of the merged clustering, with its soft links (guidedNuclAssemble.sh:182-186)
+        SeqDb rep(ctx);
+        if (K(plasship_merged_repseqs(ctx, mg, db, rep.out())) || KW(plasship_seqdb_write(ctx, rep, f.repOut.c_str()))) return fail(name);
+        if (const int rc = linkAncillary(c.pos[0], f.repOut)) return rc;
+    }
+    return EXIT_SUCCESS;
 }
 static int runAssembleresults(Call &c) {          // assembleresults and nuclassembleresults
     plasship_ctx *ctx = c.ctx; SeqDb db(ctx); Alns al(ctx); SeqDb o(ctx);
@@ -1048,6 +1154,10 @@ static const Module kModules[] = {
     {"linclust-pre", LINCLUST_PRE, 3, "linclust-pre <i:sequenceDB> <o:preClusterDB> <o:prefilterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; }, validateLinclustPre, runLinclustPre},
     {"mergeclusters-greedy", MERGECLUSTERS_GREEDY, 4, "mergeclusters-greedy <i:sequenceDB> <o:clusterDB> <i:clusterDB1> <i:clusterDB2>", nullptr, validateMergeclusters, runMergeclusters},
     {"linclust-ungapped", LINCLUST_UNGAPPED, 2, "linclust-ungapped <i:sequenceDB> <o:clusterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; f.filterHits = 1; }, validateLinclustUngapped, runLinclustUngapped},
+    // the protein workflow's filter step, the driver with it, and result2repseq (our own names: the reference's keep their answers)
+    {"rescorediagonal-subst", RESCOREDIAGONAL_SUBST, 4, "rescorediagonal-subst <i:queryDB> <i:targetDB> <i:prefDB> <o:prefDB>", nullptr, validateRescoreSubst, runRescoreSubst},
+    {"linclust-ungapped-prot", LINCLUST_UNGAPPED_PROT, 2, "linclust-ungapped-prot <i:sequenceDB> <o:clusterDB> [--rep-out DB]", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; f.filterHits = 1; }, validateLinclustUngappedProt, runLinclustUngapped},
+    {"clust-repseq", CLUST_REPSEQ, 3, "clust-repseq <i:sequenceDB> <i:clusterDB> <o:sequenceDB>", nullptr, nullptr, runClustRepseq},
     {"assembleresults", ASSEMBLERESULTS, 3, "assembleresults <i:sequenceDB> <i:alnResult> <o:reprSeqDB>", nullptr, nullptr, runAssembleresults},
     {"nuclassembleresults", NUCLASSEMBLERESULTS, 3, "nuclassembleresults <i:sequenceDB> <i:alnResult> <o:reprSeqDB>", nullptr, nullptr, runAssembleresults},
     {"guidedassembleresults", GUIDEDASSEMBLERESULTS, 5, "guidedassembleresults <i:nuclSequenceDB> <i:aaSequenceDB> <i:nuclAlnResult> <o:nuclAssembly> <o:aaAssembly>", nullptr, nullptr, runGuidedassembleresults},

@@ -21,16 +21,10 @@
 #include "../../include/plasship_ext/linclust.h"
 #include "device_utils.hpp"
 #include "host_util.hpp"
+#include "merged.hpp"
 #include <algorithm>
 #include <cstring>
 #include <memory>
-
-struct plasship_merged {
-    size_t n = 0;                  // == DB size
-    uint64_t nClusters = 0;
-    uint64_t dbGen = 0;
-    plasship::DevBuf d_pairs;      // uint64 [n]: representative id << 32 | member id, in the order of the merged DB
-};
 
 namespace plasship {
 
