@@ -24,7 +24,8 @@ typedef struct plasship_clusters plasship_clusters; /* clustering result (repres
  *      records of an alignment list (plasship_rescore, plasship_aln2nucl, plasship_alns_read: dbtype 5; identity pairs left as stubs are not
  *      scored for this); scores are not read.  The list must have been made on `db` and hold db's number of queries: PLASSHIP_ERR_ARG otherwise
  *      (the reference exits there too).  A context with a communicator of more than one rank: PLASSHIP_ERR_UNSUPPORTED.  Ids are 32-bit.
- *      Set cover (--cluster-mode 0) and connected component (1) are not implemented.
+ *      Connected component (--cluster-mode 1) is in libplasship_cc.so (cc.h).  Set cover (--cluster-mode 0) stays with the reference: setCover is a
+ *      bucket-queue greedy whose ties follow the history of swaps in decreaseClustersize, which no parallel form reproduces byte for byte.
  *      plasship_clusters_download: db.n pairs (representative key, member key), sorted by representative key, then member key.
  *      plasship_clusters_write: the DB Clustering::writeData writes (dbtype 6): one entry per representative under its key — its own key, then
  *      the other members' keys ascending, one per line — in one data file in key order; the text is laid out on the device. ---- */

@@ -6,9 +6,9 @@ so the parity tests read like invocations of the reference modules.  There is no
 in-tree HIP library (plass_amd/libplasship.so) or without a GPU every entry point raises.
 """
 from ._lib import (  # noqa: F401
-    PlasshipError, Context, SeqDB, Candidates, Alignments, Clusters, MergedClusters, ClustStats,
-    KmermatchParams, RescoreParams, AssembleParams, OrfParams, OrfHeaders, SynthParams, MergeParams, MergeStats, CreatedbStats, lib_path, clust_lib_path, linclust_lib_path, subst_lib_path, load_library, resume_point,
+    PlasshipError, Context, SeqDB, Candidates, Alignments, Clusters, MergedClusters, ClustStats, CcStats,
+    KmermatchParams, RescoreParams, AssembleParams, OrfParams, OrfHeaders, SynthParams, MergeParams, MergeStats, CreatedbStats, lib_path, clust_lib_path, linclust_lib_path, subst_lib_path, cc_lib_path, load_library, resume_point,
 )
 
-__all__ = ["PlasshipError", "Context", "SeqDB", "Candidates", "Alignments", "Clusters", "MergedClusters", "ClustStats", "KmermatchParams",
-           "RescoreParams", "AssembleParams", "OrfParams", "OrfHeaders", "SynthParams", "MergeParams", "MergeStats", "CreatedbStats", "lib_path", "clust_lib_path", "linclust_lib_path", "subst_lib_path", "load_library", "resume_point"]
+__all__ = ["PlasshipError", "Context", "SeqDB", "Candidates", "Alignments", "Clusters", "MergedClusters", "ClustStats", "CcStats", "KmermatchParams",
+           "RescoreParams", "AssembleParams", "OrfParams", "OrfHeaders", "SynthParams", "MergeParams", "MergeStats", "CreatedbStats", "lib_path", "clust_lib_path", "linclust_lib_path", "subst_lib_path", "cc_lib_path", "load_library", "resume_point"]

@@ -27,6 +27,11 @@ def subst_lib_path():
     return os.path.join(os.path.dirname(lib_path()), "libplasship_subst.so")
 
 
+def cc_lib_path():
+    """the extension library with connected-component clustering (clust --cluster-mode 1, include/plasship_ext/cc.h), beside the others"""
+    return os.path.join(os.path.dirname(lib_path()), "libplasship_cc.so")
+
+
 class PlasshipError(RuntimeError):
     pass
 
@@ -75,6 +80,11 @@ class _LocalParams(C.Structure):
 class ClustStats(C.Structure):
     _fields_ = [("n_sequences", C.c_uint64), ("n_edges", C.c_uint64), ("n_clusters", C.c_uint64), ("n_promoted", C.c_uint64),
                 ("n_long_queries", C.c_uint64), ("ms_kernel", C.c_float)]
+
+
+class CcStats(C.Structure):
+    _fields_ = [("n_sequences", C.c_uint64), ("n_edges", C.c_uint64), ("n_clusters", C.c_uint64), ("n_missing_links", C.c_uint64),
+                ("n_hook_rounds", C.c_uint32), ("n_bfs_levels", C.c_uint32), ("ms_kernel", C.c_float)]
 
 
 class _AssembleParams(C.Structure):
@@ -259,6 +269,11 @@ SUBST_SYMBOLS = [
     ("plasship_clusters_repseqs", C.c_int, [P, P, P, C.POINTER(P)]),
     ("plasship_merged_repseqs", C.c_int, [P, P, P, C.POINTER(P)]),
 ]
+# include/plasship_ext/cc.h (the extension library libplasship_cc.so: connected-component clustering)
+CC_SYMBOLS = [
+    ("plasship_clust_connected_cands", C.c_int, [P, P, P, C.c_int, C.POINTER(P), C.POINTER(CcStats)]),
+    ("plasship_clust_connected_alns", C.c_int, [P, P, P, C.c_int, C.POINTER(P), C.POINTER(CcStats)]),
+]
 # include/plasship_rccl.h (native RCCL communicator of a sharded run)
 RCCL_SYMBOLS = [
     ("plasship_rccl_get_unique_id", C.c_int, [P]),
@@ -336,6 +351,24 @@ def load_subst_library():
             fn.argtypes = args
         lib.subst = ext
     return lib.subst
+
+
+def load_cc_library():
+    """the extension library with connected-component clustering, loaded when it is first asked for (Context.clust_connected) behind the
+    library it takes its handles from: its entry points are then reached as load_library().cc.<name>.  A missing library is an error, there
+    is no fall-back."""
+    lib = load_library()
+    if getattr(lib, "cc", None) is None:
+        cpath = cc_lib_path()
+        if not os.path.exists(cpath):
+            raise PlasshipError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`" % cpath)
+        ext = C.CDLL(cpath)
+        for name, res, args in CC_SYMBOLS:
+            fn = getattr(ext, name)
+            fn.restype = res
+            fn.argtypes = args
+        lib.cc = ext
+    return lib.cc
 
 
 def resume_point(dir, num_iterations, name="assembly_"):
@@ -582,6 +615,19 @@ class Context:
             _check(self.lib.clust.plasship_clust_greedy_alns(self.h, db.h, cands_or_alns.h, C.byref(h), C.byref(st)), "plasship_clust_greedy_alns")
         else:
             _check(self.lib.clust.plasship_clust_greedy_cands(self.h, db.h, cands_or_alns.h, C.byref(h), C.byref(st)), "plasship_clust_greedy_cands")
+        return Clusters(self, h, db), st
+
+    def clust_connected(self, db, cands_or_alns, max_iterations=1000):
+        """`clust --cluster-mode 1` (connected component: the components of the list, each under its member with the largest symmetric list,
+        ties to the shorter sequence and then the larger key) on a candidate list or an alignment list made on `db` -> (Clusters, CcStats).
+        max_iterations: --max-iterations, the reference's default; where a sequence lies more than max_iterations + 1 steps from its
+        representative the reference's answer depends on its visiting order and the call raises (PLASSHIP_ERR_UNSUPPORTED)"""
+        h = P(); st = CcStats()
+        ext = load_cc_library()
+        if isinstance(cands_or_alns, Alignments):
+            _check(ext.plasship_clust_connected_alns(self.h, db.h, cands_or_alns.h, int(max_iterations), C.byref(h), C.byref(st)), "plasship_clust_connected_alns")
+        else:
+            _check(ext.plasship_clust_connected_cands(self.h, db.h, cands_or_alns.h, int(max_iterations), C.byref(h), C.byref(st)), "plasship_clust_connected_cands")
         return Clusters(self, h, db), st
 
     def read_clusters(self, db, path):

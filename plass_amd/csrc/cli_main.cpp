@@ -13,6 +13,7 @@
 #include "../../include/plasship_ext/clust.h"
 #include "../../include/plasship_ext/linclust.h"
 #include "../../include/plasship_ext/subst.h"
+#include "../../include/plasship_ext/cc.h"
 #include <chrono>
 #include <unistd.h>
 #include <cstdarg>
@@ -76,6 +77,7 @@ struct Flags {
     int clusterMode = 0;                 // clust: Parameters::SET_COVER (not one of kMembers: the dump's lines are pinned as they are)
     float scorePerColThr = 0.0f;         // rescorediagonal-local --score-per-col-thr (our own flag; not one of kMembers either)
     std::string repOut;                  // linclust-ungapped[-prot] --rep-out DB: the representatives' sequence DB (our own flag; not one of kMembers either)
+    int maxIterations = 1000;            // clust --max-iterations, read by connected component only (Parameters.cpp:2171; not one of kMembers either)
     std::set<std::string> seen;
 };
 
@@ -178,15 +180,15 @@ enum : unsigned {
     NUCLASSEMBLE_CHAIN = 1u << 12, GUIDEDASSEMBLE_CHAIN = 1u << 13, CREATEDB_READS = 1u << 14, MERGEREADS = 1u << 15, RESCOREDIAGONAL_HAMMING = 1u << 16,
     ANY_ASSEMBLERESULTS = ASSEMBLERESULTS | NUCLASSEMBLERESULTS | GUIDEDASSEMBLERESULTS, CHAINS = ASSEMBLE_CHAIN | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN,
     CLUST_GREEDY = 1u << 17, LINCLUST_PRE = 1u << 18, RESCOREDIAGONAL_LOCAL = 1u << 19, MERGECLUSTERS_GREEDY = 1u << 20, LINCLUST_UNGAPPED = 1u << 21,
-    RESCOREDIAGONAL_SUBST = 1u << 22, LINCLUST_UNGAPPED_PROT = 1u << 23, CLUST_REPSEQ = 1u << 24,
+    RESCOREDIAGONAL_SUBST = 1u << 22, LINCLUST_UNGAPPED_PROT = 1u << 23, CLUST_REPSEQ = 1u << 24, CLUST_CONNECTED = 1u << 25,
     // (rescorediagonal-hamming, rescorediagonal-local and rescorediagonal-subst take rescorediagonal's flag set, clust-greedy clust's; linclust-pre the union of its three steps',
     //  linclust-ungapped the union of linclust-pre's and rescorediagonal-local's; mergeclusters-greedy has the reference's: --threads, --compressed, -v;
-    //  linclust-ungapped-prot has linclust-ungapped's set, clust-repseq result2repseq's: --db-load-mode, --compressed, --threads, -v)
+    //  linclust-ungapped-prot has linclust-ungapped's set, clust-repseq result2repseq's: --db-load-mode, --compressed, --threads, -v; clust-connected clust's)
     ANY_LINCLUST_UNGAPPED = LINCLUST_UNGAPPED | LINCLUST_UNGAPPED_PROT,
     ANY_KMERMATCHER = KMERMATCHER | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
     ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING | RESCOREDIAGONAL_LOCAL | RESCOREDIAGONAL_SUBST | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
-    ANY_CLUST = CLUST_GREEDY | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
-    ALL = 0x1FFFFFFu
+    ANY_CLUST = CLUST_GREEDY | CLUST_CONNECTED | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
+    ALL = 0x3FFFFFFu
 };
 
 // ---- the flags: each once, with the modules that own it (its parameter vector in the reference; for the fused drivers the workflow's own),
@@ -244,7 +246,7 @@ static const Flag kFlags[] = {
     {"--wrapped-scoring", ANY_RESCOREDIAGONAL, BOOL, M(wrapped)}, {"--filter-hits", ANY_RESCOREDIAGONAL, BOOL, M(filterHits)}, {"-a", ANY_RESCOREDIAGONAL, BOOL, M(addBt)},
     {"--add-self-matches", ANY_RESCOREDIAGONAL, BOOL, M(addSelf)}, {"--sort-results", ANY_RESCOREDIAGONAL, VALUE, M(sortResults)}, {"--db-load-mode", ANY_RESCOREDIAGONAL | CLUST_REPSEQ, IGNORED},
     {"--score-per-col-thr", RESCOREDIAGONAL_LOCAL | RESCOREDIAGONAL_SUBST | ANY_LINCLUST_UNGAPPED, VALUE, M(scorePerColThr)}, {"--rep-out", ANY_LINCLUST_UNGAPPED, VALUE, M(repOut)},
-    {"--cluster-mode", ANY_CLUST, VALUE, M(clusterMode)}, {"--max-iterations", ANY_CLUST, IGNORED}, {"--similarity-type", ANY_CLUST, IGNORED},
+    {"--cluster-mode", ANY_CLUST, VALUE, M(clusterMode)}, {"--max-iterations", ANY_CLUST, VALUE, M(maxIterations)}, {"--similarity-type", ANY_CLUST, IGNORED},
     {"--gap-open", PROTEINALN2NUCL, NUCL, M(gapOpenNucl)}, {"--gap-extend", PROTEINALN2NUCL, NUCL, M(gapExtendNucl)},
     {"--min-length", EXTRACTORFS, VALUE, M(orfMin)}, {"--max-length", EXTRACTORFS, VALUE, M(orfMax)}, {"--max-gaps", EXTRACTORFS, VALUE, M(orfGaps)},
     {"--contig-start-mode", EXTRACTORFS, VALUE, M(contigStart)}, {"--contig-end-mode", EXTRACTORFS, VALUE, M(contigEnd)}, {"--orf-start-mode", EXTRACTORFS, VALUE, M(orfStart)},
@@ -569,12 +571,35 @@ static int validateClustMode(Call &c) {
     return c.f.clusterMode != 2 && c.f.clusterMode != 3
         ? unsupported("plass-hip %s: --cluster-mode %d is not part of the GPU path (2 and 3, the greedy modes, only)\n", c.m->name, c.f.clusterMode) : 0;
 }
-static int validateClustGreedy(Call &c) {
-    if (const int rc = validateClustMode(c)) return rc;
+static int validateClustResultDb(Call &c) {
     if (c.pos.size() != 3) return 0;
     const int dbtype = probeDbtype(c.pos[1]);     // prefilter DBs (7, 14) and alignment DBs (5)
     return dbtype >= 0 && dbtype != PLASSHIP_DBTYPE_PREFILTER_RES && dbtype != PLASSHIP_DBTYPE_PREFILTER_REV_RES && dbtype != PLASSHIP_DBTYPE_ALIGNMENT_RES
-        ? unsupported("plass-hip clust-greedy: a result DB of type %d is not part of the GPU path (prefilter and alignment DBs only)\n", dbtype) : 0;
+        ? unsupported("plass-hip %s: a result DB of type %d is not part of the GPU path (prefilter and alignment DBs only)\n", c.m->name, dbtype) : 0;
+}
+static int validateClustGreedy(Call &c) {
+    if (const int rc = validateClustMode(c)) return rc;
+    return validateClustResultDb(c);
+}
+// connected component, Parameters::CONNECTED_COMPONENT = 1: --max-iterations is the depth of its breadth-first search and matches ^[1-9]{1}[0-9]*$
+// in the reference (Parameters.cpp:91), which ends with "Error in argument" otherwise
+static int validateMaxIterations(Call &c) {
+    if (c.f.maxIterations >= 1) return 0;
+    fprintf(stdout, "Error in argument --max-iterations\n");
+    return EXIT_FAILURE;
+}
+// clust-connected (our own name: `clust` stays with the reference): the one mode this module is; a call without --cluster-mode is the reference's set cover
+static int validateClustConnected(Call &c) {
+    if (c.f.clusterMode != 1)
+        return unsupported("plass-hip clust-connected: --cluster-mode %d is not this module's (1, connected component, only; 2 and 3: clust-greedy)\n", c.f.clusterMode);
+    if (const int rc = validateMaxIterations(c)) return rc;
+    return validateClustResultDb(c);
+}
+// the fused drivers run both `clust` calls of linclust.sh:35,82 in the mode they are given: greedy (2, 3) or connected component (1)
+static int validateClustModeDriver(Call &c) {
+    if (c.f.clusterMode == 1) return validateMaxIterations(c);
+    return c.f.clusterMode != 2 && c.f.clusterMode != 3
+        ? unsupported("plass-hip %s: --cluster-mode %d is not part of the GPU path (1, connected component, and 2 and 3, the greedy modes, only)\n", c.m->name, c.f.clusterMode) : 0;
 }
 // linclust-pre: linclust.sh:21-57 from the sequence DB to pre_clust and pref_filter2, one DB as query and target
 static int validateLinclustPre(Call &c) {
@@ -591,7 +616,7 @@ static int validateMergeclusters(Call &c) {
 // and stays set), so the threshold has to come with --score-per-col-thr unless --filter-hits 0 is given.  A protein DB has the workflow's extra
 // filter step 3 (linclust.sh:59-68), which is not built
 static int validateLinclustUngapped(Call &c) {
-    if (const int rc = validateClustMode(c)) return rc;
+    if (const int rc = validateClustModeDriver(c)) return rc;
     if (const int rc = validateKmermatcher(c)) return rc;
     if (c.f.seen.count("--rescore-mode") && c.f.rescoreMode != 2) return unsupported("plass-hip linclust-ungapped: --rescore-mode %d is not this driver's (its alignment step is mode 2)\n", c.f.rescoreMode);
     // (the reference's mode 2 ends with "wrapped scoring is only allowed with RESCORE_MODE_HAMMING", and the workflow passes one flag set to both steps)
@@ -606,7 +631,7 @@ static int validateLinclustUngapped(Call &c) {
 // subset of the prefilter list and the alignment.  Both rescore steps run with --filter-hits 1 and look their threshold up with the same
 // --min-seq-id, -c and --cov-mode (Linclust.cpp:116-127), so one --score-per-col-thr serves both
 static int validateLinclustUngappedProt(Call &c) {
-    if (const int rc = validateClustMode(c)) return rc;
+    if (const int rc = validateClustModeDriver(c)) return rc;
     if (const int rc = validateKmermatcher(c)) return rc;
     if (c.f.seen.count("--rescore-mode") && c.f.rescoreMode != 2) return unsupported("plass-hip linclust-ungapped-prot: --rescore-mode %d is not this driver's (its alignment step is mode 2)\n", c.f.rescoreMode);
     if (c.f.wrapped || c.f.sortResults > 0) return unsupported("plass-hip linclust-ungapped-prot: --wrapped-scoring 1 / --sort-results are not part of the GPU path\n");
@@ -825,6 +850,27 @@ static int runClustGreedy(Call &c) {
     printClustStats(st);
     return KW(plasship_clusters_write(ctx, cl, db, pos[2].c_str())) ? fail("clust-greedy") : EXIT_SUCCESS;
 }
+static void printCcStats(const plasship_cc_stats &st) {
+    fprintf(stdout, "sequences: %llu edges: %llu clusters: %llu missing links: %llu | hook rounds: %u bfs levels: %u | kernel ms: %.3f\n", (unsigned long long) st.n_sequences,
+            (unsigned long long) st.n_edges, (unsigned long long) st.n_clusters, (unsigned long long) st.n_missing_links, st.n_hook_rounds, st.n_bfs_levels, st.ms_kernel);
+}
+static int runClustConnected(Call &c) {
+    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
+    SeqDb db(ctx); Cands cands(ctx); Alns al(ctx); Clusters cl(ctx); plasship_cc_stats st = {};
+    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out()))) return fail("clust-connected");
+    size_t n = 0; plasship_seqdb_info(db, &n, nullptr, nullptr, nullptr, nullptr);
+    if (indexLines(pos[1]) != (long) n) { fprintf(stdout, "Sequence db size != result db size\n"); return EXIT_FAILURE; }      // ClusteringAlgorithms.cpp:20-23
+    if (probeDbtype(pos[1]) == PLASSHIP_DBTYPE_ALIGNMENT_RES) {
+        // (lines plasship_alns_read cannot take — fewer than ten columns — are left to the reference: nothing has been written)
+        if (K(plasship_alns_read(ctx, db, pos[1].c_str(), al.out())))
+            return g_lastRc == PLASSHIP_ERR_ARG ? unsupported("plass-hip clust-connected: %s\n", plasship_last_error()) : fail("clust-connected");
+        if (K(plasship_clust_connected_alns(ctx, db, al, c.f.maxIterations, cl.out(), &st))) return fail("clust-connected");
+    } else {
+        if (K(plasship_cands_read(ctx, db, db, pos[1].c_str(), cands.out())) || K(plasship_clust_connected_cands(ctx, db, cands, c.f.maxIterations, cl.out(), &st))) return fail("clust-connected");
+    }
+    printCcStats(st);
+    return KW(plasship_clusters_write(ctx, cl, db, pos[2].c_str())) ? fail("clust-connected") : EXIT_SUCCESS;
+}
 static int runLinclustPre(Call &c) {              // kmermatcher -> rescorediagonal (Hamming) -> clust -> createsubdb + filterdb of pref, on handles
     plasship_ctx *ctx = c.ctx; const Flags &f = c.f;
     SeqDb db(ctx); Cands pref(ctx), rescored(ctx), filtered(ctx); Clusters cl(ctx);
@@ -861,20 +907,23 @@ static int runLinclustUngapped(Call &c) {
     plasship_hamming_params hp = hammingParams(f);      // Linclust.cpp:106-111: the Hamming step never goes below 0.5 in seq. id. and coverage
     hp.seq_id_thr = std::max(0.5f, f.seqIdThr); hp.cov_thr = std::max(0.5f, f.covThr);
     const plasship_local_params lp = localParams(f); const plasship_subst_params sp = substParams(f);
-    plasship_rescore_stats rs = {}, fs = {}, ls = {}; plasship_clust_stats st = {}, st2 = {};
+    plasship_rescore_stats rs = {}, fs = {}, ls = {}; plasship_clust_stats st = {}, st2 = {}; plasship_cc_stats cs = {}, cs2 = {};
+    const bool connected = f.clusterMode == 1;    // both `clust` calls of linclust.sh:35,82 run in the workflow's one mode
     if (K(plasship_kmermatch(ctx, db, &kp, pref.out(), &ks)) || K(plasship_rescore_hamming(ctx, db, db, pref, &hp, rescored.out(), &rs)) ||
-        K(plasship_clust_greedy_cands(ctx, db, rescored, pre.out(), &st)) || K(plasship_cands_filter(ctx, pref, pre, filtered.out()))) return fail(name);
+        K(connected ? plasship_clust_connected_cands(ctx, db, rescored, f.maxIterations, pre.out(), &cs) : plasship_clust_greedy_cands(ctx, db, rescored, pre.out(), &st)) ||
+        K(plasship_cands_filter(ctx, pref, pre, filtered.out()))) return fail(name);
     if (prot) {                                   // linclust.sh:59-68: pref_filter2 -> pref_rescore2
         Cands passed(ctx);
         if (K(plasship_rescore_subst_subset(ctx, db, filtered, pre, &sp, passed.out(), &fs))) return fail(name);
         filtered = std::move(passed);
     }
-    if (K(plasship_rescore_local_subset(ctx, db, filtered, pre, &lp, al.out(), &ls)) || K(plasship_clust_greedy_alns(ctx, db, al, cl.out(), &st2)) ||
+    if (K(plasship_rescore_local_subset(ctx, db, filtered, pre, &lp, al.out(), &ls)) ||
+        K(connected ? plasship_clust_connected_alns(ctx, db, al, f.maxIterations, cl.out(), &cs2) : plasship_clust_greedy_alns(ctx, db, al, cl.out(), &st2)) ||
         K(plasship_clusters_merge(ctx, db, pre, cl, mg.out()))) return fail(name);
     fprintf(stdout, "candidates: %llu scored: %llu kept: %llu | aligned: %llu kept: %llu | kernel ms: hamming %.3f local %.3f\n", (unsigned long long) ks.n_candidates,
             (unsigned long long) rs.n_scored, (unsigned long long) rs.n_accepted, (unsigned long long) ls.n_scored, (unsigned long long) ls.n_accepted, rs.ms_kernel, ls.ms_kernel);
     if (prot) fprintf(stdout, "filtered: %llu kept: %llu | kernel ms: subst %.3f\n", (unsigned long long) fs.n_scored, (unsigned long long) fs.n_accepted, fs.ms_kernel);
-    printClustStats(st);
+    if (connected) { printCcStats(cs); printCcStats(cs2); } else printClustStats(st);
     uint64_t n = 0, nC = 0; plasship_merged_count(mg, &n, &nC);
     fprintf(stdout, "sequences: %llu clusters: %llu\n", (unsigned long long) n, (unsigned long long) nC);
     if (KW(plasship_merged_write(ctx, mg, db, c.pos[1].c_str()))) return fail(name);
@@ -1151,6 +1200,8 @@ static const Module kModules[] = {
     {"rescorediagonal-local", RESCOREDIAGONAL_LOCAL, 4, "rescorediagonal-local <i:queryDB> <i:targetDB> <i:prefDB> <o:alnDB>", nullptr, validateRescoreLocal, runRescoreLocal},
     // linclust's greedy `clust` and its whole pre-cluster stage, lib/mmseqs/data/workflow/linclust.sh:21-57 (our own names: `clust` and `linclust` stay with the reference)
     {"clust-greedy", CLUST_GREEDY, 3, "clust-greedy <i:sequenceDB> <i:resultDB> <o:clusterDB>", nullptr, validateClustGreedy, runClustGreedy},
+    // connected component under its own name, lib/mmseqs/data/workflow/linclust.sh:35,82 with --cluster-mode 1
+    {"clust-connected", CLUST_CONNECTED, 3, "clust-connected <i:sequenceDB> <i:resultDB> <o:clusterDB>", nullptr, validateClustConnected, runClustConnected},
     {"linclust-pre", LINCLUST_PRE, 3, "linclust-pre <i:sequenceDB> <o:preClusterDB> <o:prefilterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; }, validateLinclustPre, runLinclustPre},
     {"mergeclusters-greedy", MERGECLUSTERS_GREEDY, 4, "mergeclusters-greedy <i:sequenceDB> <o:clusterDB> <i:clusterDB1> <i:clusterDB2>", nullptr, validateMergeclusters, runMergeclusters},
     {"linclust-ungapped", LINCLUST_UNGAPPED, 2, "linclust-ungapped <i:sequenceDB> <o:clusterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; f.filterHits = 1; }, validateLinclustUngapped, runLinclustUngapped},
