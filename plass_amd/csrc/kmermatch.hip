@@ -199,6 +199,14 @@ static int launchLinePart(plasship_ctx *ctx, const LinePartArgs &a, uint64_t nPi
     return PLASSHIP_OK;
 }
 
+// PLASSHIP_DEBUG_ROWTIER=1 (debug only, off by default): one stderr line per kmermatcher call that runs the row kernels (kmermatch_extract.hpp
+// section 2e) — the sequences in the four lists of the 16-lane launches and how many of them fell through to the 4-scores tier; the same for the
+// three 32-lane lists and the 64-lane list, which share one fall-through queue in front of the 16-scores tier; the length of the list they were
+// sorted from, and its histogram by window count in 24 classes of 32 from 257 on.  It waits for the stream and copies the lengths to the host.
+static bool rowTierDebugOn() { return getenv("PLASSHIP_DEBUG_ROWTIER") != nullptr; }
+// the last window counts of the three 32-lane lists: <10, 32>, <12, 32> and <16, 32> of extractRowKernel; the rest, up to 1024, is <16, 64>
+static constexpr uint32_t ROW_WIDE_BINS[3] = {320u, 384u, 512u};
+
 // PLASSHIP_DEBUG_LINELIST=1 (debug only, off by default): one stderr line per line-list build — the caller (hash partition or rep sort), the
 // level, its buckets, the output lines the kernel walks, the lines listed, the chunk size and the number of chunks, the regions (level 2: also
 // the pieces they were written in), and the largest bucket in lines.  It waits for the stream.
@@ -1177,10 +1185,11 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         //  wave tiers 0.35 ms per iteration, 1.64 -> 1.99 ms; at 12.5 M reads the rows win 1.9 ms, at 50 M 5.8: profiles/r06_ab_knobs.txt)
         if (rowTier) {
             const uint32_t rs = N + 1;
-            if (dRowLists.alloc((size_t) 4 * rs * 4) != hipSuccess || dRowCounts.alloc(16) != hipSuccess || dRowFall.alloc((size_t) rs * 4) != hipSuccess || dRowFallCnt.alloc(4) != hipSuccess) {
+            // (counts: [0..3] the four lists of the 16-lane launches, [4..7] those of the 32- and 64-lane launches, [8] what these leave to the 16-scores tier)
+            if (dRowLists.alloc((size_t) 4 * rs * 4) != hipSuccess || dRowCounts.alloc(48) != hipSuccess || dRowFall.alloc((size_t) rs * 4) != hipSuccess || dRowFallCnt.alloc(4) != hipSuccess) {
                 setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE;
             }
-            PH_CHECK(hipMemsetAsync(dRowCounts.p, 0, 16, st));
+            PH_CHECK(hipMemsetAsync(dRowCounts.p, 0, 48, st));
             PH_CHECK(hipMemsetAsync(dRowFallCnt.p, 0, 4, st));
             hipLaunchKernelGGL(binWaveListKernel, dim3(std::min<uint32_t>((nMine + 2047) / 2048, (uint32_t) ctx->numCU * 8)), dim3(256), 0, st, (const uint32_t *) dWaveList.as<uint32_t>(), (const uint32_t *) dWaveCount.as<uint32_t>(),
                                (const uint32_t *) db->d_len.as<uint32_t>(), (uint32_t) k, 96u, 128u, 192u, dRowLists.as<uint32_t>(), rs, dRowCounts.as<uint32_t>());
@@ -1203,7 +1212,45 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         //  per iteration, nothing gained; profiles/r05_ab_knobs.txt)
         hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 4, 256>), dim3(wide), dim3(64), 0, st, e0);
         ExtractArgs e1 = ea; e1.waveList = dLongList.as<uint32_t>(); e1.waveCount = dLongCount.as<uint32_t>();
+        // two sequences or one per wavefront for the sequences of the 16-scores tier (257-1024 windows; section 2e with groups of 32 and 64 lanes):
+        // the list sorted by window count into four lists of its own, the pairs of a 32-lane launch alike to ROW_WIDE_BINS; what a launch
+        // cannot finish is queued for the 16-scores tier, which reads that queue instead of the list
+        DevBuf dWideLists, dWideFall;
+        if (rowTier) {
+            const uint32_t rs = N + 1;
+            if (dWideLists.alloc((size_t) 4 * rs * 4) != hipSuccess || dWideFall.alloc((size_t) rs * 4) != hipSuccess) { setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+            uint32_t *wideCounts = dRowCounts.as<uint32_t>() + 4, *wideFallCnt = dRowCounts.as<uint32_t>() + 8;
+            hipLaunchKernelGGL(binWaveListKernel, dim3(std::min<uint32_t>((nMine + 2047) / 2048, (uint32_t) ctx->numCU * 8)), dim3(256), 0, st, (const uint32_t *) dLongList.as<uint32_t>(), (const uint32_t *) dLongCount.as<uint32_t>(),
+                               (const uint32_t *) db->d_len.as<uint32_t>(), (uint32_t) k, ROW_WIDE_BINS[0], ROW_WIDE_BINS[1], ROW_WIDE_BINS[2], dWideLists.as<uint32_t>(), rs, wideCounts);
+            RowArgs ra; memset(&ra, 0, sizeof(ra));
+            ra.s = ea.s; ra.slotOff = ea.slotOff; ra.arr = ea.arr; ra.map = ea.map; ra.fallList = dWideFall.as<uint32_t>(); ra.fallCount = wideFallCnt;
+            ra.k = k; ra.xCode = ea.xCode; ra.kps = ea.kps; ra.ignoreMulti = ea.ignoreMulti; ra.seed = ea.seed; ra.base = (uint32_t) ea.powers[1]; ra.base7 = (uint32_t) ea.powers[7];
+            ra.slotBias = slotBias; ra.kstats = dKStats.as<unsigned long long>();
+            const dim3 pairGrid(std::min<uint32_t>((nMine + 1) / 2, (uint32_t) ctx->numCU * 32u)), oneGrid(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * 32u));
+            for (int b = 0; b < 4; b++) {
+                ra.list = dWideLists.as<uint32_t>() + (size_t) b * rs; ra.count = wideCounts + b;
+                if (b == 0) hipLaunchKernelGGL((extractRowKernel<10, 32>), pairGrid, dim3(64), 0, st, ra);
+                else if (b == 1) hipLaunchKernelGGL((extractRowKernel<12, 32>), pairGrid, dim3(64), 0, st, ra);
+                else if (b == 2) hipLaunchKernelGGL((extractRowKernel<16, 32>), pairGrid, dim3(64), 0, st, ra);
+                else hipLaunchKernelGGL((extractRowKernel<16, 64>), oneGrid, dim3(64), 0, st, ra);
+            }
+            e1.waveList = dWideFall.as<uint32_t>(); e1.waveCount = wideFallCnt;
+        }
         hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 16, 992>), dim3(wide), dim3(64), 0, st, e1);
+        if (rowTier && rowTierDebugOn()) {
+            uint32_t c[12], fell16 = 0;
+            PH_COPY_SYNC(st, c, dRowCounts.p, sizeof(c), hipMemcpyDeviceToHost);
+            PH_COPY_SYNC(st, &fell16, dRowFallCnt.p, 4, hipMemcpyDeviceToHost);
+            uint32_t nLong = 0;
+            PH_COPY_SYNC(st, &nLong, dLongCount.p, 4, hipMemcpyDeviceToHost);
+            std::vector<uint32_t> ids(nLong), lens(N);
+            if (nLong) PH_COPY_SYNC(st, ids.data(), dLongList.p, (size_t) nLong * 4, hipMemcpyDeviceToHost);
+            if (N) PH_COPY_SYNC(st, lens.data(), db->d_len.p, (size_t) N * 4, hipMemcpyDeviceToHost);
+            uint32_t hist[24] = {0};
+            for (uint32_t id : ids) { const uint32_t nw = lens[id] - (uint32_t) k + 1; if (nw > 256u && nw <= 1024u) hist[(nw - 257u) / 32u]++; }
+            std::string h; for (int i = 0; i < 24; i++) h += (i ? "," : "") + std::to_string(hist[i]);
+            fprintf(stderr, "rowTier rows16 %u %u %u %u fell %u rows32 %u %u %u rows64 %u fell %u of %u hist %s\n", c[0], c[1], c[2], c[3], fell16, c[4], c[5], c[6], c[7], c[8], nLong, h.c_str());
+        }
         ExtractArgs e2 = ea; e2.waveList = dOvIds.as<uint32_t>(); e2.waveCount = dOvCnt.as<uint32_t>();
         e2.overflowIds = dOv2Ids.as<uint32_t>(); e2.overflowCount = dOv2Cnt.as<uint32_t>();
         // (round 4: a nucleotide sequence of this tier has at most 3 072 windows, i.e. 60 + 0.1 L <= 370 selected k-mers at the workflow's

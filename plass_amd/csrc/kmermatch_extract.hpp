@@ -1137,6 +1137,15 @@ __global__ __launch_bounds__(64) void extractCachedKernel(CachedArgs a) {
 //     then owns the slot range.  Lists by window count (binWaveListKernel) keep the four sequences of a wavefront alike.
 //     Protein runs with k <= 14, alphabet base <= 16, no length scaling, --kmer-per-seq <= 60 (the Plass workflow);
 //     PLASSHIP_TUNE_ROWTIER=2 switches it off.
+//     The same kernel with a GROUP of LANES = 32 or 64 lanes per sequence (two rows, or the whole wavefront) stands in front of the
+//     16-scores tier: window p is lane p % LANES' register p / LANES, so <10 / 12 / 16, 32> hold 257-320 / -384 / -512 windows, two
+//     sequences per wavefront, and <16, 64> holds 513-1024, one per wavefront (lists by window count as above: kmermatch.hip,
+//     ROW_WIDE_BINS).  Sums and scans are the row forms plus one (32) or two (64) row-joining steps on gfx950's lane swaps
+//     (RowGroup), still without ballots or a scalar loop per sequence; staging is 16 bytes per lane in at most two chunks; a lane
+//     writes 64 / LANES of the <= 59 records.  What a launch cannot finish is queued for the 16-scores tier.  No instantiation
+//     spills (<16, 32> and <16, 64>: 128 VGPRs, four wavefronts per SIMD; 7.0 and 2.6 KB of LDS per one-wavefront workgroup, so
+//     LDS leaves the 16 workgroups of a CU resident — the 64-lane group splits its table of powers for that: with the one table,
+//     10.4 KB, it took 10.6 instead of 9.1 ms per launch; profiles/rows_wide_bench_ab.txt).
 // =====================================================================================================
 struct RowArgs {
     SeqView s; const uint64_t *slotOff; void *arr; const unsigned char *map;
@@ -1160,6 +1169,42 @@ __device__ __forceinline__ unsigned long long rowSum16U64(unsigned long long v) 
     v += dppMov64<0xB1>(v); v += dppMov64<0x4E>(v); v += dppMov64<0x141>(v); v += dppMov64<0x140>(v);
     return v;
 }
+// A group of LANES = 16, 32 or 64 lanes (one, two or four rows) owns a sequence.  Sums and scans keep their DPP row steps; the rows of a
+// group are joined by the swaps of gfx950, which stay on the VALU: v_permlane16_swap exchanges the odd rows of its first operand with
+// the even rows of its second, so from a row-uniform value v it leaves (v of the pair's even row, v of its odd row) in every lane of
+// both rows; v_permlane32_swap does the same with the two halves of the wavefront.
+template <int LANES> struct RowGroup {
+    static_assert(LANES == 16 || LANES == 32 || LANES == 64, "a group is one, two or four rows of 16 lanes");
+    // t: the sum of the lane's row, in every lane of the row -> lo: the sum of the group's rows in front of the lane's, all: of all its rows
+    static __device__ __forceinline__ void joinRows(uint32_t t, uint32_t &lo, uint32_t &all) {
+        lo = 0; all = t;
+        if constexpr (LANES >= 32) {
+            const auto r = __builtin_amdgcn_permlane16_swap(t, t, false, false);
+            lo = (threadIdx.x & 16u) ? r[0] : 0u; all = r[0] + r[1];
+        }
+        if constexpr (LANES == 64) {
+            const auto q = __builtin_amdgcn_permlane32_swap(all, all, false, false);
+            lo += (threadIdx.x & 32u) ? q[0] : 0u; all = q[0] + q[1];
+        }
+    }
+    static __device__ __forceinline__ uint32_t sum(uint32_t v) { uint32_t lo, all; joinRows((uint32_t) rowSum16((int) v), lo, all); return all; }
+    static __device__ __forceinline__ uint32_t exclusiveScan(uint32_t v) {      // exclusive prefix sum inside each group
+        uint32_t lo, all; joinRows((uint32_t) rowSum16((int) v), lo, all);
+        return rowExclusiveScan16(v) + lo;
+    }
+    static __device__ __forceinline__ unsigned long long sumU64(unsigned long long v) {      // modulo 2^64
+        v = rowSum16U64(v);
+        if constexpr (LANES >= 32) {
+            const auto l = __builtin_amdgcn_permlane16_swap((uint32_t) v, (uint32_t) v, false, false), h = __builtin_amdgcn_permlane16_swap((uint32_t) (v >> 32), (uint32_t) (v >> 32), false, false);
+            v = (((unsigned long long) h[0] << 32) | l[0]) + (((unsigned long long) h[1] << 32) | l[1]);
+        }
+        if constexpr (LANES == 64) {
+            const auto l = __builtin_amdgcn_permlane32_swap((uint32_t) v, (uint32_t) v, false, false), h = __builtin_amdgcn_permlane32_swap((uint32_t) (v >> 32), (uint32_t) (v >> 32), false, false);
+            v = (((unsigned long long) h[0] << 32) | l[0]) + (((unsigned long long) h[1] << 32) | l[1]);
+        }
+        return v;
+    }
+};
 // the ids of a list sorted into four lists by window count (<= w0, <= w1, <= w2, the rest): the rows of a wavefront share their loop bounds
 __global__ __launch_bounds__(256) void binWaveListKernel(const uint32_t *__restrict__ list, const uint32_t *__restrict__ count, const uint32_t *__restrict__ len, uint32_t k,
                                                          uint32_t w0, uint32_t w1, uint32_t w2, uint32_t *__restrict__ out, uint32_t outStride, uint32_t *__restrict__ outCount) {
@@ -1190,22 +1235,30 @@ __global__ __launch_bounds__(256) void binWaveListKernel(const uint32_t *__restr
     }
 }
 
-template <int REGS>
+template <int REGS, int LANES = 16>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void extractRowKernel(RowArgs a) {
-    constexpr uint32_t MAXWIN = 16u * REGS, MAXL = MAXWIN + 13u;           // k <= 14
+    static_assert(LANES == 16 || LANES == 32 || LANES == 64, "a group is one, two or four rows of 16 lanes");
+    constexpr int GROUPS = 64 / LANES;                                      // sequences per wavefront
+    constexpr uint32_t MAXWIN = (uint32_t) LANES * REGS, MAXL = MAXWIN + 13u;      // k <= 14
     constexpr uint32_t ROWB = (MAXL + 31u + 15u) & ~15u;                    // staged codes of a row, X padding included
-    constexpr bool TWO = MAXL > 256u;                                       // a second 16-byte chunk per lane
+    constexpr bool TWO = MAXL > 16u * LANES;                                // a second 16-byte chunk per lane
+    static_assert(MAXL <= 32u * LANES, "two chunks of 16 bytes per lane hold the longest sequence");
     constexpr uint32_t NPOW = MAXL + 17u;
     __shared__ unsigned char sMap[256];
-    __shared__ __attribute__((aligned(16))) unsigned char sCode[4][ROWB];
-    __shared__ unsigned long long sPow[NPOW];                               // 31^(x - 15) modulo 2^64 (31 is odd: the inverse exists)
-    __shared__ unsigned short sSel[4][64];                                  // window positions of the selection, row by row
-    __shared__ __attribute__((aligned(16))) uint32_t sSet[4][128];          // repeat check: 32-bit tags of the selected k-mers
+    __shared__ __attribute__((aligned(16))) unsigned char sCode[GROUPS][ROWB];
+    // 31^(x - 15) modulo 2^64 (31 is odd: the inverse exists).  The 64-lane group's table of 1054 powers would alone cost 8.4 KB per one-wavefront
+    // workgroup (16 of them pass the CU's 160 KB of LDS); it keeps 31^(16 h - 15) and 31^l, l < 16, instead and pays one more product per chunk
+    constexpr bool SPLIT = LANES == 64;
+    constexpr uint32_t NHI = (NPOW + 15u) / 16u;
+    __shared__ unsigned long long sPow[SPLIT ? NHI + 16u : NPOW];
+    __shared__ unsigned short sSel[GROUPS][64];                                  // window positions of the selection, row by row
+    __shared__ __attribute__((aligned(16))) uint32_t sSet[GROUPS][128];          // repeat check: 32-bit tags of the selected k-mers
     typedef Rec<false> R;
+    typedef RowGroup<LANES> G;
     R *arr = reinterpret_cast<R *>(a.arr);
-    const int lane = threadIdx.x, row = lane >> 4, sub = lane & 15;
+    const int lane = threadIdx.x, row = lane / LANES, sub = lane % LANES;
     const int k = a.k;
-    if (blockIdx.x * 4u >= *a.count) return;                               // (a list shorter than the grid: nothing to set up)
+    if (blockIdx.x * (uint32_t) GROUPS >= *a.count) return;                               // (a list shorter than the grid: nothing to set up)
     for (int i = lane; i < 256; i += 64) sMap[i] = a.map[i];
     {
         // 31^(lane - 15) by the bits of the lane (compile-time squares), then steps of 31^64: a block's set-up is a dozen multiplications
@@ -1213,12 +1266,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
         constexpr uint64_t inv31 = rowInv31(), c0 = rowPowU64(inv31, 15), p64 = rowPowU64(31ull, 64);
         uint64_t m = c0;
 #pragma unroll
-        for (int b = 0; b < 6; b++) if ((lane >> b) & 1) m *= rowPowU64(31ull, 1u << b);
-        for (uint32_t x = lane; x < NPOW; x += 64) { sPow[x] = m; m *= p64; }
+        for (int b = 0; b < 6; b++) if ((lane >> b) & 1) m *= rowPowU64(31ull, (SPLIT ? 16u : 1u) << b);
+        if constexpr (SPLIT) {
+            for (uint32_t x = lane; x < NHI; x += 64) { sPow[x] = m; m *= rowPowU64(31ull, 1024); }      // 31^(16 x - 15)
+            uint64_t l = 1;
+#pragma unroll
+            for (int b = 0; b < 4; b++) if ((lane >> b) & 1) l *= rowPowU64(31ull, 1u << b);
+            if (lane < 16) sPow[NHI + (uint32_t) lane] = l;
+        } else {
+            for (uint32_t x = lane; x < NPOW; x += 64) { sPow[x] = m; m *= p64; }
+        }
     }
     __syncthreads();
     const uint32_t nWork = *a.count;
-    const uint32_t stride = gridDim.x * 4u;
+    const uint32_t stride = gridDim.x * (uint32_t) GROUPS;
     const uint32_t xC = (uint32_t) a.xCode;
     const uint32_t considerRaw = (uint32_t) (a.kps - 1);                    // kmermatcher.cpp:223 with --kmer-per-seq-scale 0
     unsigned long long stRes = 0, stRec = 0;
@@ -1229,7 +1290,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
         return m;
     };
     auto loadRaw = [&](const Meta &m, uint32_t at) { uint4 v = make_uint4(0, 0, 0, 0); if (at < m.L) __builtin_memcpy(&v, a.s.data + m.off + at, 16); return v; };      // (buffers are padded past their ends)
-    uint32_t w = blockIdx.x * 4u + (uint32_t) row;
+    uint32_t w = blockIdx.x * (uint32_t) GROUPS + (uint32_t) row;
     auto loadId = [&](uint32_t ww) { return ww < nWork ? a.list[ww] : 0xFFFFFFFFu; };
     auto metaOf = [&](uint32_t id) {
         Meta m; m.id = id; m.L = 0; m.off = 0; m.slot = 0; m.slot1 = 0;
@@ -1238,10 +1299,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
     };
     Meta mNext = loadMeta(w); uint32_t id2 = loadId(w + stride);
     uint4 rawN0 = loadRaw(mNext, (uint32_t) sub * 16u);
-    for (uint32_t w0 = blockIdx.x * 4u; w0 < nWork; w0 += stride, w += stride) {
+    for (uint32_t w0 = blockIdx.x * (uint32_t) GROUPS; w0 < nWork; w0 += stride, w += stride) {
         const Meta cur = mNext; const uint4 raw0 = rawN0;
         uint4 raw1 = make_uint4(0, 0, 0, 0);
-        if (TWO) raw1 = loadRaw(cur, 256u + (uint32_t) sub * 16u);         // (the last 13 residues of the longest sequences: requested here, used behind the first chunk)
+        if (TWO) raw1 = loadRaw(cur, 16u * LANES + (uint32_t) sub * 16u);         // (the last 13 residues of the longest sequences: requested here, used behind the first chunk)
         mNext = metaOf(id2);
         rawN0 = loadRaw(mNext, (uint32_t) sub * 16u);
         id2 = loadId(w + 2u * stride);
@@ -1273,25 +1334,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
                 }
                 constexpr unsigned long long K4 = 923521ull;                 // 31^4
                 const unsigned long long H = (((unsigned long long) q[0] * K4 + q[1]) * K4 + q[2]) * K4 + q[3];
-                hAcc += H * sPow[(uint32_t) ((int) L - 16 * (int) (c + 1) + 15)];
+                const uint32_t e = (uint32_t) ((int) L - 16 * (int) (c + 1) + 15);
+                hAcc += H * (SPLIT ? sPow[e >> 4] * sPow[NHI + (e & 15u)] : sPow[e]);
             }
         };
         stageChunk(raw0, (uint32_t) sub);
-        if (TWO) stageChunk(raw1, 16u + (uint32_t) sub);
-        if (active && !tooLong) for (uint32_t i = (uint32_t) sub; i < 31u; i += 16u) sCode[row][L + i] = (unsigned char) xC;      // X behind the sequence: every window read stays defined
-        for (uint32_t i = (uint32_t) sub * 4u; i < 128u; i += 64u) *reinterpret_cast<uint4 *>(&sSet[row][i]) = make_uint4(0, 0, 0, 0);
+        if (TWO) stageChunk(raw1, (uint32_t) LANES + (uint32_t) sub);
+        if (active && !tooLong) for (uint32_t i = (uint32_t) sub; i < 31u; i += (uint32_t) LANES) sCode[row][L + i] = (unsigned char) xC;      // X behind the sequence: every window read stays defined
+        for (uint32_t i = (uint32_t) sub * 4u; i < 128u; i += 4u * LANES) *reinterpret_cast<uint4 *>(&sSet[row][i]) = make_uint4(0, 0, 0, 0);
         __syncthreads();
-        const unsigned long long seqHash = rowSum16U64(hAcc);
+        const unsigned long long seqHash = G::sumU64(hAcc);
         // ---- one score per window, in registers ----
         uint32_t sc[REGS];
         uint32_t nLane = 0;
 #pragma unroll
         for (int j = 0; j < REGS; j++) {
             sc[j] = 0xFFFFFFFFu;
-            if ((uint32_t) j * 16u < nWinU) {
+            if ((uint32_t) j * LANES < nWinU) {
                 // (every lane hashes — a window behind the row's last one reads stale codes inside the row's buffer and is discarded: the rows of a
                 //  wavefront differ in length, and a branch per row and window costs more than the masked lanes it saves)
-                const uint32_t p = (uint32_t) j * 16u + (uint32_t) sub;
+                const uint32_t p = (uint32_t) j * LANES + (uint32_t) sub;
                 uint64_t kmer;
                 const bool v = kmerIndexFastAligned(sCode[row], p, k, xC, a.base, a.base7, kmer);
                 const uint32_t h = xxh64Score16(kmer, a.seed);
@@ -1300,7 +1362,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
             }
             __builtin_amdgcn_sched_barrier(0);      // one window's hash at a time: the temporaries of interleaved windows cost a wavefront per SIMD
         }
-        const uint32_t n = (uint32_t) rowSum16((int) nLane);
+        const uint32_t n = G::sum(nLane);
         const uint32_t considered = min(considerRaw, n);
         // ---- the reference's walk over 65 536 score bins (kmermatcher.cpp:224-239) as a bisection: every count a per-lane count + a row sum ----
         uint32_t t = 0;
@@ -1309,22 +1371,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
             const uint32_t tr = t | (1u << bit);
             uint32_t c = 0;
 #pragma unroll
-            for (int j = 0; j < REGS; j++) if ((uint32_t) j * 16u < nWinU) c += (sc[j] < tr) ? 1u : 0u;
-            if ((uint32_t) rowSum16((int) c) < considered) t = tr;
+            for (int j = 0; j < REGS; j++) if ((uint32_t) j * LANES < nWinU) c += (sc[j] < tr) ? 1u : 0u;
+            if (G::sum(c) < considered) t = tr;
         }
         if (n <= considered) t = 0xFFFFu;                                   // every valid window is selected
         uint32_t selMask = 0;
 #pragma unroll
-        for (int j = 0; j < REGS; j++) if ((uint32_t) j * 16u < nWinU) selMask |= (sc[j] <= t) ? (1u << j) : 0u;
+        for (int j = 0; j < REGS; j++) if ((uint32_t) j * LANES < nWinU) selMask |= (sc[j] <= t) ? (1u << j) : 0u;
         const uint32_t cLane = (uint32_t) __popc(selMask);
-        const uint32_t C = (uint32_t) rowSum16((int) cLane);
+        const uint32_t C = G::sum(cLane);
         bool ok = active && !tooLong && C == considered;                    // no surplus in the threshold bin
         // ---- the selected windows' positions, row by row (any order: see the fast path of extractKernel) ----
         {
-            uint32_t at = rowExclusiveScan16(cLane);
+            uint32_t at = G::exclusiveScan(cLane);
             if (ok) {
 #pragma unroll
-                for (int j = 0; j < REGS; j++) if ((selMask >> j) & 1u) { sSel[row][at] = (unsigned short) ((uint32_t) j * 16u + (uint32_t) sub); at++; }
+                for (int j = 0; j < REGS; j++) if ((selMask >> j) & 1u) { sSel[row][at] = (unsigned short) ((uint32_t) j * LANES + (uint32_t) sub); at++; }
             }
         }
         __syncthreads();
@@ -1332,8 +1394,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
         const uint32_t bound = (uint32_t) (cur.slot1 - cur.slot);
         bool rep = false;
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t r = (uint32_t) sub + 16u * (uint32_t) i;
+        for (int i = 0; i < GROUPS; i++) {      // (at most 59 selected windows: 64 / LANES records per lane)
+            const uint32_t r = (uint32_t) sub + (uint32_t) LANES * (uint32_t) i;
             if (ok && r < C) {
                 const uint32_t p = sSel[row][r];
                 uint64_t kmer; (void) kmerIndexFastAligned(sCode[row], p, k, xC, a.base, a.base7, kmer);
@@ -1353,21 +1415,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (rowSum16(rep ? 1 : 0) != 0) ok = false;
+        if (G::sum(rep ? 1u : 0u) != 0u) ok = false;
         if (ok) {
-            if (sub == 15) { R rec; rec.kmer = xxh64U64(seqHash, a.seed); rec.id = id; rec.len = (uint16_t) L; rec.pos = 0; arr[slot] = rec; }      // identity record (kmermatcher.cpp:241-249)
-            for (uint32_t i = 1u + C + (uint32_t) sub; i < bound; i += 16u) { R rec; memset(&rec, 0xFF, sizeof(R)); arr[slot + i] = rec; }
+            if (sub == LANES - 1) { R rec; rec.kmer = xxh64U64(seqHash, a.seed); rec.id = id; rec.len = (uint16_t) L; rec.pos = 0; arr[slot] = rec; }      // identity record (kmermatcher.cpp:241-249)
+            for (uint32_t i = 1u + C + (uint32_t) sub; i < bound; i += (uint32_t) LANES) { R rec; memset(&rec, 0xFF, sizeof(R)); arr[slot + i] = rec; }
             unsigned char *cl = reinterpret_cast<unsigned char *>(a.kstats[4]);
             if (cl) {       // selected-window cache (section 2c): the same line the wave tiers' fast path leaves
                 unsigned short *ln = reinterpret_cast<unsigned short *>(cl + (size_t) id * KMC_LINE);
 #pragma unroll
-                for (int i = 0; i < 4; i++) { const uint32_t r = (uint32_t) sub + 16u * (uint32_t) i; if (r < KMC_POS) ln[4 + r] = (r < C) ? sSel[row][r] : (unsigned short) 0xFFFFu; }
+                for (int i = 0; i < GROUPS; i++) { const uint32_t r = (uint32_t) sub + (uint32_t) LANES * (uint32_t) i; if (r < KMC_POS) ln[4 + r] = (r < C) ? sSel[row][r] : (unsigned short) 0xFFFFu; }
                 if (sub == 0) *reinterpret_cast<unsigned long long *>(ln) = seqHash;
-                if (sub == 15) ln[KMC_FLAGS] = (unsigned short) KMC_CLEAN;
+                if (sub == LANES - 1) ln[KMC_FLAGS] = (unsigned short) KMC_CLEAN;
             }
             if (sub == 0) { stRes += L; stRec += 1 + C; }
         }
-        // ---- what is left to the 4-scores tier: one atomic per wavefront ----
+        // ---- what is left to the wave tier behind this launch (4 scores behind 16 lanes, 16 scores behind 32 and 64): one atomic per wavefront ----
         {
             const bool fall = active && !ok && sub == 0;
             const unsigned long long fm = __ballot(fall);
