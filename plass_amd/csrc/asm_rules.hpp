@@ -40,6 +40,22 @@ PLASSHIP_AR_HD DiagSpan diagonalSpan(int diag, unsigned qLen, unsigned tLen) {
     else if (diag < 0 && dist < tLen) { s.hit = true; s.to = dist; s.len = tLen - dist < qLen ? tLen - dist : qLen; }
     return s;
 }
+// computeUngappedAlignment's walk over the wraps of a diagonal kept in 16 bits (DistanceCalculator.h:98-111): d16 - 65536 j for
+// j = 1 .. 1 + tLen / 32768, then d16 + 65536 j for j = 0 .. qLen / 65536.  f(realDiagonal, span) for every wrap that meets the sequences,
+// in that order; a wrap that misses them scores 0 there and never wins: f is not called for it.  The caller keeps the best, a strictly
+// greater score replacing it.
+template <typename F> PLASSHIP_AR_HD void forEachWrap(unsigned d16, unsigned qLen, unsigned tLen, F &&f) {
+    for (unsigned j = 1; j <= 1u + tLen / 32768u; j++) {
+        const int real = (int) (d16 - j * 65536u);
+        const DiagSpan s = diagonalSpan(real, qLen, tLen);
+        if (s.hit) f(real, s);
+    }
+    for (unsigned j = 0; j <= qLen / 65536u; j++) {
+        const int real = (int) (j * 65536u + d16);
+        const DiagSpan s = diagonalSpan(real, qLen, tLen);
+        if (s.hit) f(real, s);
+    }
+}
 // updateAlignment: the columns [startPos, endPos] of a diagonal as query and target coordinates (assembleresult.cpp:73-87)
 PLASSHIP_AR_HD AlnCoords alnOnDiagonal(int diag, int startPos, int endPos) {
     const int dist = abs(diag);

@@ -331,6 +331,46 @@ int deviceKeysDiffer(plasship_ctx *ctx, const uint32_t *a, const uint32_t *b, si
 // error too); dKeep may go after it.  what: the public call or list the error texts name.
 int compactCsr(plasship_ctx *ctx, const char *what, const uint64_t *dInQoff, uint64_t nQ, const void *dRecs, size_t recBytes, const uint32_t *dKeep,
                uint64_t nRecs, uint64_t nKept, DevBuf &outQoff, DevBuf &outRecs);
+// The E-value gate of rescorediagonal as a table (rescore.hip): hMinScore[l] = the smallest raw score that passes -e evalThr for a query of
+// length l, for every length qdb holds (0xFFFFFFFF elsewhere), uploaded to dMinScore.  Exact, because E(score) is monotone (host_util.cpp).
+// Waits for the stream once; the upload is only queued: hMinScore must live until the caller's next wait.
+struct HostEvaluer;
+int evalueGateTable(plasship_ctx *ctx, const char *what, const plasship_seqdb *qdb, const HostEvaluer &ev, double evalThr, DevBuf &dMinScore,
+                    std::vector<uint32_t> &hMinScore);
+// ---- list-in, list-out rescoring (scan.hip): what plasship_rescore_hamming, plasship_rescore_local[_subset] and
+// plasship_rescore_subst[_subset] do around their kernels ----
+enum RescoreStat { RL_KEPT, RL_RESIDUES, RL_VISIBLE, RL_BAD, RL_NSTATS };      // pairs kept, residues compared or scored, kept lines that are not an implicit self line, ids out of range
+// what every one of these kernels is handed
+struct RescoreListArgs {
+    const CandHit *hits;
+    uint64_t nHits;
+    uint32_t *keep;              // [nHits] 1: the pair's line or record is written (slot h belongs to pair h)
+    const uint32_t *minScore;    // [minScoreLen] evalueGateTable
+    uint32_t minScoreLen;
+    const signed char *mat;      // 123 x 123 in global memory, staged to LDS
+    int reverseCapable;
+    double lambda, logK, ln2;
+    unsigned long long *stats;   // [RL_NSTATS]
+};
+struct RescoreList {
+    plasship_ctx *ctx; const char *what;                     // what: the public call the error texts name
+    const plasship_seqdb *qdb, *tdb;                         // tdb == nullptr: one DB is query and target
+    const plasship_cands *c;
+    // after prepare()
+    bool nucl = false; size_t slotBytes = 0;
+    uint64_t residues = 0;                                   // the E-value's database size
+    DevBuf dKeep, dSlots, dStats, dMinScore, dMat;
+    std::vector<uint32_t> hMinScore;
+    RescoreListArgs args = {};
+    // after collect()
+    uint64_t nKept = 0, nNonSelf = 0;
+    // The shared argument checks, the buffers (slots of slotBytes per pair), the tables and the first event; the kernel is launched after it.
+    // evalThr == nullptr: no E-value table and no matrix (mode 0).  subset: the E-value's database size is the residue count of its
+    // representatives.
+    int prepare(size_t slotBytes, bool wrapped, const double *evalThr, const plasship_clusters *subset);
+    // The second event, the counters, the kept slots in input order with the CSR over them (compactCsr), and `stats` (nullable)
+    int collect(DevBuf &outQoff, DevBuf &outRecs, plasship_rescore_stats *stats);
+};
 // dense (hole-free) copy of an alignment list's CSR and records on the device (rescore.hip); for a list that is not sparse the buffers
 // stay empty and *qoff / *recs point at the list's own arrays
 int denseAlnsCopy(plasship_ctx *ctx, const plasship_alns *a, DevBuf &qoffBuf, DevBuf &recsBuf, const uint64_t **qoff, const AlnRec **recs);

@@ -284,6 +284,7 @@ __global__ __launch_bounds__(RS_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, W
             // showed 16 of 64 lanes active per vector instruction of this kernel — with one loop over the wrap index for all lanes, the
             // lanes whose diagonal is the negative wrap scored in the first round and those with the positive wrap in the second, each
             // round with about half the wavefront masked; a pair of sequences below 32 768 residues has exactly one such wrap)
+            // (forEachWrap, asm_rules.hpp, is this walk for one pair per wavefront; here every LANE has a pair of its own, hence the index form)
             const unsigned nWrap = nNeg + nPos;
             auto wrapDiag = [&](unsigned c) -> int { return c < nNeg ? (int) (d16 - (c + 1) * 65536u) : (int) ((c - nNeg) * 65536u + d16); };
             auto nextWrap = [&](unsigned c) -> unsigned {
@@ -354,6 +355,30 @@ __global__ void markLengthsKernel(const uint32_t *__restrict__ len, uint32_t n, 
     }
 }
 
+int evalueGateTable(plasship_ctx *ctx, const char *what, const plasship_seqdb *qdb, const HostEvaluer &ev, double evalThr, DevBuf &dMinScore,
+                    std::vector<uint32_t> &hMinScore) {
+    // which query lengths exist (device) -> min passing score per length (host, exact doubles)
+    const uint32_t maxQLen = qdb->maxEntryLen >= 2 ? qdb->maxEntryLen - 2 : 0;
+    const uint32_t tabLen = maxQLen + 1;
+    DevBuf dPresent;
+    if (dPresent.alloc((size_t) tabLen * 4) != hipSuccess || dMinScore.alloc((size_t) tabLen * 4) != hipSuccess) {
+        setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE;
+    }
+    PH_CHECK(hipMemsetAsync(dPresent.p, 0, (size_t) tabLen * 4, ctx->stream));
+    if (qdb->n) hipLaunchKernelGGL(markLengthsKernel, dim3(std::min<size_t>(4096, (qdb->n + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   qdb->d_len.as<uint32_t>(), (uint32_t) qdb->n, dPresent.as<uint32_t>(), tabLen);
+    std::vector<uint32_t> present(tabLen);
+    hMinScore.assign(tabLen, 0xFFFFFFFFu);
+    PH_CHECK(hipMemcpyAsync(present.data(), dPresent.p, (size_t) tabLen * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PH_CHECK(plasship::streamSync(ctx->stream));
+    // max raw score of an overlap of length L: max matrix entry (11 for BLOSUM62 W-W, 2 for nucl) * L
+    const int maxEntry = qdb->dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES ? 2 : 11;
+    int guess = -1;                                   // neighbouring lengths have neighbouring thresholds
+    for (uint32_t l = 1; l < tabLen; l++)
+        if (present[l]) { guess = ev.minScoreForEvalue(evalThr, (int) l, maxEntry * (int) l + 1, guess); hMinScore[l] = (uint32_t) guess; }
+    PH_CHECK(hipMemcpyAsync(dMinScore.p, hMinScore.data(), (size_t) tabLen * 4, hipMemcpyHostToDevice, ctx->stream));
+    return PLASSHIP_OK;
+}
 
 int denseAlnsCopy(plasship_ctx *ctx, const plasship_alns *a, DevBuf &qoffBuf, DevBuf &recsBuf, const uint64_t **qoff, const AlnRec **recs) {
     *qoff = a->d_qoff.as<uint64_t>(); *recs = a->d_recs.as<AlnRec>();
@@ -420,29 +445,14 @@ extern "C" int plasship_rescore(plasship_ctx *ctx, const plasship_seqdb *qdb, co
     PH_ENTER(ctx);
     const bool nucl = qdb->dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES;
     const uint64_t nHits = c->nHits;
-    const uint32_t maxQLen = qdb->maxEntryLen >= 2 ? qdb->maxEntryLen - 2 : 0;
 
-    // E-value gate table: which query lengths exist (device) -> min passing score per length (host, exact doubles)
-    DevBuf dPresent, dMinScore, dMat, dStats;
-    const uint32_t tabLen = maxQLen + 1;
-    if (dPresent.alloc((size_t) tabLen * 4) != hipSuccess || dMinScore.alloc((size_t) tabLen * 4) != hipSuccess ||
-        dMat.alloc(123 * 123) != hipSuccess || dStats.alloc(16) != hipSuccess) { setError("plasship_rescore: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    PH_CHECK(hipMemsetAsync(dPresent.p, 0, (size_t) tabLen * 4, ctx->stream));
+    DevBuf dMinScore, dMat, dStats;
+    std::vector<uint32_t> minScore;                       // (lives until the wait at the end: the table's upload is only queued)
+    if (dMat.alloc(123 * 123) != hipSuccess || dStats.alloc(16) != hipSuccess) { setError("plasship_rescore: out of device memory"); return PLASSHIP_ERR_DEVICE; }
     PH_CHECK(hipMemsetAsync(dStats.p, 0, 16, ctx->stream));
-    if (qdb->n) hipLaunchKernelGGL(markLengthsKernel, dim3(std::min<size_t>(4096, (qdb->n + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   qdb->d_len.as<uint32_t>(), (uint32_t) qdb->n, dPresent.as<uint32_t>(), tabLen);
-    std::vector<uint32_t> present(tabLen), minScore(tabLen, 0xFFFFFFFFu);
-    PH_CHECK(hipMemcpyAsync(present.data(), dPresent.p, (size_t) tabLen * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PH_CHECK(plasship::streamSync(ctx->stream));
     HostEvaluer ev(nucl, tdb->residues);
-    {
-        // max raw score of an overlap of length L: max matrix entry (11 for BLOSUM62 W-W, 2 for nucl) * L
-        const int maxEntry = nucl ? 2 : 11;
-        int guess = -1;                                   // neighbouring lengths have neighbouring thresholds
-        for (uint32_t l = 1; l < tabLen; l++)
-            if (present[l]) { guess = ev.minScoreForEvalue(par->eval_thr, (int) l, maxEntry * (int) l + 1, guess); minScore[l] = (uint32_t) guess; }
-    }
-    PH_CHECK(hipMemcpyAsync(dMinScore.p, minScore.data(), (size_t) tabLen * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (const int rc = evalueGateTable(ctx, "plasship_rescore", qdb, ev, par->eval_thr, dMinScore, minScore)) return rc;
+    const uint32_t tabLen = (uint32_t) minScore.size();
     PH_CHECK(hipMemcpyAsync(dMat.p, asciiSubMat(nucl), 123 * 123, hipMemcpyHostToDevice, ctx->stream));
 
     std::unique_ptr<plasship_alns> holder(new plasship_alns());     // released to the caller on success only

@@ -1,6 +1,8 @@
-// Device-wide exclusive scan (see device_utils.hpp) and what every list filter does with one: compactCsr (common.hpp).  Product code.
+// Device-wide exclusive scan (see device_utils.hpp) and what every list filter does with one: compactCsr (common.hpp); the host side of the
+// list-in, list-out rescore modules around it: RescoreList (common.hpp).  Product code.
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "host_util.hpp"
 #include <algorithm>
 
 namespace plasship {
@@ -131,6 +133,63 @@ int compactCsr(plasship_ctx *ctx, const char *what, const uint64_t *dInQoff, uin
     PH_COPY_SYNC(ctx->stream, &total, dPos.as<uint64_t>() + nRecs, 8, hipMemcpyDeviceToHost);
     PH_CHECK(hipGetLastError());
     if (total != nKept) { setError(std::string(what) + ": internal error: the kept records do not add up to the list's count"); return PLASSHIP_ERR_DEVICE; }
+    return PLASSHIP_OK;
+}
+
+// ---- RescoreList: the host side of a list-in, list-out rescoring call (common.hpp) ----
+int RescoreList::prepare(size_t slotBytes_, bool wrapped, const double *evalThr, const plasship_clusters *subset) {
+    const std::string w(what);
+    slotBytes = slotBytes_;
+    if (ctx->hasComm && ctx->comm.world > 1) { setError(w + ": not part of a sharded run (a communicator of more than one rank is set)"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (c->nQueries != qdb->n) { setError(w + (tdb ? ": candidate list does not belong to the query DB" : ": candidate list does not belong to the DB")); return PLASSHIP_ERR_ARG; }
+    if (tdb && qdb->dbtype != tdb->dbtype) { setError(w + ": query and target DB types differ"); return PLASSHIP_ERR_ARG; }
+    nucl = qdb->dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES;
+    if (wrapped && !nucl) { setError("Wrapped scoring is only supported for nucleotides."); return PLASSHIP_ERR_ARG; }      // rescorediagonal.cpp:70-76
+    if (c->reverseCapable && !nucl) { setError(w + ": a candidate list with strands on a DB that is not nucleotides"); return PLASSHIP_ERR_ARG; }
+    PH_ENTER(ctx);
+    const uint64_t nHits = c->nHits;
+    const size_t nQ = qdb->n;
+    residues = (tdb ? tdb : qdb)->residues;
+    if (subset) {
+        if (subset->n != qdb->n || subset->dbGen != qdb->gen) { setError(w + ": the clustering does not belong to this DB"); return PLASSHIP_ERR_ARG; }
+        std::vector<uint32_t> lens(nQ), repOf(nQ);
+        PH_CHECK(streamSync(ctx->stream));
+        if (nQ) { int rc = stagedCopyToHost(ctx, lens.data(), qdb->d_len.p, nQ * 4); if (!rc) rc = stagedCopyToHost(ctx, repOf.data(), subset->d_repOf.p, nQ * 4); if (rc) return rc; }
+        residues = 0;
+        for (size_t q = 0; q < nQ; q++) if (repOf[q] == q) residues += lens[q];
+    }
+    if (dKeep.alloc(std::max<uint64_t>(nHits, 1) * 4) != hipSuccess || dSlots.alloc(std::max<uint64_t>(nHits, 1) * slotBytes) != hipSuccess ||
+        dStats.alloc(RL_NSTATS * 8) != hipSuccess || (evalThr && dMat.alloc(123 * 123) != hipSuccess)) {
+        setError(w + ": out of device memory"); return PLASSHIP_ERR_DEVICE;
+    }
+    PH_CHECK(hipMemsetAsync(dStats.p, 0, RL_NSTATS * 8, ctx->stream));
+    args.hits = c->d_hits.as<CandHit>(); args.nHits = nHits; args.keep = dKeep.as<uint32_t>(); args.reverseCapable = c->reverseCapable;
+    args.stats = dStats.as<unsigned long long>();
+    if (evalThr) {
+        const HostEvaluer ev(nucl, residues);
+        if (const int rc = evalueGateTable(ctx, what, qdb, ev, *evalThr, dMinScore, hMinScore)) return rc;
+        PH_CHECK(hipMemcpyAsync(dMat.p, asciiSubMat(nucl), 123 * 123, hipMemcpyHostToDevice, ctx->stream));
+        args.minScore = dMinScore.as<uint32_t>(); args.minScoreLen = (uint32_t) hMinScore.size(); args.mat = dMat.as<signed char>();
+        args.lambda = ev.g[0]; args.logK = ev.logK; args.ln2 = ev.ln2;
+    }
+    { int rc = ensureOffLen(ctx, qdb); if (!rc && tdb) rc = ensureOffLen(ctx, tdb); if (rc) return rc; }
+    PH_CHECK(hipEventRecord(ctx->ev[0], ctx->stream));
+    return PLASSHIP_OK;
+}
+
+int RescoreList::collect(DevBuf &outQoff, DevBuf &outRecs, plasship_rescore_stats *stats) {
+    PH_CHECK(hipEventRecord(ctx->ev[1], ctx->stream));
+    unsigned long long hs[RL_NSTATS] = {};
+    PH_CHECK(hipMemcpyAsync(hs, dStats.p, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
+    PH_CHECK(streamSync(ctx->stream));
+    PH_CHECK(hipGetLastError());
+    if (hs[RL_BAD]) { setError(std::string(what) + (tdb ? ": the candidate list names sequences that are not in the DBs" : ": the candidate list names sequences that are not in the DB")); return PLASSHIP_ERR_ARG; }
+    nKept = hs[RL_KEPT]; nNonSelf = hs[RL_VISIBLE];
+    if (const int rc = compactCsr(ctx, what, c->d_qoff.as<uint64_t>(), qdb->n, dSlots.p, slotBytes, dKeep.as<uint32_t>(), args.nHits, nKept, outQoff, outRecs)) return rc;
+    if (stats) {
+        stats->n_scored = args.nHits; stats->n_accepted = nKept; stats->overlap_residues = hs[RL_RESIDUES];
+        float ms = 0; (void) hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); stats->ms_kernel = ms;
+    }
     return PLASSHIP_OK;
 }
 

@@ -382,6 +382,64 @@ void mirror(int qs, int qe, int ds, int de, unsigned dl, int *o) { const AlnCoor
     assert four(lib.mirror, ctypes.c_int, 49, 20, 0, 29, 40) == (20, 49, 10, 39)
 
 
+def test_wrap_walk_agrees_with_the_reference_lines(tmp_path):
+    """plass_amd/csrc/asm_rules.hpp, forEachWrap: the walk over the wraps of a 16-bit diagonal that the rescore kernels of modes 0, 1 and 2
+    share, compiled with g++ as the kernels' build compiles it (-ffp-contract=off).  Every expected list of (diagonal, query offset, target
+    offset, columns) below is worked out by hand from DistanceCalculator.h:98-111 (the two loops and their order) and :119-125,148-150 (which
+    diagonals meet the sequences, and where), none by a second copy of the rule."""
+    import subprocess, ctypes
+    src = tmp_path / "w.cpp"
+    src.write_text(r'''
+#include "asm_rules.hpp"
+using namespace plasship;
+extern "C" int walk(unsigned d16, unsigned qLen, unsigned tLen, int *diag, unsigned *o, int cap) {
+    int n = 0;
+    forEachWrap(d16, qLen, tLen, [&](int real, const DiagSpan &s) {
+        if (n < cap) { diag[n] = real; o[3 * n] = s.qo; o[3 * n + 1] = s.to; o[3 * n + 2] = s.len; }
+        n++;
+    });
+    return n;
+}
+''')
+    so = tmp_path / "w.so"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "plass_amd", "csrc"), str(src), "-o", str(so)])
+    lib = ctypes.CDLL(str(so))
+
+    def walk(d16, qLen, tLen):
+        diag, o = (ctypes.c_int * 8)(), (ctypes.c_uint * 24)()
+        n = lib.walk(d16, qLen, tLen, diag, o, 8)
+        assert 0 <= n <= 8
+        return [(diag[i], o[3 * i], o[3 * i + 1], o[3 * i + 2]) for i in range(n)]
+
+    # both lengths below 32 768: the loops try d16 - 65536 and d16 only.  Query of 50, target of 30:
+    assert walk(0, 50, 30) == [(0, 0, 0, 30)]                       # d16 = 0: min(30, 50 - 0) columns
+    assert walk(49, 50, 30) == [(49, 49, 0, 1)]                     # d16 = qLen - 1: 49 < 50, min(30, 1)
+    assert walk(50, 50, 30) == []                                   # d16 = qLen: 50 < 50 fails, and 65486 < 30 fails
+    assert walk(65535, 50, 30) == [(-1, 0, 1, 29)]                  # d16 = 65535 is -1: 1 < 30, min(30 - 1, 50); 65535 < 50 fails
+    assert walk(65507, 50, 30) == [(-29, 0, 29, 1)]                 # -(tLen - 1): min(1, 50)
+    assert walk(65506, 50, 30) == []                                # -tLen: 30 < 30 fails; no wrap meets either sequence
+    assert walk(30000, 50, 30) == []                                # 30000 < 50 fails, 35536 < 30 fails
+    # the first loop's bound 1 + tLen / 32768, query of 100.  d16 = 65535: j = 1 is -1, j = 2 is -65537, which needs tLen > 65537
+    for tLen in (32767, 32768, 65535, 65536, 65537):
+        assert walk(65535, 100, tLen) == [(-1, 0, 1, 100)], tLen    # min(tLen - 1, 100)
+    assert walk(65535, 100, 65538) == [(-1, 0, 1, 100), (-65537, 0, 65537, 1)]
+    # d16 = 1: j = 1 is -65535, which needs tLen > 65535; then the diagonal 1 itself: 1 < 100, min(tLen, 99)
+    for tLen in (32767, 32768, 65535):
+        assert walk(1, 100, tLen) == [(1, 1, 0, 99)], tLen
+    assert walk(1, 100, 65536) == [(-65535, 0, 65535, 1), (1, 1, 0, 99)]
+    assert walk(1, 100, 65537) == [(-65535, 0, 65535, 2), (1, 1, 0, 99)]
+    # the second loop's bound qLen / 65536, target of 100.  d16 = 0: j = 1 is 65536, which needs qLen > 65536
+    assert walk(0, 65535, 100) == [(0, 0, 0, 100)]
+    assert walk(0, 65536, 100) == [(0, 0, 0, 100)]
+    assert walk(0, 131072, 100) == [(0, 0, 0, 100), (65536, 65536, 0, 100)]         # j = 2 is 131072: 131072 < 131072 fails
+    assert walk(65535, 65535, 100) == [(-1, 0, 1, 99)]                                # 65535 < 65535 fails
+    assert walk(65535, 65536, 100) == [(-1, 0, 1, 99), (65535, 65535, 0, 1)]          # min(100, 65536 - 65535)
+    # both loops with more than one wrap: query of 100 000, target of 65 538, d16 = 65535 (j = 3 is -131073; j = 1 of the second loop is 131071)
+    assert walk(65535, 100000, 65538) == [(-1, 0, 1, 65537), (-65537, 0, 65537, 1), (65535, 65535, 0, 34465)]
+    # the wrap_tie case of the GPU tests, 70 000 against 70 000 at d16 = 100: -65436 (70000 - 65436 = 4564 columns), 100 (69900), 65636 (4364)
+    assert walk(100, 70000, 70000) == [(-65436, 0, 65436, 4564), (100, 100, 0, 69900), (65636, 65636, 0, 4364)]
+
+
 def test_cli_exit_codes_separate_unsupported_from_failed():
     """plass-hip's exit-code contract (INTEGRATION.md section 1; no GPU needed with PLASSHIP_CLI_DRYRUN=1): 95 = the call is well-formed
     for the reference but outside the GPU path (the wrapper hands it to the reference binary: linclust's rescorediagonal at the end of
