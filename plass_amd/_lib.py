@@ -926,15 +926,18 @@ class Candidates:
             self.ctx.lib.plasship_cands_free(self.ctx.h, self.h); self.h = P()
 
 
-class Clusters:
-    """greedy clustering of a DB, device resident"""
+class _PairList:
+    """(representative, member) pairs over a DB, device resident; a subclass names the loader of the library with its entry points and their prefix"""
     def __init__(self, ctx, h, db):
         self.ctx, self.h, self.db = ctx, h, db      # keeps the DB alive (ids -> keys)
+
+    def _call(self, name, *args):
+        _check(getattr(self._load(), self._prefix + name)(*args), self._prefix + name)
 
     def count(self):
         """(members = DB size, clusters)"""
         n = C.c_uint64(); k = C.c_uint64()
-        _check(self.ctx.lib.clust.plasship_clusters_count(self.h, C.byref(n), C.byref(k)), "plasship_clusters_count")
+        self._call("_count", self.h, C.byref(n), C.byref(k))
         return n.value, k.value
 
     def download(self, db=None):
@@ -942,42 +945,32 @@ class Clusters:
         import numpy as np
         n = self.count()[0]
         rep = np.zeros(n, dtype=np.uint32); mem = np.zeros(n, dtype=np.uint32)
-        _check(self.ctx.lib.clust.plasship_clusters_download(self.ctx.h, self.h, (db or self.db).h, rep.ctypes.data, mem.ctypes.data), "plasship_clusters_download")
+        self._call("_download", self.ctx.h, self.h, (db or self.db).h, rep.ctypes.data, mem.ctypes.data)
         return rep, mem
 
     def write(self, path, db=None):
-        _check(self.ctx.lib.clust.plasship_clusters_write(self.ctx.h, self.h, (db or self.db).h, os.fsencode(path)), "plasship_clusters_write")
+        self._call("_write", self.ctx.h, self.h, (db or self.db).h, os.fsencode(path))
 
     def free(self):
         if self.h:
-            self.ctx.lib.clust.plasship_clusters_free(self.ctx.h, self.h); self.h = P()
+            getattr(self._load(), self._prefix + "_free")(self.ctx.h, self.h); self.h = P()
 
 
-class MergedClusters:
+class Clusters(_PairList):
+    """greedy clustering of a DB, device resident"""
+    _load, _prefix = staticmethod(lambda: load_library().clust), "plasship_clusters"
+
+
+class MergedClusters(_PairList):
     """what mergeclusters makes of two clusterings of a DB, device resident: the members in the merged DB's order"""
-    def __init__(self, ctx, h, db):
-        self.ctx, self.h, self.db = ctx, h, db      # keeps the DB alive (ids -> keys)
-
-    def count(self):
-        """(members = DB size, clusters)"""
-        n = C.c_uint64(); k = C.c_uint64()
-        _check(load_linclust_library().plasship_merged_count(self.h, C.byref(n), C.byref(k)), "plasship_merged_count")
-        return n.value, k.value
+    _load, _prefix = staticmethod(load_linclust_library), "plasship_merged"
 
     def download(self):
         """(representative keys, member keys) in the merged DB's order"""
-        import numpy as np
-        n = self.count()[0]
-        rep = np.zeros(n, dtype=np.uint32); mem = np.zeros(n, dtype=np.uint32)
-        _check(load_linclust_library().plasship_merged_download(self.ctx.h, self.h, self.db.h, rep.ctypes.data, mem.ctypes.data), "plasship_merged_download")
-        return rep, mem
+        return _PairList.download(self)
 
     def write(self, path):
-        _check(load_linclust_library().plasship_merged_write(self.ctx.h, self.h, self.db.h, os.fsencode(path)), "plasship_merged_write")
-
-    def free(self):
-        if self.h:
-            load_linclust_library().plasship_merged_free(self.ctx.h, self.h); self.h = P()
+        _PairList.write(self, path)
 
 
 class Alignments:

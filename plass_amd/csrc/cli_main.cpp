@@ -833,43 +833,27 @@ static void printClustStats(const plasship_clust_stats &st) {
     fprintf(stdout, "sequences: %llu edges: %llu clusters: %llu promoted: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_sequences, (unsigned long long) st.n_edges,
             (unsigned long long) st.n_clusters, (unsigned long long) st.n_promoted, st.ms_kernel);
 }
-static int runClustGreedy(Call &c) {
-    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
-    SeqDb db(ctx); Cands cands(ctx); Alns al(ctx); Clusters cl(ctx); plasship_clust_stats st = {};
-    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out()))) return fail("clust-greedy");
-    size_t n = 0; plasship_seqdb_info(db, &n, nullptr, nullptr, nullptr, nullptr);
-    if (indexLines(pos[1]) != (long) n) { fprintf(stdout, "Sequence db size != result db size\n"); return EXIT_FAILURE; }      // ClusteringAlgorithms.cpp:20-23
-    if (probeDbtype(pos[1]) == PLASSHIP_DBTYPE_ALIGNMENT_RES) {
-        // (lines plasship_alns_read cannot take — fewer than ten columns — are left to the reference: nothing has been written)
-        if (K(plasship_alns_read(ctx, db, pos[1].c_str(), al.out())))
-            return g_lastRc == PLASSHIP_ERR_ARG ? unsupported("plass-hip clust-greedy: %s\n", plasship_last_error()) : fail("clust-greedy");
-        if (K(plasship_clust_greedy_alns(ctx, db, al, cl.out(), &st))) return fail("clust-greedy");
-    } else {
-        if (K(plasship_cands_read(ctx, db, db, pos[1].c_str(), cands.out())) || K(plasship_clust_greedy_cands(ctx, db, cands, cl.out(), &st))) return fail("clust-greedy");
-    }
-    printClustStats(st);
-    return KW(plasship_clusters_write(ctx, cl, db, pos[2].c_str())) ? fail("clust-greedy") : EXIT_SUCCESS;
-}
 static void printCcStats(const plasship_cc_stats &st) {
     fprintf(stdout, "sequences: %llu edges: %llu clusters: %llu missing links: %llu | hook rounds: %u bfs levels: %u | kernel ms: %.3f\n", (unsigned long long) st.n_sequences,
             (unsigned long long) st.n_edges, (unsigned long long) st.n_clusters, (unsigned long long) st.n_missing_links, st.n_hook_rounds, st.n_bfs_levels, st.ms_kernel);
 }
-static int runClustConnected(Call &c) {
-    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
-    SeqDb db(ctx); Cands cands(ctx); Alns al(ctx); Clusters cl(ctx); plasship_cc_stats st = {};
-    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out()))) return fail("clust-connected");
+static int runClust(Call &c) {                    // clust-greedy and clust-connected: <seqDB> <resultDB> <cluDB>
+    plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos; const char *name = c.m->name; const bool connected = c.m->id == CLUST_CONNECTED;
+    SeqDb db(ctx); Cands cands(ctx); Alns al(ctx); Clusters cl(ctx); plasship_clust_stats st = {}; plasship_cc_stats cs = {};
+    if (K(plasship_seqdb_read(ctx, pos[0].c_str(), db.out()))) return fail(name);
     size_t n = 0; plasship_seqdb_info(db, &n, nullptr, nullptr, nullptr, nullptr);
     if (indexLines(pos[1]) != (long) n) { fprintf(stdout, "Sequence db size != result db size\n"); return EXIT_FAILURE; }      // ClusteringAlgorithms.cpp:20-23
     if (probeDbtype(pos[1]) == PLASSHIP_DBTYPE_ALIGNMENT_RES) {
         // (lines plasship_alns_read cannot take — fewer than ten columns — are left to the reference: nothing has been written)
         if (K(plasship_alns_read(ctx, db, pos[1].c_str(), al.out())))
-            return g_lastRc == PLASSHIP_ERR_ARG ? unsupported("plass-hip clust-connected: %s\n", plasship_last_error()) : fail("clust-connected");
-        if (K(plasship_clust_connected_alns(ctx, db, al, c.f.maxIterations, cl.out(), &st))) return fail("clust-connected");
+            return g_lastRc == PLASSHIP_ERR_ARG ? unsupported("plass-hip %s: %s\n", name, plasship_last_error()) : fail(name);
+        if (K(connected ? plasship_clust_connected_alns(ctx, db, al, c.f.maxIterations, cl.out(), &cs) : plasship_clust_greedy_alns(ctx, db, al, cl.out(), &st))) return fail(name);
     } else {
-        if (K(plasship_cands_read(ctx, db, db, pos[1].c_str(), cands.out())) || K(plasship_clust_connected_cands(ctx, db, cands, c.f.maxIterations, cl.out(), &st))) return fail("clust-connected");
+        if (K(plasship_cands_read(ctx, db, db, pos[1].c_str(), cands.out())) ||
+            K(connected ? plasship_clust_connected_cands(ctx, db, cands, c.f.maxIterations, cl.out(), &cs) : plasship_clust_greedy_cands(ctx, db, cands, cl.out(), &st))) return fail(name);
     }
-    printCcStats(st);
-    return KW(plasship_clusters_write(ctx, cl, db, pos[2].c_str())) ? fail("clust-connected") : EXIT_SUCCESS;
+    if (connected) printCcStats(cs); else printClustStats(st);
+    return KW(plasship_clusters_write(ctx, cl, db, pos[2].c_str())) ? fail(name) : EXIT_SUCCESS;
 }
 static int runLinclustPre(Call &c) {              // kmermatcher -> rescorediagonal (Hamming) -> clust -> createsubdb + filterdb of pref, on handles
     plasship_ctx *ctx = c.ctx; const Flags &f = c.f;
@@ -1199,9 +1183,9 @@ static const Module kModules[] = {
     {"rescorediagonal-hamming", RESCOREDIAGONAL_HAMMING, 4, "rescorediagonal-hamming <i:queryDB> <i:targetDB> <i:prefDB> <o:prefDB>", nullptr, validateRescoreHamming, runRescoreHamming},
     {"rescorediagonal-local", RESCOREDIAGONAL_LOCAL, 4, "rescorediagonal-local <i:queryDB> <i:targetDB> <i:prefDB> <o:alnDB>", nullptr, validateRescoreLocal, runRescoreLocal},
     // linclust's greedy `clust` and its whole pre-cluster stage, lib/mmseqs/data/workflow/linclust.sh:21-57 (our own names: `clust` and `linclust` stay with the reference)
-    {"clust-greedy", CLUST_GREEDY, 3, "clust-greedy <i:sequenceDB> <i:resultDB> <o:clusterDB>", nullptr, validateClustGreedy, runClustGreedy},
+    {"clust-greedy", CLUST_GREEDY, 3, "clust-greedy <i:sequenceDB> <i:resultDB> <o:clusterDB>", nullptr, validateClustGreedy, runClust},
     // connected component under its own name, lib/mmseqs/data/workflow/linclust.sh:35,82 with --cluster-mode 1
-    {"clust-connected", CLUST_CONNECTED, 3, "clust-connected <i:sequenceDB> <i:resultDB> <o:clusterDB>", nullptr, validateClustConnected, runClustConnected},
+    {"clust-connected", CLUST_CONNECTED, 3, "clust-connected <i:sequenceDB> <i:resultDB> <o:clusterDB>", nullptr, validateClustConnected, runClust},
     {"linclust-pre", LINCLUST_PRE, 3, "linclust-pre <i:sequenceDB> <o:preClusterDB> <o:prefilterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; }, validateLinclustPre, runLinclustPre},
     {"mergeclusters-greedy", MERGECLUSTERS_GREEDY, 4, "mergeclusters-greedy <i:sequenceDB> <o:clusterDB> <i:clusterDB1> <i:clusterDB2>", nullptr, validateMergeclusters, runMergeclusters},
     {"linclust-ungapped", LINCLUST_UNGAPPED, 2, "linclust-ungapped <i:sequenceDB> <o:clusterDB>", [](Flags &f) { f.covThr = 0.8f; f.alph = 13; f.kps = 0; f.filterHits = 1; }, validateLinclustUngapped, runLinclustUngapped},

@@ -26,7 +26,10 @@
 // duplicate lines and the unscored identity stubs of an alignment list are minima that change nothing.  The pairs are sorted by a second
 // radix sort (ids are ranks in key order, so id order is key order) and the entries' text is laid out by a scan of the per-pair byte counts.
 // Algorithmic bytes: 16 per sequence and sort pass, 4 (target id) + one 4-byte atomic per edge; unmeasured, see DESIGN.md.
-#include "common.hpp"
+//
+// This file also defines what clust_shared.hpp declares for the whole clustering family (clust_cc.hip, merge_clusters.hip, repseqs.hip): the
+// length rank, the key sort, the list-against-DB checks, and count, download and the cluster-DB writer of a PairList.
+#include "clust_shared.hpp"
 #include "../../include/plasship_ext/clust.h"
 #include "device_utils.hpp"
 #include "host_util.hpp"
@@ -40,10 +43,7 @@ namespace plasship {
 constexpr int CL_BLOCK = 256;
 constexpr uint32_t CL_WAVE_MAX_LINES = 1024;     // 16 steps of a wavefront; longer lists go to the workgroup kernel
 
-__device__ __forceinline__ bool edgeTarget(const CandHit &r, uint32_t &t) { t = r.target; return true; }
-__device__ __forceinline__ bool edgeTarget(const AlnRec &r, uint32_t &t) { t = r.target; return r.accepted != 0; }      // (a sparse list keeps rejected pairs as holes)
-
-__global__ void clustRankKeyKernel(const uint32_t *__restrict__ len, uint64_t *__restrict__ keys, uint32_t n) {
+__global__ void lengthRankKeyKernel(const uint32_t *__restrict__ len, uint64_t *__restrict__ keys, uint32_t n) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) keys[i] = ((uint64_t) ~len[i] << 32) | i;
 }
 __global__ void clustRankScatterKernel(const uint64_t *__restrict__ sorted, uint32_t *__restrict__ rank, uint32_t *__restrict__ idOfRank,
@@ -60,8 +60,8 @@ __device__ __forceinline__ unsigned edgesOfQuery(const Rec *__restrict__ recs, u
                                                  const uint32_t *__restrict__ rank, uint32_t *__restrict__ assigned) {
     unsigned bad = 0;
     for (uint64_t i = b + first; i < e; i += step) {
-        uint32_t t;
-        if (!edgeTarget(recs[i], t)) continue;
+        uint32_t q, t;
+        if (!lineOf(recs[i], q, t)) continue;
         if (t >= n) { bad++; continue; }
         atomicMin(&assigned[rank[t]], rq);
     }
@@ -118,8 +118,8 @@ __global__ void clustApplyKernel(const uint32_t *__restrict__ assigned0, const u
     if (laneId() == 0) { if (reps) atomicAdd(&stats[2], (unsigned long long) reps); if (promoted) atomicAdd(&stats[3], (unsigned long long) promoted); }
 }
 
-// ---- the cluster DB's text (Clustering::writeData): pair j contributes the representative's line when it opens an entry, its own line unless
-//      it is the representative, and the entry's '\0' when it closes one ----
+// ---- the cluster DB's text: pair j contributes the entry's '\0' when it closes one and, before it, its member's line.  repFirst
+//      (Clustering::writeData): the representative's line when it opens an entry, and no member line when it is the representative ----
 __device__ __forceinline__ uint32_t decDigits(uint32_t v) {
     return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u : v < 10000000u ? 7u : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
 }
@@ -134,22 +134,24 @@ __device__ __forceinline__ void pairEnds(const uint64_t *__restrict__ pairs, uin
     head = j == 0 || (uint32_t) (pairs[j - 1] >> 32) != rep;
     tail = j + 1 == n || (uint32_t) (pairs[j + 1] >> 32) != rep;
 }
-__global__ void clustTextLenKernel(const uint64_t *__restrict__ pairs, const uint32_t *__restrict__ keys, uint64_t n, uint32_t *__restrict__ bytes, uint32_t *__restrict__ heads) {
+template <bool repFirst>
+__global__ void pairTextLenKernel(const uint64_t *__restrict__ pairs, const uint32_t *__restrict__ keys, uint64_t n, uint32_t *__restrict__ bytes, uint32_t *__restrict__ heads) {
     for (uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t) gridDim.x * blockDim.x) {
         const uint32_t rep = (uint32_t) (pairs[j] >> 32), mem = (uint32_t) pairs[j];
         bool head, tail; pairEnds(pairs, j, n, head, tail);
-        bytes[j] = (head ? decDigits(keys[rep]) + 1u : 0u) + (mem != rep ? decDigits(keys[mem]) + 1u : 0u) + (tail ? 1u : 0u);
+        bytes[j] = (repFirst && head ? decDigits(keys[rep]) + 1u : 0u) + (!repFirst || mem != rep ? decDigits(keys[mem]) + 1u : 0u) + (tail ? 1u : 0u);
         heads[j] = head ? 1u : 0u;
     }
 }
-__global__ void clustTextWriteKernel(const uint64_t *__restrict__ pairs, const uint32_t *__restrict__ keys, uint64_t n, const uint64_t *__restrict__ pos,
-                                     const uint64_t *__restrict__ entryOf, char *__restrict__ text, uint64_t *__restrict__ entryOff, uint32_t *__restrict__ entryKey) {
+template <bool repFirst>
+__global__ void pairTextWriteKernel(const uint64_t *__restrict__ pairs, const uint32_t *__restrict__ keys, uint64_t n, const uint64_t *__restrict__ pos,
+                                    const uint64_t *__restrict__ entryOf, char *__restrict__ text, uint64_t *__restrict__ entryOff, uint32_t *__restrict__ entryKey) {
     for (uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t) gridDim.x * blockDim.x) {
         const uint32_t rep = (uint32_t) (pairs[j] >> 32), mem = (uint32_t) pairs[j];
         bool head, tail; pairEnds(pairs, j, n, head, tail);
-        char *p = text + pos[j];                          // (pos[j + 1] - pos[j] bytes are this pair's: clustTextLenKernel counted what is written here)
-        if (head) { p = putKeyLine(p, keys[rep]); entryOff[entryOf[j]] = pos[j]; entryKey[entryOf[j]] = keys[rep]; }
-        if (mem != rep) p = putKeyLine(p, keys[mem]);
+        char *p = text + pos[j];                          // (pos[j + 1] - pos[j] bytes are this pair's: pairTextLenKernel counted what is written here)
+        if (head) { if (repFirst) p = putKeyLine(p, keys[rep]); entryOff[entryOf[j]] = pos[j]; entryKey[entryOf[j]] = keys[rep]; }
+        if (!repFirst || mem != rep) p = putKeyLine(p, keys[mem]);
         if (tail) *p = '\0';
     }
 }
@@ -174,23 +176,26 @@ __global__ void clustFilterFlagKernel(const CandHit *__restrict__ hits, uint64_t
     }
 }
 
-static unsigned gridFor(uint64_t n, const plasship_ctx *ctx) { return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->numCU * 32)); }
-
-static int sortU64(plasship_ctx *ctx, uint64_t *in, uint64_t *out, uint32_t n, const char *what) {
+int sortKeysU64(plasship_ctx *ctx, const char *what, uint64_t *in, uint64_t *out, uint64_t n) {
+    if (n > 0xFFFFFFFFull) { setError(std::string(what) + ": list sizes are 32-bit"); return PLASSHIP_ERR_UNSUPPORTED; }      // (rocPRIM's size; every caller refuses earlier, at its own limit)
     size_t tmpBytes = 0;
-    PH_CHECK(rocprim::radix_sort_keys(nullptr, tmpBytes, in, out, n, 0, 64, ctx->stream));
+    PH_CHECK(rocprim::radix_sort_keys(nullptr, tmpBytes, in, out, (unsigned int) n, 0, 64, ctx->stream));
     DevBuf tmp;
     if (tmp.alloc(std::max<size_t>(tmpBytes, 8)) != hipSuccess) { setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    PH_CHECK(rocprim::radix_sort_keys(tmp.p, tmpBytes, in, out, n, 0, 64, ctx->stream));
+    PH_CHECK(rocprim::radix_sort_keys(tmp.p, tmpBytes, in, out, (unsigned int) n, 0, 64, ctx->stream));
     PH_CHECK(plasship::streamSync(ctx->stream));          // (tmp is released with this function)
     return PLASSHIP_OK;
+}
+int lengthRank(plasship_ctx *ctx, const char *what, const plasship_seqdb *db, uint64_t *keysTmp, uint64_t *sortedOut) {
+    hipLaunchKernelGGL(lengthRankKeyKernel, dim3(flatGrid(db->n, ctx->numCU)), dim3(256), 0, ctx->stream, db->d_len.as<uint32_t>(), keysTmp, (uint32_t) db->n);
+    return sortKeysU64(ctx, what, keysTmp, sortedOut, db->n);
 }
 
 template <class Rec>
 static int clustGreedy(plasship_ctx *ctx, const plasship_seqdb *db, const uint64_t *dQoff, const Rec *dRecs, uint64_t nRecs, plasship_clusters **out,
                        plasship_clust_stats *stats, const char *what) {
     PH_ENTER(ctx);
-    if (db->n >= 0xFFFFFFFFull) { setError(std::string(what) + ": ids are 32-bit"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseWideIds(what, db)) return rc;
     const uint32_t n = (uint32_t) db->n;
     const uint64_t n1 = std::max<uint32_t>(n, 1);
     const uint32_t longCap = (uint32_t) std::min<uint64_t>(n1, nRecs / (CL_WAVE_MAX_LINES + 1) + 1);
@@ -208,10 +213,9 @@ static int clustGreedy(plasship_ctx *ctx, const plasship_seqdb *db, const uint64
     PH_CHECK(hipMemsetAsync(dFlag.p, 0, n1 * 4, ctx->stream));
     PH_CHECK(hipEventRecord(ctx->ev[0], ctx->stream));
     if (n) {
-        const unsigned g = gridFor(n, ctx);
+        const unsigned g = flatGrid(n, ctx->numCU);
         // the rank: position in the order (length descending, id ascending)
-        hipLaunchKernelGGL(clustRankKeyKernel, dim3(g), dim3(256), 0, ctx->stream, db->d_len.as<uint32_t>(), dKeys.as<uint64_t>(), n);
-        { const int rc = sortU64(ctx, dKeys.as<uint64_t>(), dSorted.as<uint64_t>(), n, what); if (rc) return rc; }
+        if (const int rc = lengthRank(ctx, what, db, dKeys.as<uint64_t>(), dSorted.as<uint64_t>())) return rc;
         hipLaunchKernelGGL(clustRankScatterKernel, dim3(g), dim3(256), 0, ctx->stream, dSorted.as<uint64_t>(), dRank.as<uint32_t>(), dIdOfRank.as<uint32_t>(), dAssigned.as<uint32_t>(), n);
         // pass 1
         if (nRecs) {
@@ -225,7 +229,7 @@ static int clustGreedy(plasship_ctx *ctx, const plasship_seqdb *db, const uint64
         hipLaunchKernelGGL(clustFlagKernel, dim3(g), dim3(256), 0, ctx->stream, dAssigned.as<uint32_t>(), dFlag.as<uint32_t>(), n);
         hipLaunchKernelGGL(clustApplyKernel, dim3(g), dim3(256), 0, ctx->stream, dAssigned.as<uint32_t>(), dFlag.as<uint32_t>(), dRank.as<uint32_t>(), dIdOfRank.as<uint32_t>(),
                            cl->d_repOf.as<uint32_t>(), dPairs.as<uint64_t>(), n, dStats.as<unsigned long long>());
-        { const int rc = sortU64(ctx, dPairs.as<uint64_t>(), cl->d_pairs.as<uint64_t>(), n, what); if (rc) return rc; }
+        if (const int rc = sortKeysU64(ctx, what, dPairs.as<uint64_t>(), cl->d_pairs.as<uint64_t>(), n)) return rc;
     }
     PH_CHECK(hipEventRecord(ctx->ev[1], ctx->stream));
     PH_CHECK(hipMemcpyAsync(hs, dStats.p, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -241,75 +245,46 @@ static int clustGreedy(plasship_ctx *ctx, const plasship_seqdb *db, const uint64
     return PLASSHIP_OK;
 }
 
-static int checkClusters(const plasship_clusters *cl, const plasship_seqdb *db, const char *what) {
-    if (cl->n != db->n || cl->dbGen != db->gen) { setError(std::string(what) + ": the clustering does not belong to this DB"); return PLASSHIP_ERR_ARG; }
-    return PLASSHIP_OK;
-}
-static int fetchKeys(plasship_ctx *ctx, const plasship_seqdb *db, std::vector<uint32_t> &keys) {
-    keys.resize(db->n);
-    PH_CHECK(plasship::streamSync(ctx->stream));
-    return db->n ? stagedCopyToHost(ctx, keys.data(), db->d_key.p, db->n * 4) : PLASSHIP_OK;
-}
-
-}  // namespace plasship
-using namespace plasship;
-
-static int unsharded(const plasship_ctx *ctx, const char *what) {
-    if (ctx->hasComm && ctx->comm.world > 1) { setError(std::string(what) + ": not part of a sharded run (a communicator of more than one rank is set)"); return PLASSHIP_ERR_UNSUPPORTED; }
-    return PLASSHIP_OK;
-}
-
-extern "C" int plasship_clust_greedy_cands(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_cands *c, plasship_clusters **out, plasship_clust_stats *stats) {
-    const char *what = "plasship_clust_greedy_cands";
-    if (!ctx || !db || !c || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (const int rc = unsharded(ctx, what)) return rc;
-    // ClusteringAlgorithms.cpp:20-23: "Sequence db size != result db size"
+int checkListOnDb(const char *what, const plasship_seqdb *db, const plasship_cands *c) {
     if (c->nQueries != db->n) { setError(std::string(what) + ": the candidate list has another number of queries than the DB has sequences"); return PLASSHIP_ERR_ARG; }
-    return clustGreedy<CandHit>(ctx, db, c->d_qoff.as<uint64_t>(), c->d_hits.as<CandHit>(), c->nHits, out, stats, what);
+    return PLASSHIP_OK;
 }
-
-extern "C" int plasship_clust_greedy_alns(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_alns *a, plasship_clusters **out, plasship_clust_stats *stats) {
-    const char *what = "plasship_clust_greedy_alns";
-    if (!ctx || !db || !a || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (const int rc = unsharded(ctx, what)) return rc;
+int checkListOnDb(const char *what, const plasship_seqdb *db, const plasship_alns *a) {
     if (a->nQueries != db->n) { setError(std::string(what) + ": the alignment list has another number of queries than the DB has sequences"); return PLASSHIP_ERR_ARG; }
     if (a->qdb != db || a->tdb != db) { setError(std::string(what) + ": the alignment list was built on another DB"); return PLASSHIP_ERR_ARG; }
-    return clustGreedy<AlnRec>(ctx, db, a->d_qoff.as<uint64_t>(), a->d_recs.as<AlnRec>(), a->nSlots, out, stats, what);
-}
-
-extern "C" int plasship_clusters_count(const plasship_clusters *cl, uint64_t *n_members, uint64_t *n_clusters) {
-    if (!cl) { setError("plasship_clusters_count: NULL"); return PLASSHIP_ERR_ARG; }
-    if (n_members) *n_members = cl->n;
-    if (n_clusters) *n_clusters = cl->nClusters;
     return PLASSHIP_OK;
 }
 
-extern "C" void plasship_clusters_free(plasship_ctx *ctx, plasship_clusters *cl) {
-    if (!cl) return;
-    if (ctx) { (void) hipSetDevice(ctx->device); plasship::poolEnter(ctx->stream); }
-    delete cl;
+int pairListCount(const char *what, const PairList *list, uint64_t *nMembers, uint64_t *nClusters) {
+    if (!list) { setError(std::string(what) + ": NULL"); return PLASSHIP_ERR_ARG; }
+    if (nMembers) *nMembers = list->n;
+    if (nClusters) *nClusters = list->nClusters;
+    return PLASSHIP_OK;
 }
 
-extern "C" int plasship_clusters_download(plasship_ctx *ctx, const plasship_clusters *cl, const plasship_seqdb *db, uint32_t *rep_key, uint32_t *member_key) {
-    if (!ctx || !cl || !db) { setError("plasship_clusters_download: bad argument"); return PLASSHIP_ERR_ARG; }
-    if (const int rc = checkClusters(cl, db, "plasship_clusters_download")) return rc;
+int pairListDownload(plasship_ctx *ctx, const char *what, const PairList *list, const plasship_seqdb *db, uint32_t *repKey, uint32_t *memberKey) {
+    if (!ctx || !list || !db) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
+    if (const int rc = refuseForeign(what, list, db)) return rc;
     PH_ENTER(ctx);
-    std::vector<uint32_t> keys; std::vector<uint64_t> pairs(cl->n);
-    int rc = fetchKeys(ctx, db, keys); if (rc) return rc;
-    if (cl->n) { rc = stagedCopyToHost(ctx, pairs.data(), cl->d_pairs.p, cl->n * 8); if (rc) return rc; }
-    for (size_t j = 0; j < cl->n; j++) {
-        if (rep_key) rep_key[j] = keys[(size_t) (pairs[j] >> 32)];
-        if (member_key) member_key[j] = keys[(size_t) (uint32_t) pairs[j]];
+    const size_t n = list->n;
+    std::vector<uint32_t> keys(n); std::vector<uint64_t> pairs(n);
+    PH_CHECK(plasship::streamSync(ctx->stream));
+    if (n) {
+        int rc = stagedCopyToHost(ctx, keys.data(), db->d_key.p, n * 4); if (rc) return rc;
+        rc = stagedCopyToHost(ctx, pairs.data(), list->d_pairs.p, n * 8); if (rc) return rc;
+    }
+    for (size_t j = 0; j < n; j++) {
+        if (repKey) repKey[j] = keys[(size_t) (pairs[j] >> 32)];
+        if (memberKey) memberKey[j] = keys[(size_t) (uint32_t) pairs[j]];
     }
     return PLASSHIP_OK;
 }
 
-extern "C" int plasship_clusters_write(plasship_ctx *ctx, const plasship_clusters *cl, const plasship_seqdb *db, const char *db_path) {
-    const char *what = "plasship_clusters_write";
-    if (!ctx || !cl || !db || !db_path) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (const int rc = checkClusters(cl, db, what)) return rc;
+int pairListWrite(plasship_ctx *ctx, const char *what, const PairList *list, const plasship_seqdb *db, const char *dbPath, bool repFirst) {
+    if (!ctx || !list || !db || !dbPath) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
+    if (const int rc = refuseForeign(what, list, db)) return rc;
     PH_ENTER(ctx);
-    const uint64_t n = cl->n, nC = cl->nClusters;
+    const uint64_t n = list->n, nC = list->nClusters;
     std::vector<uint64_t> entryOff(nC + 1, 0); std::vector<uint32_t> entryKey(nC), elen(nC);
     uint64_t total = 0;
     DevBuf dBytes, dHeads, dPos, dEntryOf, dTmp, dText, dEntryOff, dEntryKey;
@@ -319,8 +294,9 @@ extern "C" int plasship_clusters_write(plasship_ctx *ctx, const plasship_cluster
             dTmp.alloc(tmpBytes) != hipSuccess || dEntryOff.alloc(std::max<uint64_t>(nC, 1) * 8) != hipSuccess || dEntryKey.alloc(std::max<uint64_t>(nC, 1) * 4) != hipSuccess) {
             setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE;
         }
-        const unsigned g = gridFor(n, ctx);
-        hipLaunchKernelGGL(clustTextLenKernel, dim3(g), dim3(256), 0, ctx->stream, cl->d_pairs.as<uint64_t>(), db->d_key.as<uint32_t>(), n, dBytes.as<uint32_t>(), dHeads.as<uint32_t>());
+        const unsigned g = flatGrid(n, ctx->numCU);
+        hipLaunchKernelGGL(repFirst ? pairTextLenKernel<true> : pairTextLenKernel<false>, dim3(g), dim3(256), 0, ctx->stream, list->d_pairs.as<uint64_t>(), db->d_key.as<uint32_t>(), n,
+                           dBytes.as<uint32_t>(), dHeads.as<uint32_t>());
         if (exclusiveScanU32(ctx->stream, dBytes.as<uint32_t>(), dPos.as<uint64_t>(), n, dTmp.p, tmpBytes) ||
             exclusiveScanU32(ctx->stream, dHeads.as<uint32_t>(), dEntryOf.as<uint64_t>(), n, dTmp.p, tmpBytes)) { (void) plasship::streamSync(ctx->stream); setError("scan failed"); return PLASSHIP_ERR_DEVICE; }
         uint64_t ends[2] = {0, 0};
@@ -330,8 +306,8 @@ extern "C" int plasship_clusters_write(plasship_ctx *ctx, const plasship_cluster
         total = ends[0];
         if (ends[1] != nC) { setError(std::string(what) + ": internal error: the number of entries differs from the number of clusters"); return PLASSHIP_ERR_DEVICE; }
         if (dText.alloc(std::max<uint64_t>(total, 1)) != hipSuccess) { setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
-        hipLaunchKernelGGL(clustTextWriteKernel, dim3(g), dim3(256), 0, ctx->stream, cl->d_pairs.as<uint64_t>(), db->d_key.as<uint32_t>(), n, dPos.as<uint64_t>(),
-                           dEntryOf.as<uint64_t>(), dText.as<char>(), dEntryOff.as<uint64_t>(), dEntryKey.as<uint32_t>());
+        hipLaunchKernelGGL(repFirst ? pairTextWriteKernel<true> : pairTextWriteKernel<false>, dim3(g), dim3(256), 0, ctx->stream, list->d_pairs.as<uint64_t>(), db->d_key.as<uint32_t>(), n,
+                           dPos.as<uint64_t>(), dEntryOf.as<uint64_t>(), dText.as<char>(), dEntryOff.as<uint64_t>(), dEntryKey.as<uint32_t>());
         PH_CHECK(plasship::streamSync(ctx->stream));
         PH_CHECK(hipGetLastError());
         int rc = stagedCopyToHost(ctx, entryOff.data(), dEntryOff.p, nC * 8); if (rc) return rc;
@@ -340,20 +316,57 @@ extern "C" int plasship_clusters_write(plasship_ctx *ctx, const plasship_cluster
     entryOff[nC] = total;
     for (uint64_t c = 0; c < nC; c++) elen[c] = (uint32_t) (entryOff[c + 1] - entryOff[c]);
     DBFileWriter w; std::string err;
-    if (!w.open(db_path, PLASSHIP_DBTYPE_CLUSTER_RES, err)) { setError(err); return PLASSHIP_ERR_IO; }
+    if (!w.open(dbPath, PLASSHIP_DBTYPE_CLUSTER_RES, err)) { setError(err); return PLASSHIP_ERR_IO; }
     if (total) {
         const int rc = stagedDownload(ctx, dText.p, total, [&](const char *src, uint64_t, uint64_t bytes) { w.data(src, bytes); return !w.failed.load(); });
-        if (rc) { setError(std::string(what) + ": writing " + db_path + " failed"); return rc; }
+        if (rc) { setError(std::string(what) + ": writing " + dbPath + " failed"); return rc; }
     }
     w.index(entryKey.data(), elen.data(), nC);
     if (!w.close(err)) { setError(err); return PLASSHIP_ERR_IO; }
     return PLASSHIP_OK;
 }
 
+}  // namespace plasship
+using namespace plasship;
+
+extern "C" int plasship_clust_greedy_cands(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_cands *c, plasship_clusters **out, plasship_clust_stats *stats) {
+    const char *what = "plasship_clust_greedy_cands";
+    if (!ctx || !db || !c || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
+    if (const int rc = refuseSharded(ctx, what)) return rc;
+    if (const int rc = checkListOnDb(what, db, c)) return rc;
+    return clustGreedy<CandHit>(ctx, db, c->d_qoff.as<uint64_t>(), c->d_hits.as<CandHit>(), c->nHits, out, stats, what);
+}
+
+extern "C" int plasship_clust_greedy_alns(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_alns *a, plasship_clusters **out, plasship_clust_stats *stats) {
+    const char *what = "plasship_clust_greedy_alns";
+    if (!ctx || !db || !a || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
+    if (const int rc = refuseSharded(ctx, what)) return rc;
+    if (const int rc = checkListOnDb(what, db, a)) return rc;
+    return clustGreedy<AlnRec>(ctx, db, a->d_qoff.as<uint64_t>(), a->d_recs.as<AlnRec>(), a->nSlots, out, stats, what);
+}
+
+extern "C" int plasship_clusters_count(const plasship_clusters *cl, uint64_t *n_members, uint64_t *n_clusters) {
+    return pairListCount("plasship_clusters_count", cl, n_members, n_clusters);
+}
+
+extern "C" void plasship_clusters_free(plasship_ctx *ctx, plasship_clusters *cl) {
+    if (!cl) return;
+    if (ctx) { (void) hipSetDevice(ctx->device); plasship::poolEnter(ctx->stream); }
+    delete cl;
+}
+
+extern "C" int plasship_clusters_download(plasship_ctx *ctx, const plasship_clusters *cl, const plasship_seqdb *db, uint32_t *rep_key, uint32_t *member_key) {
+    return pairListDownload(ctx, "plasship_clusters_download", cl, db, rep_key, member_key);
+}
+
+extern "C" int plasship_clusters_write(plasship_ctx *ctx, const plasship_clusters *cl, const plasship_seqdb *db, const char *db_path) {
+    return pairListWrite(ctx, "plasship_clusters_write", cl, db, db_path, true);
+}
+
 extern "C" int plasship_cands_filter(plasship_ctx *ctx, const plasship_cands *c, const plasship_clusters *cl, plasship_cands **out) {
     const char *what = "plasship_cands_filter";
     if (!ctx || !c || !cl || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (const int rc = unsharded(ctx, what)) return rc;
+    if (const int rc = refuseSharded(ctx, what)) return rc;
     if (c->nQueries != cl->n) { setError(std::string(what) + ": the candidate list and the clustering belong to DBs of different sizes"); return PLASSHIP_ERR_ARG; }
     PH_ENTER(ctx);
     const uint64_t nHits = c->nHits; const size_t nQ = c->nQueries;
@@ -362,7 +375,7 @@ extern "C" int plasship_cands_filter(plasship_ctx *ctx, const plasship_cands *c,
         setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE;
     }
     PH_CHECK(hipMemsetAsync(dStats.p, 0, 32, ctx->stream));
-    if (nHits) hipLaunchKernelGGL(clustFilterFlagKernel, dim3(gridFor(nHits, ctx)), dim3(256), 0, ctx->stream, c->d_hits.as<CandHit>(), nHits, cl->d_repOf.as<uint32_t>(), (uint32_t) cl->n,
+    if (nHits) hipLaunchKernelGGL(clustFilterFlagKernel, dim3(flatGrid(nHits, ctx->numCU)), dim3(256), 0, ctx->stream, c->d_hits.as<CandHit>(), nHits, cl->d_repOf.as<uint32_t>(), (uint32_t) cl->n,
                                   dKeep.as<uint32_t>(), dStats.as<unsigned long long>());
     unsigned long long hs[4] = {0, 0, 0, 0};
     PH_CHECK(hipMemcpyAsync(hs, dStats.p, 32, hipMemcpyDeviceToHost, ctx->stream));

@@ -4,7 +4,7 @@
 //
 // Reference behaviour reproduced (file:line in lib/mmseqs/src of the reference):
 //   clustering/Clustering.cpp:18-19                    the sequence DB is opened SORT_BY_LENGTH: every "id" of ClusteringAlgorithms is the position in
-//                                                      (length descending, key order ascending) — the LENGTH RANK below, as in clust.hip
+//                                                      (length descending, key order ascending) — the LENGTH RANK below (lengthRank, clust_shared.hpp)
 //   clustering/ClusteringAlgorithms.cpp:345-351        an entry without lines counts 1 ...
 //   clustering/AlignmentSymmetry.cpp:45-47             ... and is read as the list of the sequence itself
 //   clustering/AlignmentSymmetry.cpp:123-165           findMissingLinks: for every line (set, element) — a line listed twice is taken twice — whose
@@ -28,7 +28,7 @@
 //
 // Kernel design: everything is a lane per LINE over flat arrays, so a hub with thousands of lines is thousands of lanes like any other lines.
 // The accepted lines become 64-bit keys (query id << 32 | target id) and are radix-sorted once; a line's reverse is then one binary search,
-// and all later passes stream the sorted keys (8 bytes a line).  Rank: two radix sorts of n keys (length rank as clust.hip, then
+// and all later passes stream the sorted keys (8 bytes a line).  Rank: two radix sorts of n keys (lengthRank, then
 // ~size << 32 | ~length rank).  Components: parent[] holds ranks; every line hooks the larger of its two roots under the smaller with
 // atomicMin, a second kernel makes every parent a root (pointer jumping), and both repeat until no line joined two trees (one 4-byte read a
 // round).  parent[] only ever decreases, so there are no cycles, a hook that an atomicMin of another line overwrote is found again in the next
@@ -37,11 +37,10 @@
 // Algorithmic bytes: per line 16 or 64 read once (the record) + 8 written, 16 per sort pass, 8 + a binary search (log2 lines probes of 8, the
 // upper levels cached) for the reverse, and per hook round and BFS level 8 + two 4-byte rank reads + the parent / depth reads; per sequence
 // 16 per sort pass of the two rank sorts and of the pair sort, 4 per round for the jump.  Unmeasured, see DESIGN.md row C4.
-#include "common.hpp"
+#include "clust_shared.hpp"
 #include "../../include/plasship_ext/cc.h"
 #include "device_utils.hpp"
 #include "host_util.hpp"
-#include <rocprim/device/device_radix_sort.hpp>
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -51,9 +50,6 @@ namespace plasship {
 constexpr uint32_t CC_UNSET = 0xFFFFFFFFu;
 constexpr uint64_t CC_NO_LINE = ~0ull;            // a hole of a sparse alignment list: sorts behind every line (ids are below 2^32 - 1)
 
-__device__ __forceinline__ bool ccLine(const CandHit &r, uint32_t &q, uint32_t &t) { q = r.query; t = r.target; return true; }
-__device__ __forceinline__ bool ccLine(const AlnRec &r, uint32_t &q, uint32_t &t) { q = r.query; t = r.target; return r.accepted != 0; }   // (a sparse list keeps rejected pairs as holes)
-
 // stats: [0] lines, [1] lines that name an id outside the DB or lie outside their query's range, [2] missing links, [3] representatives
 template <class Rec>
 __global__ void ccLineKeyKernel(const uint64_t *__restrict__ qoff, const Rec *__restrict__ recs, uint64_t nRecs, uint32_t n, uint64_t *__restrict__ keys,
@@ -61,7 +57,7 @@ __global__ void ccLineKeyKernel(const uint64_t *__restrict__ qoff, const Rec *__
     int good = 0, bad = 0;
     for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < nRecs; i += (uint64_t) gridDim.x * blockDim.x) {
         uint32_t q, t; uint64_t key = CC_NO_LINE;
-        if (ccLine(recs[i], q, t)) {
+        if (lineOf(recs[i], q, t)) {
             if (q >= n || t >= n || i < qoff[q] || i >= qoff[q + 1]) bad++;      // (checked before anything is indexed with them)
             else { key = ((uint64_t) q << 32) | t; atomicAdd(&lines[q], 1u); good++; }
         }
@@ -86,9 +82,6 @@ __global__ void ccMissingKernel(const uint64_t *__restrict__ sorted, uint64_t nL
     if (laneId() == 0 && found) atomicAdd(&stats[2], (unsigned long long) found);
 }
 
-__global__ void ccLenKeyKernel(const uint32_t *__restrict__ len, uint64_t *__restrict__ keys, uint32_t n) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) keys[i] = ((uint64_t) ~len[i] << 32) | i;
-}
 // sortedLen[lr] names the id of length rank lr; the second key orders by (size descending, length rank descending)
 __global__ void ccSizeKeyKernel(const uint64_t *__restrict__ sortedLen, const uint32_t *__restrict__ lines, const uint32_t *__restrict__ missing,
                                 uint32_t *__restrict__ idOfLenRank, uint64_t *__restrict__ keys, uint32_t n) {
@@ -162,23 +155,11 @@ __global__ void ccPairsKernel(const uint32_t *__restrict__ parent, const uint32_
     if (laneId() == 0 && reps) atomicAdd(&stats[3], (unsigned long long) reps);
 }
 
-static unsigned ccGrid(uint64_t n, const plasship_ctx *ctx) { return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->numCU * 32)); }
-
-static int ccSort(plasship_ctx *ctx, uint64_t *in, uint64_t *out, uint64_t n, const char *what) {
-    size_t tmpBytes = 0;
-    PH_CHECK(rocprim::radix_sort_keys(nullptr, tmpBytes, in, out, (unsigned int) n, 0, 64, ctx->stream));
-    DevBuf tmp;
-    if (tmp.alloc(std::max<size_t>(tmpBytes, 8)) != hipSuccess) { setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    PH_CHECK(rocprim::radix_sort_keys(tmp.p, tmpBytes, in, out, (unsigned int) n, 0, 64, ctx->stream));
-    PH_CHECK(plasship::streamSync(ctx->stream));          // (tmp is released with this function)
-    return PLASSHIP_OK;
-}
-
 template <class Rec>
 static int clustConnected(plasship_ctx *ctx, const plasship_seqdb *db, const uint64_t *dQoff, const Rec *dRecs, uint64_t nRecs, int maxIterations, plasship_clusters **out,
                           plasship_cc_stats *stats, const char *what) {
     PH_ENTER(ctx);
-    if (db->n >= 0xFFFFFFFFull) { setError(std::string(what) + ": ids are 32-bit"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseWideIds(what, db)) return rc;
     if (nRecs >= 0x80000000ull) { setError(std::string(what) + ": list sizes are 32-bit (2^31 lines or more)"); return PLASSHIP_ERR_UNSUPPORTED; }
     const uint32_t n = (uint32_t) db->n;
     const uint64_t n1 = std::max<uint32_t>(n, 1), r1 = std::max<uint64_t>(nRecs, 1);
@@ -200,26 +181,25 @@ static int clustConnected(plasship_ctx *ctx, const plasship_seqdb *db, const uin
     PH_CHECK(hipMemsetAsync(dMissing.p, 0, n1 * 4, ctx->stream));
     PH_CHECK(hipEventRecord(ctx->ev[0], ctx->stream));
     if (n) {
-        const unsigned g = ccGrid(n, ctx);
+        const unsigned g = flatGrid(n, ctx->numCU);
         uint64_t nLines = 0;
         const uint64_t *lines = dLines.as<uint64_t>();
         // the lines as sorted keys, and how many each sequence lists
         if (nRecs) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(ccLineKeyKernel<Rec>), dim3(ccGrid(nRecs, ctx)), dim3(256), 0, ctx->stream, dQoff, dRecs, nRecs, n, dLineKeys.as<uint64_t>(),
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(ccLineKeyKernel<Rec>), dim3(flatGrid(nRecs, ctx->numCU)), dim3(256), 0, ctx->stream, dQoff, dRecs, nRecs, n, dLineKeys.as<uint64_t>(),
                                dCount.as<uint32_t>(), dStats.as<unsigned long long>());
-            { const int rc = ccSort(ctx, dLineKeys.as<uint64_t>(), dLines.as<uint64_t>(), nRecs, what); if (rc) return rc; }
+            if (const int rc = sortKeysU64(ctx, what, dLineKeys.as<uint64_t>(), dLines.as<uint64_t>(), nRecs)) return rc;
             PH_COPY_SYNC(ctx->stream, hs, dStats.p, 32, hipMemcpyDeviceToHost);
             if (hs[1]) { setError(std::string(what) + ": the list names sequences that are not in the DB"); return PLASSHIP_ERR_ARG; }
             nLines = hs[0];                               // (the holes sorted behind them)
         }
-        const unsigned gl = ccGrid(nLines, ctx);
+        const unsigned gl = flatGrid(nLines, ctx->numCU);
         if (nLines) hipLaunchKernelGGL(ccMissingKernel, dim3(gl), dim3(256), 0, ctx->stream, lines, nLines, dMissing.as<uint32_t>(), dStats.as<unsigned long long>());
         // the rank: position in the order (symmetric list size descending, length rank descending)
-        hipLaunchKernelGGL(ccLenKeyKernel, dim3(g), dim3(256), 0, ctx->stream, db->d_len.as<uint32_t>(), dKeys.as<uint64_t>(), n);
-        { const int rc = ccSort(ctx, dKeys.as<uint64_t>(), dSorted.as<uint64_t>(), n, what); if (rc) return rc; }
+        if (const int rc = lengthRank(ctx, what, db, dKeys.as<uint64_t>(), dSorted.as<uint64_t>())) return rc;
         hipLaunchKernelGGL(ccSizeKeyKernel, dim3(g), dim3(256), 0, ctx->stream, dSorted.as<uint64_t>(), dCount.as<uint32_t>(), dMissing.as<uint32_t>(), dIdOfLenRank.as<uint32_t>(),
                            dKeys.as<uint64_t>(), n);
-        { const int rc = ccSort(ctx, dKeys.as<uint64_t>(), dSorted.as<uint64_t>(), n, what); if (rc) return rc; }
+        if (const int rc = sortKeysU64(ctx, what, dKeys.as<uint64_t>(), dSorted.as<uint64_t>(), n)) return rc;
         hipLaunchKernelGGL(ccRankScatterKernel, dim3(g), dim3(256), 0, ctx->stream, dSorted.as<uint64_t>(), dIdOfLenRank.as<uint32_t>(), dRank.as<uint32_t>(), dIdOfRank.as<uint32_t>(),
                            dParent.as<uint32_t>(), n);
         // the components: hook and jump until no line joined two trees
@@ -247,7 +227,7 @@ static int clustConnected(plasship_ctx *ctx, const plasship_seqdb *db, const uin
         }
         hipLaunchKernelGGL(ccPairsKernel, dim3(g), dim3(256), 0, ctx->stream, dParent.as<uint32_t>(), dRank.as<uint32_t>(), dIdOfRank.as<uint32_t>(), cl->d_repOf.as<uint32_t>(),
                            dPairs.as<uint64_t>(), n, dStats.as<unsigned long long>());
-        { const int rc = ccSort(ctx, dPairs.as<uint64_t>(), cl->d_pairs.as<uint64_t>(), n, what); if (rc) return rc; }
+        if (const int rc = sortKeysU64(ctx, what, dPairs.as<uint64_t>(), cl->d_pairs.as<uint64_t>(), n)) return rc;
     }
     PH_CHECK(hipEventRecord(ctx->ev[1], ctx->stream));
     PH_CHECK(hipMemcpyAsync(hs, dStats.p, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -266,7 +246,7 @@ static int clustConnected(plasship_ctx *ctx, const plasship_seqdb *db, const uin
 using namespace plasship;
 
 static int ccArgs(const plasship_ctx *ctx, int maxIterations, const char *what) {
-    if (ctx->hasComm && ctx->comm.world > 1) { setError(std::string(what) + ": not part of a sharded run (a communicator of more than one rank is set)"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseSharded(ctx, what)) return rc;
     // mm/commons/Parameters.cpp:91: --max-iterations matches ^[1-9]{1}[0-9]*$
     if (maxIterations < 1) { setError(std::string(what) + ": max_iterations must be at least 1"); return PLASSHIP_ERR_ARG; }
     return PLASSHIP_OK;
@@ -277,8 +257,7 @@ extern "C" int plasship_clust_connected_cands(plasship_ctx *ctx, const plasship_
     const char *what = "plasship_clust_connected_cands";
     if (!ctx || !db || !c || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
     if (const int rc = ccArgs(ctx, max_iterations, what)) return rc;
-    // ClusteringAlgorithms.cpp:20-23: "Sequence db size != result db size"
-    if (c->nQueries != db->n) { setError(std::string(what) + ": the candidate list has another number of queries than the DB has sequences"); return PLASSHIP_ERR_ARG; }
+    if (const int rc = checkListOnDb(what, db, c)) return rc;
     return clustConnected<CandHit>(ctx, db, c->d_qoff.as<uint64_t>(), c->d_hits.as<CandHit>(), c->nHits, max_iterations, out, stats, what);
 }
 
@@ -287,7 +266,6 @@ extern "C" int plasship_clust_connected_alns(plasship_ctx *ctx, const plasship_s
     const char *what = "plasship_clust_connected_alns";
     if (!ctx || !db || !a || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
     if (const int rc = ccArgs(ctx, max_iterations, what)) return rc;
-    if (a->nQueries != db->n) { setError(std::string(what) + ": the alignment list has another number of queries than the DB has sequences"); return PLASSHIP_ERR_ARG; }
-    if (a->qdb != db || a->tdb != db) { setError(std::string(what) + ": the alignment list was built on another DB"); return PLASSHIP_ERR_ARG; }
+    if (const int rc = checkListOnDb(what, db, a)) return rc;
     return clustConnected<AlnRec>(ctx, db, a->d_qoff.as<uint64_t>(), a->d_recs.as<AlnRec>(), a->nSlots, max_iterations, out, stats, what);
 }

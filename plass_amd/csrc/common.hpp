@@ -1,6 +1,7 @@
 // plasship internal declarations (product code; never includes anything from oracle/).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstddef>
 #include <cstdio>
@@ -235,14 +236,21 @@ struct plasship_cands {
     std::vector<uint8_t> h_present;
 };
 
-// greedy clustering (clust.hip): every sequence of the DB with its representative
-struct plasship_clusters {
+// every sequence of a DB with its representative, as the cluster DB lists them: what the clustering family's handles share (clust_shared.hpp)
+namespace plasship {
+struct PairList {
     size_t n = 0;                  // == DB size
     uint64_t nClusters = 0;
     uint64_t dbGen = 0;            // plasship_seqdb::gen of the DB it was made on
-    plasship::DevBuf d_pairs;      // uint64 [n]: representative id << 32 | member id, ascending (ids are ranks in key order: the keys' order)
+    DevBuf d_pairs;                // uint64 [n]: representative id << 32 | member id (ids are ranks in key order: the keys' order)
+};
+}
+// a clustering (clust.hip, clust_cc.hip, plasship_clusters_read): the pairs ascending
+struct plasship_clusters : plasship::PairList {
     plasship::DevBuf d_repOf;      // uint32 [n]: the representative's id of every id
 };
+// what plasship_clusters_merge makes (include/plasship_ext/linclust.h): the pairs in the order of the merged DB
+struct plasship_merged : plasship::PairList {};
 
 struct plasship_alns {
     size_t nQueries = 0;
@@ -276,6 +284,22 @@ struct plasship_alns {
 };
 
 namespace plasship {
+// ---- what the single-GPU modules refuse, in the words every one of them uses; what: the public call the text names ----
+inline int refuseSharded(const plasship_ctx *ctx, const char *what) {
+    if (ctx->hasComm && ctx->comm.world > 1) { setError(std::string(what) + ": not part of a sharded run (a communicator of more than one rank is set)"); return PLASSHIP_ERR_UNSUPPORTED; }
+    return PLASSHIP_OK;
+}
+inline int refuseForeign(const char *what, const PairList *list, const plasship_seqdb *db) {
+    if (list->n != db->n || list->dbGen != db->gen) { setError(std::string(what) + ": the clustering does not belong to this DB"); return PLASSHIP_ERR_ARG; }
+    return PLASSHIP_OK;
+}
+inline int refuseWideIds(const char *what, const plasship_seqdb *db) {
+    if (db->n >= 0xFFFFFFFFull) { setError(std::string(what) + ": ids are 32-bit"); return PLASSHIP_ERR_UNSUPPORTED; }
+    return PLASSHIP_OK;
+}
+// the grid of a flat grid-stride kernel of 256 threads over n items: enough workgroups for n, at most 32 per CU, at least one
+inline unsigned flatGrid(uint64_t n, int numCU) { return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) numCU * 32)); }
+
 // ---- sharded operation (comm.hip): thin wrappers over the caller's collectives; all of them synchronise the stream first ----
 inline const plasship_comm *commOf(const plasship_ctx *ctx) { return ctx->hasComm ? &ctx->comm : nullptr; }
 // first id owned by rank r of `world` when n ids are split into contiguous ranges: ceil(r*n/world)

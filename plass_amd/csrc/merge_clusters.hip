@@ -14,14 +14,13 @@
 //            + [x's place in r's list: r first, the others ascending]
 // Both clusterings are sorted pair arrays (representative id << 32 | member id; ids are ranks in key order), so the first term and the
 // second are differences of ONE exclusive scan of the first-step cluster sizes taken in the second clustering's pair order, and the third
-// is x's index in its segment.  Three flat kernels and a scan; the text is laid out by a scan of the per-line byte counts, as clust.hip does.
+// is x's index in its segment.  Three flat kernels and a scan; the merged DB is written by the family's one writer (pairListWrite, clust_shared.hpp).
 // Every index is bounds-checked against n before it is used: a clustering that names an id outside the DB ends with an error.
 // Algorithmic bytes: 8 (pair) + ~28 (the per-id arrays) read and 8 written per sequence, twice 12 for the scans; unmeasured, see DESIGN.md.
-#include "common.hpp"
+#include "clust_shared.hpp"
 #include "../../include/plasship_ext/linclust.h"
 #include "device_utils.hpp"
 #include "host_util.hpp"
-#include "merged.hpp"
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -67,43 +66,17 @@ __global__ void mergePlaceKernel(const uint64_t *__restrict__ p1, uint32_t n, co
     }
 }
 
-__device__ __forceinline__ uint32_t keyDigits(uint32_t v) { uint32_t d = 1; while (v >= 10u) { v /= 10u; d++; } return d; }
-__global__ void mergeTextLenKernel(const uint64_t *__restrict__ pairs, const uint32_t *__restrict__ keys, uint64_t n, uint32_t *__restrict__ bytes, uint32_t *__restrict__ heads) {
-    for (uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t) gridDim.x * blockDim.x) {
-        const uint32_t rep = (uint32_t) (pairs[j] >> 32);
-        const bool head = j == 0 || (uint32_t) (pairs[j - 1] >> 32) != rep, tail = j + 1 == n || (uint32_t) (pairs[j + 1] >> 32) != rep;
-        bytes[j] = keyDigits(keys[(uint32_t) pairs[j]]) + 1u + (tail ? 1u : 0u);
-        heads[j] = head ? 1u : 0u;
-    }
-}
-__global__ void mergeTextWriteKernel(const uint64_t *__restrict__ pairs, const uint32_t *__restrict__ keys, uint64_t n, const uint64_t *__restrict__ pos,
-                                     const uint64_t *__restrict__ entryOf, char *__restrict__ text, uint64_t *__restrict__ entryOff, uint32_t *__restrict__ entryKey) {
-    for (uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t) gridDim.x * blockDim.x) {
-        const uint32_t rep = (uint32_t) (pairs[j] >> 32);
-        const bool head = j == 0 || (uint32_t) (pairs[j - 1] >> 32) != rep, tail = j + 1 == n || (uint32_t) (pairs[j + 1] >> 32) != rep;
-        char *p = text + pos[j];                          // (pos[j + 1] - pos[j] bytes are this line's: mergeTextLenKernel counted what is written here)
-        if (head) { entryOff[entryOf[j]] = pos[j]; entryKey[entryOf[j]] = keys[rep]; }
-        uint32_t v = keys[(uint32_t) pairs[j]];
-        const uint32_t d = keyDigits(v);
-        for (uint32_t k = d; k > 0; k--) { p[k - 1] = (char) ('0' + v % 10u); v /= 10u; }
-        p[d] = '\n';
-        if (tail) p[d + 1] = '\0';
-    }
-}
-
-static unsigned mergeGrid(uint64_t n, const plasship_ctx *ctx) { return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->numCU * 32)); }
-
 }  // namespace plasship
 using namespace plasship;
 
 extern "C" int plasship_clusters_merge(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_clusters *first, const plasship_clusters *second, plasship_merged **out) {
     const char *what = "plasship_clusters_merge";
     if (!ctx || !db || !first || !second || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (ctx->hasComm && ctx->comm.world > 1) { setError(std::string(what) + ": not part of a sharded run (a communicator of more than one rank is set)"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseSharded(ctx, what)) return rc;
     if (first->n != db->n || first->dbGen != db->gen || second->n != db->n || second->dbGen != db->gen) {
         setError(std::string(what) + ": a clustering does not belong to this DB (a clustering of a subset DB comes in through plasship_clusters_read, by key)"); return PLASSHIP_ERR_ARG;
     }
-    if (db->n >= 0xFFFFFFFFull) { setError(std::string(what) + ": ids are 32-bit"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseWideIds(what, db)) return rc;
     PH_ENTER(ctx);
     const uint32_t n = (uint32_t) db->n;
     std::unique_ptr<plasship_merged> holder(new plasship_merged());     // released to the caller on success only
@@ -123,7 +96,7 @@ extern "C" int plasship_clusters_merge(plasship_ctx *ctx, const plasship_seqdb *
     PH_CHECK(hipMemsetAsync(dStart2.p, 0xFF, (size_t) n * 4, ctx->stream));      // (no segment: caught by the bounds check)
     PH_CHECK(hipMemsetAsync(dPos2.p, 0xFF, (size_t) n * 4, ctx->stream));
     PH_CHECK(hipMemsetAsync(m->d_pairs.p, 0xFF, (size_t) n * 8, ctx->stream));   // (a place nobody takes stays recognisable)
-    const unsigned g = mergeGrid(n, ctx);
+    const unsigned g = flatGrid(n, ctx->numCU);
     unsigned long long *bad = dBad.as<unsigned long long>();
     hipLaunchKernelGGL(mergeSegKernel, dim3(g), dim3(256), 0, ctx->stream, first->d_pairs.as<uint64_t>(), n, dStart1.as<uint32_t>(), dEnd1.as<uint32_t>(), bad);
     hipLaunchKernelGGL(mergeSizeKernel, dim3(g), dim3(256), 0, ctx->stream, second->d_pairs.as<uint64_t>(), n, first->d_repOf.as<uint32_t>(), dStart1.as<uint32_t>(), dEnd1.as<uint32_t>(),
@@ -149,10 +122,7 @@ extern "C" int plasship_clusters_merge(plasship_ctx *ctx, const plasship_seqdb *
 }
 
 extern "C" int plasship_merged_count(const plasship_merged *m, uint64_t *n_members, uint64_t *n_clusters) {
-    if (!m) { setError("plasship_merged_count: NULL"); return PLASSHIP_ERR_ARG; }
-    if (n_members) *n_members = m->n;
-    if (n_clusters) *n_clusters = m->nClusters;
-    return PLASSHIP_OK;
+    return pairListCount("plasship_merged_count", m, n_members, n_clusters);
 }
 
 extern "C" void plasship_merged_free(plasship_ctx *ctx, plasship_merged *m) {
@@ -162,67 +132,11 @@ extern "C" void plasship_merged_free(plasship_ctx *ctx, plasship_merged *m) {
 }
 
 extern "C" int plasship_merged_download(plasship_ctx *ctx, const plasship_merged *m, const plasship_seqdb *db, uint32_t *rep_key, uint32_t *member_key) {
-    const char *what = "plasship_merged_download";
-    if (!ctx || !m || !db) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (m->n != db->n || m->dbGen != db->gen) { setError(std::string(what) + ": the clustering does not belong to this DB"); return PLASSHIP_ERR_ARG; }
-    PH_ENTER(ctx);
-    std::vector<uint32_t> keys(m->n); std::vector<uint64_t> pairs(m->n);
-    PH_CHECK(plasship::streamSync(ctx->stream));
-    if (m->n) {
-        int rc = stagedCopyToHost(ctx, keys.data(), db->d_key.p, m->n * 4); if (rc) return rc;
-        rc = stagedCopyToHost(ctx, pairs.data(), m->d_pairs.p, m->n * 8); if (rc) return rc;
-    }
-    for (size_t j = 0; j < m->n; j++) {
-        if (rep_key) rep_key[j] = keys[(size_t) (pairs[j] >> 32)];
-        if (member_key) member_key[j] = keys[(size_t) (uint32_t) pairs[j]];
-    }
-    return PLASSHIP_OK;
+    return pairListDownload(ctx, "plasship_merged_download", m, db, rep_key, member_key);
 }
 
 extern "C" int plasship_merged_write(plasship_ctx *ctx, const plasship_merged *m, const plasship_seqdb *db, const char *db_path) {
-    const char *what = "plasship_merged_write";
-    if (!ctx || !m || !db || !db_path) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (m->n != db->n || m->dbGen != db->gen) { setError(std::string(what) + ": the clustering does not belong to this DB"); return PLASSHIP_ERR_ARG; }
-    PH_ENTER(ctx);
-    const uint64_t n = m->n, nC = m->nClusters;
-    std::vector<uint64_t> entryOff(nC + 1, 0); std::vector<uint32_t> entryKey(nC), elen(nC);
-    uint64_t total = 0;
-    DevBuf dBytes, dHeads, dPos, dEntryOf, dTmp, dText, dEntryOff, dEntryKey;
-    if (n) {
-        const size_t tmpBytes = exclusiveScanTmpBytes(n);
-        if (dBytes.alloc(n * 4) != hipSuccess || dHeads.alloc(n * 4) != hipSuccess || dPos.alloc((n + 1) * 8) != hipSuccess || dEntryOf.alloc((n + 1) * 8) != hipSuccess ||
-            dTmp.alloc(tmpBytes) != hipSuccess || dEntryOff.alloc(std::max<uint64_t>(nC, 1) * 8) != hipSuccess || dEntryKey.alloc(std::max<uint64_t>(nC, 1) * 4) != hipSuccess) {
-            setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE;
-        }
-        const unsigned g = mergeGrid(n, ctx);
-        hipLaunchKernelGGL(mergeTextLenKernel, dim3(g), dim3(256), 0, ctx->stream, m->d_pairs.as<uint64_t>(), db->d_key.as<uint32_t>(), n, dBytes.as<uint32_t>(), dHeads.as<uint32_t>());
-        if (exclusiveScanU32(ctx->stream, dBytes.as<uint32_t>(), dPos.as<uint64_t>(), n, dTmp.p, tmpBytes) ||
-            exclusiveScanU32(ctx->stream, dHeads.as<uint32_t>(), dEntryOf.as<uint64_t>(), n, dTmp.p, tmpBytes)) { (void) plasship::streamSync(ctx->stream); setError(std::string(what) + ": scan failed"); return PLASSHIP_ERR_DEVICE; }
-        uint64_t ends[2] = {0, 0};
-        PH_CHECK(hipMemcpyAsync(&ends[0], dPos.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        PH_CHECK(hipMemcpyAsync(&ends[1], dEntryOf.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-        PH_CHECK(plasship::streamSync(ctx->stream));
-        total = ends[0];
-        if (ends[1] != nC) { setError(std::string(what) + ": internal error: the number of entries differs from the number of clusters"); return PLASSHIP_ERR_DEVICE; }
-        if (dText.alloc(std::max<uint64_t>(total, 1)) != hipSuccess) { setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
-        hipLaunchKernelGGL(mergeTextWriteKernel, dim3(g), dim3(256), 0, ctx->stream, m->d_pairs.as<uint64_t>(), db->d_key.as<uint32_t>(), n, dPos.as<uint64_t>(),
-                           dEntryOf.as<uint64_t>(), dText.as<char>(), dEntryOff.as<uint64_t>(), dEntryKey.as<uint32_t>());
-        PH_CHECK(plasship::streamSync(ctx->stream));
-        PH_CHECK(hipGetLastError());
-        int rc = stagedCopyToHost(ctx, entryOff.data(), dEntryOff.p, nC * 8); if (rc) return rc;
-        rc = stagedCopyToHost(ctx, entryKey.data(), dEntryKey.p, nC * 4); if (rc) return rc;
-    }
-    entryOff[nC] = total;
-    for (uint64_t c = 0; c < nC; c++) elen[c] = (uint32_t) (entryOff[c + 1] - entryOff[c]);
-    DBFileWriter w; std::string err;
-    if (!w.open(db_path, PLASSHIP_DBTYPE_CLUSTER_RES, err)) { setError(err); return PLASSHIP_ERR_IO; }
-    if (total) {
-        const int rc = stagedDownload(ctx, dText.p, total, [&](const char *src, uint64_t, uint64_t bytes) { w.data(src, bytes); return !w.failed.load(); });
-        if (rc) { setError(std::string(what) + ": writing " + db_path + " failed"); return rc; }
-    }
-    w.index(entryKey.data(), elen.data(), nC);
-    if (!w.close(err)) { setError(err); return PLASSHIP_ERR_IO; }
-    return PLASSHIP_OK;
+    return pairListWrite(ctx, "plasship_merged_write", m, db, db_path, false);
 }
 
 // A cluster DB (dbtype 6) from disk as a clustering of `db`, BY KEY: an entry's key is the representative, its lines are the members.  A
@@ -231,7 +145,7 @@ extern "C" int plasship_merged_write(plasship_ctx *ctx, const plasship_merged *m
 extern "C" int plasship_clusters_read(plasship_ctx *ctx, const plasship_seqdb *db, const char *db_path, plasship_clusters **out) {
     const char *what = "plasship_clusters_read";
     if (!ctx || !db || !db_path || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (db->n >= 0xFFFFFFFFull) { setError(std::string(what) + ": ids are 32-bit"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseWideIds(what, db)) return rc;
     PH_ENTER(ctx);
     HostDB h; std::string err;
     if (!readDBFiles(db_path, h, err)) { setError(err); return PLASSHIP_ERR_IO; }

@@ -331,8 +331,6 @@ __global__ void maxLenKernel(const uint32_t *__restrict__ v, uint32_t n, uint32_
     if (laneId() == 0 && m) atomicMax(out, m);
 }
 
-static unsigned gridOf(uint64_t n, int numCU) { return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) numCU * 32)); }
-
 // finishes a device-built sequence DB: host-side totals that the handle carries
 static int finishSeqdb(plasship_ctx *ctx, plasship_seqdb *o, size_t n, uint64_t dataBytes, int dbtype, const uint32_t *dLen) {
     o->dbtype = dbtype; o->n = n; o->dataBytes = dataBytes; o->residues = dataBytes - 2 * (uint64_t) n; o->hostIndexValid = false;
@@ -340,7 +338,7 @@ static int finishSeqdb(plasship_ctx *ctx, plasship_seqdb *o, size_t n, uint64_t 
     DevBuf dMax; uint32_t mx = 0;
     if (dMax.alloc(4) != hipSuccess) { setError("out of device memory"); return PLASSHIP_ERR_DEVICE; }
     PH_CHECK(hipMemsetAsync(dMax.p, 0, 4, ctx->stream));
-    if (n) hipLaunchKernelGGL(maxLenKernel, dim3(gridOf(n, ctx->numCU)), dim3(256), 0, ctx->stream, dLen, (uint32_t) n, dMax.as<uint32_t>());
+    if (n) hipLaunchKernelGGL(maxLenKernel, dim3(flatGrid(n, ctx->numCU)), dim3(256), 0, ctx->stream, dLen, (uint32_t) n, dMax.as<uint32_t>());
     PH_COPY_SYNC(ctx->stream, &mx, dMax.p, 4, hipMemcpyDeviceToHost);
     o->maxEntryLen = n ? mx + 2 : 0;
     return PLASSHIP_OK;
@@ -386,7 +384,7 @@ extern "C" int plasship_extract_orfs(plasship_ctx *ctx, const plasship_seqdb *re
     a.translate = par->translate ? 1 : 0; a.maxSeqLen = par->max_seq_len;
     a.cnt = dCnt.as<uint32_t>(); a.bytes = dBytes.as<uint32_t>();
     PH_CHECK(hipEventRecord(ctx->ev[0], st));
-    const unsigned grid = gridOf(nSlots, ctx->numCU);
+    const unsigned grid = flatGrid(nSlots, ctx->numCU);
     if (nSlots) hipLaunchKernelGGL((orfKernel<0>), dim3(grid), dim3(256), 0, st, a);
     if (exclusiveScanU32(st, dCnt.as<uint32_t>(), dOrfBase.as<uint64_t>(), nSlots, dTmp.p, tmpBytes) ||
         exclusiveScanU32(st, dBytes.as<uint32_t>(), dByteBase.as<uint64_t>(), nSlots, dTmp.p, tmpBytes)) { setError("plasship_extract_orfs: scan failed"); return PLASSHIP_ERR_DEVICE; }
@@ -449,7 +447,7 @@ extern "C" int plasship_translate_nucs(plasship_ctx *ctx, const plasship_seqdb *
     a.s = orfs->view(); a.key = orfs->d_key.as<uint32_t>(); a.info = hdr ? hdr->d_info.as<OrfInfo>() : nullptr;
     a.addOrfStop = par->add_orf_stop ? 1 : 0; a.maxSeqLen = par->max_seq_len; a.bytes = dBytes.as<uint32_t>();
     PH_CHECK(hipEventRecord(ctx->ev[0], st));
-    const unsigned grid = gridOf(N, ctx->numCU);
+    const unsigned grid = flatGrid(N, ctx->numCU);
     if (N) {
         hipLaunchKernelGGL((translateKernel<0>), dim3(grid), dim3(256), 0, st, a);
         hipLaunchKernelGGL(nonZeroKernel, dim3(grid), dim3(256), 0, st, dBytes.as<uint32_t>(), N, dFlag.as<uint32_t>());
@@ -510,16 +508,16 @@ extern "C" int plasship_seqdb_concat(plasship_ctx *ctx, const plasship_seqdb *a,
     if (a->dataBytes) PH_CHECK(hipMemcpyAsync(o->d_data.p, a->dataPtr(), a->dataBytes, hipMemcpyDeviceToDevice, st));
     if (b->dataBytes && !b->d_fileRank.p) PH_CHECK(hipMemcpyAsync((char *) o->d_data.p + a->dataBytes, b->dataPtr(), b->dataBytes, hipMemcpyDeviceToDevice, st));
     PH_CHECK(hipMemsetAsync((char *) o->d_data.p + dataBytes, 0, 64, st));
-    hipLaunchKernelGGL(concatIndexKernel, dim3(gridOf(nn + 1, ctx->numCU)), dim3(256), 0, st, a->d_off.as<uint64_t>(), a->d_len.as<uint32_t>(), a->d_key.as<uint32_t>(), (uint32_t) a->n,
+    hipLaunchKernelGGL(concatIndexKernel, dim3(flatGrid(nn + 1, ctx->numCU)), dim3(256), 0, st, a->d_off.as<uint64_t>(), a->d_len.as<uint32_t>(), a->d_key.as<uint32_t>(), (uint32_t) a->n,
                        b->d_off.as<uint64_t>(), b->d_len.as<uint32_t>(), (uint32_t) b->n, a->dataBytes, maxKeyA + 1, o->d_off.as<uint64_t>(), o->d_len.as<uint32_t>(), o->d_key.as<uint32_t>());
     if (b->d_fileRank.p && b->n) {
         // B was read from files whose data is not in key order: the reference numbers B's entries in FILE order (see common.hpp),
         // so the B half of the output is B permuted by its file rank (lengths scattered, offsets by a prefix sum, entries copied)
         DevBuf dBytes, dNewOff, dTmp; const size_t tmpBytes = exclusiveScanTmpBytes(b->n + 2);
         if (dBytes.alloc((b->n + 1) * 8) != hipSuccess || dNewOff.alloc((b->n + 2) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess) { setError("plasship_seqdb_concat: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-        hipLaunchKernelGGL(concatRankLenKernel, dim3(gridOf(b->n, ctx->numCU)), dim3(256), 0, st, b->d_len.as<uint32_t>(), b->d_fileRank.as<uint32_t>(), (uint32_t) b->n, o->d_len.as<uint32_t>() + a->n, dBytes.as<uint64_t>());
+        hipLaunchKernelGGL(concatRankLenKernel, dim3(flatGrid(b->n, ctx->numCU)), dim3(256), 0, st, b->d_len.as<uint32_t>(), b->d_fileRank.as<uint32_t>(), (uint32_t) b->n, o->d_len.as<uint32_t>() + a->n, dBytes.as<uint64_t>());
         if (exclusiveScanU64(st, dBytes.as<uint64_t>(), dNewOff.as<uint64_t>(), b->n, dTmp.p, tmpBytes)) { setError("plasship_seqdb_concat: scan failed"); return PLASSHIP_ERR_DEVICE; }
-        hipLaunchKernelGGL(concatRankCopyKernel, dim3(gridOf((b->n + 15) / 16, ctx->numCU)), dim3(256), 0, st, b->dataPtr(), b->d_off.as<uint64_t>(), b->d_len.as<uint32_t>(), b->d_fileRank.as<uint32_t>(), (uint32_t) b->n,
+        hipLaunchKernelGGL(concatRankCopyKernel, dim3(flatGrid((b->n + 15) / 16, ctx->numCU)), dim3(256), 0, st, b->dataPtr(), b->d_off.as<uint64_t>(), b->d_len.as<uint32_t>(), b->d_fileRank.as<uint32_t>(), (uint32_t) b->n,
                            dNewOff.as<uint64_t>(), a->dataBytes, (uint32_t) a->n, maxKeyA + 1, o->d_data.as<char>(), o->d_off.as<uint64_t>(), o->d_key.as<uint32_t>());
         PH_CHECK(plasship::streamSync(st));
     }
@@ -575,13 +573,13 @@ extern "C" int plasship_seqdb_concat_keys(plasship_ctx *ctx, const plasship_seqd
     PH_CHECK(hipMemsetAsync(dDup.p, 0, 4, st));
     PH_CHECK(hipMemsetAsync((char *) o->d_data.p + dataBytes, 0, 64, st));
     if (nn) {
-        hipLaunchKernelGGL(mergeRankKernel, dim3(gridOf(nn, ctx->numCU)), dim3(256), 0, st, a->d_key.as<uint32_t>(), a->d_len.as<uint32_t>(), (uint32_t) a->n, b->d_key.as<uint32_t>(), b->d_len.as<uint32_t>(), (uint32_t) b->n,
+        hipLaunchKernelGGL(mergeRankKernel, dim3(flatGrid(nn, ctx->numCU)), dim3(256), 0, st, a->d_key.as<uint32_t>(), a->d_len.as<uint32_t>(), (uint32_t) a->n, b->d_key.as<uint32_t>(), b->d_len.as<uint32_t>(), (uint32_t) b->n,
                            dRankA.as<uint32_t>(), dRankB.as<uint32_t>(), o->d_len.as<uint32_t>(), o->d_key.as<uint32_t>(), dBytes.as<uint64_t>(), dDup.as<uint32_t>());
         if (exclusiveScanU64(st, dBytes.as<uint64_t>(), o->d_off.as<uint64_t>(), nn, dTmp.p, tmpBytes)) { setError("plasship_seqdb_concat_keys: scan failed"); return PLASSHIP_ERR_DEVICE; }
         // (the scan leaves its total at [nn]: o->d_off is the finished index)
-        if (a->n) hipLaunchKernelGGL(mergeCopyKernel, dim3(gridOf((a->n + 15) / 16, ctx->numCU)), dim3(256), 0, st, a->dataPtr(), a->d_off.as<uint64_t>(), a->d_len.as<uint32_t>(), (const uint32_t *) dRankA.as<uint32_t>(), (uint32_t) a->n,
+        if (a->n) hipLaunchKernelGGL(mergeCopyKernel, dim3(flatGrid((a->n + 15) / 16, ctx->numCU)), dim3(256), 0, st, a->dataPtr(), a->d_off.as<uint64_t>(), a->d_len.as<uint32_t>(), (const uint32_t *) dRankA.as<uint32_t>(), (uint32_t) a->n,
                                      (const uint64_t *) o->d_off.as<uint64_t>(), o->d_data.as<char>());
-        if (b->n) hipLaunchKernelGGL(mergeCopyKernel, dim3(gridOf((b->n + 15) / 16, ctx->numCU)), dim3(256), 0, st, b->dataPtr(), b->d_off.as<uint64_t>(), b->d_len.as<uint32_t>(), (const uint32_t *) dRankB.as<uint32_t>(), (uint32_t) b->n,
+        if (b->n) hipLaunchKernelGGL(mergeCopyKernel, dim3(flatGrid((b->n + 15) / 16, ctx->numCU)), dim3(256), 0, st, b->dataPtr(), b->d_off.as<uint64_t>(), b->d_len.as<uint32_t>(), (const uint32_t *) dRankB.as<uint32_t>(), (uint32_t) b->n,
                                      (const uint64_t *) o->d_off.as<uint64_t>(), o->d_data.as<char>());
     } else PH_CHECK(hipMemsetAsync(o->d_off.p, 0, 8, st));
     uint32_t dup = 0;
@@ -602,7 +600,7 @@ extern "C" int plasship_orfhdr_concat(plasship_ctx *ctx, const plasship_orfhdr *
     const uint64_t nn = (uint64_t) a->n + b->n;
     std::unique_ptr<plasship_orfhdr> o(new plasship_orfhdr());
     if (o->d_info.alloc((nn + 1) * sizeof(OrfInfo)) != hipSuccess) { setError("plasship_orfhdr_concat: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    if (nn) hipLaunchKernelGGL(concatInfoKernel, dim3(gridOf(nn, ctx->numCU)), dim3(256), 0, st, a->d_info.as<OrfInfo>(), (uint32_t) a->n, b->d_info.as<OrfInfo>(), (uint32_t) b->n, (const uint32_t *) b->d_fileRank.as<uint32_t>(), maxKeyA + 1, o->d_info.as<OrfInfo>());
+    if (nn) hipLaunchKernelGGL(concatInfoKernel, dim3(flatGrid(nn, ctx->numCU)), dim3(256), 0, st, a->d_info.as<OrfInfo>(), (uint32_t) a->n, b->d_info.as<OrfInfo>(), (uint32_t) b->n, (const uint32_t *) b->d_fileRank.as<uint32_t>(), maxKeyA + 1, o->d_info.as<OrfInfo>());
     o->n = (size_t) nn; o->nUnparsable = a->nUnparsable + b->nUnparsable;
     PH_CHECK(plasship::streamSync(st));
     PH_CHECK(hipGetLastError());

@@ -4,7 +4,7 @@
 //
 // Reference behaviour reproduced (lib/mmseqs/src/util/result2repseq.cpp:37-49): for every entry of the cluster DB the sequence of the FIRST key
 // on its list, stored under the entry's key; an empty entry gives no output entry; the output has the sequence DB's type.  Clustering::writeData
-// and mergeclusters put a cluster's own key first (clust.hip, merge_clusters.hip), so the first key is the entry's key: the output is the
+// and mergeclusters put a cluster's own key first (pairListWrite in clust.hip, the places of merge_clusters.hip), so the first key is the entry's key: the output is the
 // subset of the representatives, which a clustering names by repOf[id] == id and a merged clustering by the representatives of its pairs.
 // Three flat kernels and two scans: mark, place (index and byte offset are exclusive scans of the marks and of the marked entry lengths),
 // copy (one wavefront per entry, 16 bytes per lane and step from wherever the source entry lies; the tail byte by byte — no load leaves
@@ -14,7 +14,6 @@
 #include "../../include/plasship_ext/subst.h"
 #include "device_utils.hpp"
 #include "host_util.hpp"
-#include "merged.hpp"
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -55,8 +54,6 @@ __global__ __launch_bounds__(256) void repGatherKernel(SeqView db, const uint32_
     }
 }
 
-static unsigned repGrid(uint64_t n, const plasship_ctx *ctx) { return (unsigned) std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t) ctx->numCU * 32)); }
-
 // the marked entries of `db` as a DB of their own; dMark: uint32 [n]
 static int gatherMarked(plasship_ctx *ctx, const char *what, const plasship_seqdb *db, const uint32_t *dMark, plasship_seqdb **out) {
     const uint32_t n = (uint32_t) db->n;
@@ -67,7 +64,7 @@ static int gatherMarked(plasship_ctx *ctx, const char *what, const plasship_seqd
     PH_CHECK(hipMemsetAsync(dBad.p, 0, 8, ctx->stream));
     uint64_t ends[2] = {0, 0};
     if (n) {
-        hipLaunchKernelGGL(repBytesKernel, dim3(repGrid(n, ctx)), dim3(256), 0, ctx->stream, dMark, db->d_len.as<uint32_t>(), n, dBytes.as<uint32_t>());
+        hipLaunchKernelGGL(repBytesKernel, dim3(flatGrid(n, ctx->numCU)), dim3(256), 0, ctx->stream, dMark, db->d_len.as<uint32_t>(), n, dBytes.as<uint32_t>());
         if (exclusiveScanU32(ctx->stream, dMark, dPlace.as<uint64_t>(), n, dTmp.p, tmpBytes) ||
             exclusiveScanU32(ctx->stream, dBytes.as<uint32_t>(), dPos.as<uint64_t>(), n, dTmp.p, tmpBytes)) { (void) plasship::streamSync(ctx->stream); setError(std::string(what) + ": scan failed"); return PLASSHIP_ERR_DEVICE; }
         PH_CHECK(hipMemcpyAsync(&ends[0], dPlace.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -106,30 +103,30 @@ using namespace plasship;
 extern "C" int plasship_clusters_repseqs(plasship_ctx *ctx, const plasship_clusters *cl, const plasship_seqdb *db, plasship_seqdb **out) {
     const char *what = "plasship_clusters_repseqs";
     if (!ctx || !cl || !db || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (ctx->hasComm && ctx->comm.world > 1) { setError(std::string(what) + ": not part of a sharded run (a communicator of more than one rank is set)"); return PLASSHIP_ERR_UNSUPPORTED; }
-    if (cl->n != db->n || cl->dbGen != db->gen) { setError(std::string(what) + ": the clustering does not belong to this DB"); return PLASSHIP_ERR_ARG; }
-    if (db->n >= 0xFFFFFFFFull) { setError(std::string(what) + ": ids are 32-bit"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseSharded(ctx, what)) return rc;
+    if (const int rc = refuseForeign(what, cl, db)) return rc;
+    if (const int rc = refuseWideIds(what, db)) return rc;
     PH_ENTER(ctx);
     const uint32_t n = (uint32_t) db->n;
     DevBuf dMark;
     if (dMark.alloc(std::max<size_t>(n, 1) * 4) != hipSuccess) { setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    if (n) hipLaunchKernelGGL(repMarkClustersKernel, dim3(repGrid(n, ctx)), dim3(256), 0, ctx->stream, cl->d_repOf.as<uint32_t>(), n, dMark.as<uint32_t>());
+    if (n) hipLaunchKernelGGL(repMarkClustersKernel, dim3(flatGrid(n, ctx->numCU)), dim3(256), 0, ctx->stream, cl->d_repOf.as<uint32_t>(), n, dMark.as<uint32_t>());
     return gatherMarked(ctx, what, db, dMark.as<uint32_t>(), out);
 }
 
 extern "C" int plasship_merged_repseqs(plasship_ctx *ctx, const plasship_merged *m, const plasship_seqdb *db, plasship_seqdb **out) {
     const char *what = "plasship_merged_repseqs";
     if (!ctx || !m || !db || !out) { setError(std::string(what) + ": bad argument"); return PLASSHIP_ERR_ARG; }
-    if (ctx->hasComm && ctx->comm.world > 1) { setError(std::string(what) + ": not part of a sharded run (a communicator of more than one rank is set)"); return PLASSHIP_ERR_UNSUPPORTED; }
-    if (m->n != db->n || m->dbGen != db->gen) { setError(std::string(what) + ": the clustering does not belong to this DB"); return PLASSHIP_ERR_ARG; }
-    if (db->n >= 0xFFFFFFFFull) { setError(std::string(what) + ": ids are 32-bit"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseSharded(ctx, what)) return rc;
+    if (const int rc = refuseForeign(what, m, db)) return rc;
+    if (const int rc = refuseWideIds(what, db)) return rc;
     PH_ENTER(ctx);
     const uint32_t n = (uint32_t) db->n;
     DevBuf dMark, dBad;
     if (dMark.alloc(std::max<size_t>(n, 1) * 4) != hipSuccess || dBad.alloc(8) != hipSuccess) { setError(std::string(what) + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
     PH_CHECK(hipMemsetAsync(dMark.p, 0, std::max<size_t>(n, 1) * 4, ctx->stream));
     PH_CHECK(hipMemsetAsync(dBad.p, 0, 8, ctx->stream));
-    if (n) hipLaunchKernelGGL(repMarkMergedKernel, dim3(repGrid(n, ctx)), dim3(256), 0, ctx->stream, m->d_pairs.as<uint64_t>(), n, dMark.as<uint32_t>(), dBad.as<unsigned long long>());
+    if (n) hipLaunchKernelGGL(repMarkMergedKernel, dim3(flatGrid(n, ctx->numCU)), dim3(256), 0, ctx->stream, m->d_pairs.as<uint64_t>(), n, dMark.as<uint32_t>(), dBad.as<unsigned long long>());
     unsigned long long hb = 0;
     PH_CHECK(hipMemcpyAsync(&hb, dBad.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     PH_CHECK(plasship::streamSync(ctx->stream));

@@ -140,7 +140,7 @@ int compactCsr(plasship_ctx *ctx, const char *what, const uint64_t *dInQoff, uin
 int RescoreList::prepare(size_t slotBytes_, bool wrapped, const double *evalThr, const plasship_clusters *subset) {
     const std::string w(what);
     slotBytes = slotBytes_;
-    if (ctx->hasComm && ctx->comm.world > 1) { setError(w + ": not part of a sharded run (a communicator of more than one rank is set)"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (const int rc = refuseSharded(ctx, what)) return rc;
     if (c->nQueries != qdb->n) { setError(w + (tdb ? ": candidate list does not belong to the query DB" : ": candidate list does not belong to the DB")); return PLASSHIP_ERR_ARG; }
     if (tdb && qdb->dbtype != tdb->dbtype) { setError(w + ": query and target DB types differ"); return PLASSHIP_ERR_ARG; }
     nucl = qdb->dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES;
@@ -151,7 +151,7 @@ int RescoreList::prepare(size_t slotBytes_, bool wrapped, const double *evalThr,
     const size_t nQ = qdb->n;
     residues = (tdb ? tdb : qdb)->residues;
     if (subset) {
-        if (subset->n != qdb->n || subset->dbGen != qdb->gen) { setError(w + ": the clustering does not belong to this DB"); return PLASSHIP_ERR_ARG; }
+        if (const int rc = refuseForeign(what, subset, qdb)) return rc;
         std::vector<uint32_t> lens(nQ), repOf(nQ);
         PH_CHECK(streamSync(ctx->stream));
         if (nQ) { int rc = stagedCopyToHost(ctx, lens.data(), qdb->d_len.p, nQ * 4); if (!rc) rc = stagedCopyToHost(ctx, repOf.data(), subset->d_repOf.p, nQ * 4); if (rc) return rc; }

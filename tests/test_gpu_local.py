@@ -188,6 +188,57 @@ def test_merge_on_hand_made_clusterings(ctx, tmp_path, case):
         h.free()
 
 
+# every decimal length of a 32-bit key and both sides of each boundary (0 and 1: the one-digit end); the fixtures' keys have at most 4 digits
+EDGE_KEYS = [0, 1] + [v for d in range(1, 10) for v in (10 ** d - 1, 10 ** d)] + [4294967295]
+# 1000 and 4294967295: the largest key of their members, so the representative's line moves to the front; 9999 and 10000000: the smallest; 0 and 1: singletons
+EDGE_FIRST = {0: [0], 1: [1], 1000: [9, 10, 99, 100, 999, 1000], 9999: [9999, 10000, 99999, 100000], 10000000: [10000000, 99999999, 100000000, 999999999, 1000000000],
+              4294967295: [999999, 1000000, 9999999, 4294967295]}
+EDGE_SECOND = {9999: [9999], 4294967295: [4294967295, 1000]}       # two first-step clusters joined under the larger key
+
+
+def _written_downloaded_counted(handle, path, keys, want):
+    """want: [(key, entry bytes)] in key order, from the restatement"""
+    handle.write(str(path))
+    assert read_db(path) == (6, {k: e + b"\0" for k, e in want})
+    assert handle.count() == (len(keys), len(want))
+    return [(int(a), int(b)) for a, b in zip(*handle.download())]
+
+
+def test_cluster_db_writers_at_every_key_length(ctx, tmp_path):
+    """the one writer behind Clusters.write (representative first) and MergedClusters.write (pair order), on keys of 1 to 10 digits"""
+    assert len(EDGE_KEYS) == 21 and sorted(k for m in EDGE_FIRST.values() for k in m) == EDGE_KEYS
+    cs.write_db(str(tmp_path / "seq"), [(k, b"ACGT" * (1 + i % 3) + b"\n") for i, k in enumerate(EDGE_KEYS)], 1)
+    f = [(r, _clu_entry(r, EDGE_FIRST[r])) for r in sorted(EDGE_FIRST)]
+    s = [(r, _clu_entry(r, EDGE_SECOND[r])) for r in sorted(EDGE_SECOND)]
+    assert dict(f)[1000] == b"1000\n9\n10\n99\n100\n999\n" and dict(f)[4294967295] == b"4294967295\n999999\n1000000\n9999999\n"
+    cs.write_db(str(tmp_path / "clu1"), f, 6); cs.write_db(str(tmp_path / "clu2"), s, 6)
+    db = ctx.read_seqdb(str(tmp_path / "seq"))
+    c1, c2 = ctx.read_clusters(db, str(tmp_path / "clu1")), ctx.read_clusters(db, str(tmp_path / "clu2"))
+    # a clustering's pairs ascend by (representative, member), the representative among its members
+    assert _written_downloaded_counted(c1, tmp_path / "out1", EDGE_KEYS, f) == [(r, k) for r in sorted(EDGE_FIRST) for k in sorted(EDGE_FIRST[r])]
+    m = ctx.merge_clusters(db, c1, c2)
+    want = lc.merge_clusters(EDGE_KEYS, f, s)
+    assert dict(want)[4294967295] == b"4294967295\n999999\n1000000\n9999999\n1000\n9\n10\n99\n100\n999\n" and 1000 not in dict(want)
+    assert _written_downloaded_counted(m, tmp_path / "merged", EDGE_KEYS, want) == [(k, int(l)) for k, e in want for l in e.split()]
+    for h in (m, c2, c1, db):
+        h.free()
+
+
+def test_cluster_db_writers_on_a_db_of_one_sequence(ctx, tmp_path):
+    """head and tail of the only entry fall on the only pair"""
+    cs.write_db(str(tmp_path / "seq"), [(0, b"ACGT\n")], 1)
+    f = [(0, _clu_entry(0, [0]))]
+    cs.write_db(str(tmp_path / "clu"), f, 6)
+    db = ctx.read_seqdb(str(tmp_path / "seq"))
+    c1, c2 = ctx.read_clusters(db, str(tmp_path / "clu")), ctx.read_clusters(db, str(tmp_path / "clu"))
+    assert _written_downloaded_counted(c1, tmp_path / "out1", [0], f) == [(0, 0)]
+    m = ctx.merge_clusters(db, c1, c2)
+    assert lc.merge_clusters([0], f, f) == f
+    assert _written_downloaded_counted(m, tmp_path / "merged", [0], f) == [(0, 0)]
+    for h in (m, c2, c1, db):
+        h.free()
+
+
 def test_merge_equals_the_reference_on_the_fixture(ctx, tmp_path):
     d = str(tmp_path / "golden")
     _, merges = cs.unpack_fixture(d)
