@@ -189,12 +189,21 @@ __global__ __launch_bounds__(GR_BLOCK) void groupKernel(GroupArgs a) {
 // BLOCK x HT: 256 threads and 2048 slots hold buckets of up to 2048 positions (~1500 distinct k-mers); the 50 M-read sets fill the
 // 2^20 buckets two partition levels can make with ~4000 positions each, which 512 threads and 4096 slots take in one go (a
 // bucket beyond the registers would be read from HBM once per phase and sub-pass).  "At least two members" is one bit per slot.
+// GL_RMAX records per thread, probed ONE AT A TIME.  Issuing a thread's first probes in batches (the GL_RMAX returning CAS of phase A back to back, the
+// home-slot reads of phase C together, one cursor atomic per batch) was built and measured at 50 M reads (profiles/group_batch_bench_ab.txt): batches of
+// 8 / 4 / 2 in phase A alone cost +1.7 / +0.5 / +0.25 ms of the group stage against no batch, and any batch in phase C needs the batch's output records beside the
+// record registers — 64 to 268 B of scratch per lane at 128 VGPRs — and cost +1.9 ms (batches of 2 and 2) to +10 ms (8 and 4) against the kernel as it was.  The kernel is not a chain of LDS round
+// trips that a thread could overlap on its own: 8 wavefronts per SIMD already do.  What did pay is fewer LDS-pipe instructions per record (-20 %
+// SQ_INSTS_LDS, -2.9 ms of the group stage): the new k-mers of a thread's registers counted with one atomic per wavefront instead of one per register, the arena
+// base broadcast with v_readfirstlane instead of a trip through the LDS crossbar, and no branch in front of a probe.
 constexpr int GL_RMAX = 8;
 constexpr uint32_t glMaxKeys(uint32_t HT) { return HT / 4 * 3; }      // distinct k-mers per sub-pass before splitting further (the host's debug replay reads it too)
 // Look-ahead (round 6): the fetch of a bucket is two dependent round trips (line list entry, then the record), and the counters say the
 // wavefronts are parked two thirds of their cycles (SQ_WAIT_ANY 65 %, LDS pipe 10 %).  A second set of record registers does not fit (126 of 128 VGPRs:
 // profiles/r06_ab_knobs.txt), but the LIST ENTRIES of the next bucket do — one load per thread at the start of a bucket, parked in LDS behind its first
 // phase — so that the record loads at the bucket's end start from LDS: one round trip on the critical path instead of two.
+// SQ_WAIT_ANY over SQ_BUSY_CYCLES did not fall when the LDS instructions did (16.3 -> 17.0 per busy cycle, profiles/group_batch_kernel_stats.txt): the parked
+// share is the barriers and the record loads, not the probes.
 template <bool NUCL, int BLOCK, uint32_t HT, int WPE>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void groupLinesKernel(GroupArgs a) {
     __shared__ uint32_t sList[GL_RMAX * BLOCK / RPL];
@@ -242,73 +251,101 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, WPE)
         auto recAt = [&](uint32_t i) -> R { return in[(uint64_t) a.list[lb + i / RPL] * RPL + (i % RPL)]; };
         const bool inRegs = n <= (uint32_t) GL_RMAX * BLOCK;
         bool fetched = false;
+        // a record's key, its place in the sub-passes and its home slot
+        auto keyOf = [&](const R &r) -> unsigned long long { return NUCL ? (r.kmer | BIT63) : r.kmer; };
+        auto inSub = [&](const R &r, uint64_t hh, uint32_t nSub, uint32_t sub) -> bool { return !isSentinel(r) && !(nSub > 1 && (uint32_t) ((hh >> 40) % nSub) != sub); };
+        // the bid of a record that found its k-mer's slot: mark a second member, and bid for the run head
+        auto bid = [&](const R &r, uint32_t slot, bool claimed) {
+            if (!claimed) atomicOr(&hMulti[slot >> 5], 1u << (slot & 31));
+            const unsigned long long packed = ((unsigned long long) (0x7FFFu - (uint32_t) r.len) << 48) | ((unsigned long long) r.id << 16) |
+                                              ((unsigned long long) ((uint32_t) r.pos & 0x7FFFu) << 1) | (NUCL ? ((r.kmer >> 63) & 1ULL) : 0ULL);
+            atomicMin(&hBest[slot], packed);
+        };
+        // a record whose CAS on `slot` returned `prev`: it bids if the slot was empty or held its k-mer, else it walks on (linear probing); true = table full
+        // (round 6: double hashing — an odd step from other bits of the hash instead of 1 — changed nothing, 38.7 -> 38.3 ms at 50 M reads: the
+        //  table is loaded to a third, probing is not where the time is; profiles/r06_ab_knobs.txt, call 3)
+        auto claimFrom = [&](const R &r, unsigned long long K, uint32_t slot, unsigned long long prev, bool &claimed) -> bool {
+            for (uint32_t probe = 1; prev != ~0ULL && prev != K; probe++) {
+                if (probe == HT) return true;
+                slot = (slot + 1) & (HT - 1);
+                prev = atomicCAS(&hKey[slot], ~0ULL, K);
+            }
+            claimed = (prev == ~0ULL);
+            bid(r, slot, claimed);
+            return false;
+        };
         // phase A on one record: claim the k-mer's slot, mark a second member, and bid for the run head; called by whole wavefronts
         // (new k-mers are counted once per wavefront, not with one LDS atomic per record on a single word)
         auto phaseA = [&](const R &r, uint32_t nSub, uint32_t sub) {
             bool claimed = false, full = false;
-            const unsigned long long K = NUCL ? (r.kmer | BIT63) : r.kmer;
+            const unsigned long long K = keyOf(r);
             const uint64_t hh = K * 0xD6E8FEB86659FD93ULL;
-            if (!isSentinel(r) && !(nSub > 1 && (uint32_t) ((hh >> 40) % nSub) != sub)) {
-                uint32_t slot = (uint32_t) (hh >> 32) & (HT - 1);
-                // (round 6: double hashing — an odd step from other bits of the hash instead of 1 — changed nothing, 38.7 -> 38.3 ms at 50 M reads: the
-                //  table is loaded to a third, probing is not where the time is; profiles/r06_ab_knobs.txt, call 3)
-                full = true;
-                for (uint32_t probe = 0; probe < HT; probe++) {
-                    const unsigned long long prev = atomicCAS(&hKey[slot], ~0ULL, K);
-                    if (prev == ~0ULL || prev == K) {
-                        claimed = (prev == ~0ULL);
-                        if (!claimed) atomicOr(&hMulti[slot >> 5], 1u << (slot & 31));
-                        const unsigned long long packed = ((unsigned long long) (0x7FFFu - (uint32_t) r.len) << 48) | ((unsigned long long) r.id << 16) |
-                                                          ((unsigned long long) ((uint32_t) r.pos & 0x7FFFu) << 1) | (NUCL ? ((r.kmer >> 63) & 1ULL) : 0ULL);
-                        atomicMin(&hBest[slot], packed);
-                        full = false;
-                        break;
-                    }
-                    slot = (slot + 1) & (HT - 1);
-                }
+            if (inSub(r, hh, nSub, sub)) {
+                const uint32_t slot = (uint32_t) (hh >> 32) & (HT - 1);
+                full = claimFrom(r, K, slot, atomicCAS(&hKey[slot], ~0ULL, K), claimed);
             }
             const unsigned long long cm = __ballot(claimed);
             if (cm && laneId() == 0) atomicAdd(&sFlag[0], (uint32_t) __popcll(cm));
             if (full) atomicExch(&sFlag[1], 1u);      // table full
         };
+        // phase A on the thread's registers: as phaseA on each, but the new k-mers of all GL_RMAX registers are counted into sFlag[0] with ONE atomic per
+        // wavefront, and a record outside the sub-pass swaps "empty" for "empty" — its CAS changes nothing — so that no branch stands in front of a probe
+        auto phaseARegs = [&](uint32_t nSub, uint32_t sub) {
+            uint32_t nClaimed = 0; bool full = false;    // new k-mers of the wavefront (uniform); table full (per lane)
+#pragma unroll
+            for (int j = 0; j < GL_RMAX; j++) {
+                if ((uint32_t) j * BLOCK < n) {
+                    const unsigned long long K = keyOf(rg[j]);
+                    const uint64_t hh = K * 0xD6E8FEB86659FD93ULL;
+                    const bool act = inSub(rg[j], hh, nSub, sub);
+                    const uint32_t slot = (uint32_t) (hh >> 32) & (HT - 1);
+                    const unsigned long long prev = atomicCAS(&hKey[slot], ~0ULL, act ? K : ~0ULL);
+                    bool claimed = false;
+                    if (act) full |= claimFrom(rg[j], K, slot, prev, claimed);
+                    nClaimed += (uint32_t) __popcll(__ballot(claimed));
+                }
+            }
+            if (nClaimed && laneId() == 0) atomicAdd(&sFlag[0], nClaimed);
+            if (full) atomicExch(&sFlag[1], 1u);      // table full
+        };
+        // the output record of a member whose run's head word is `best`: (rep, member, diagonal); false = the filter drops it
+        auto member = [&](const R &r, unsigned long long K, unsigned long long best, R &o) -> bool {
+            const uint32_t repId = (uint32_t) (best >> 16);
+            const int repPos = (int) ((best >> 1) & 0x7FFFu);
+            const int queryLen = (int) (0x7FFFu - (uint32_t) (best >> 48));
+            const int mLen = (int) r.len, mPos = (int) r.pos;
+            int diagonal = repPos - mPos;
+            unsigned long long rId = repId;
+            if (NUCL) {
+                bool repIsReverse = ((best & 1ULL) == 0);
+                if (K == firstRunKey) repIsReverse = false;       // kmermatcher.cpp:463 (never refreshed for run 0)
+                const bool targetIsReverse = ((r.kmer & BIT63) == 0);
+                int qp, tp; bool qRev;
+                if (repIsReverse && !targetIsReverse) { qp = repPos; tp = mPos; qRev = true; }
+                else if (repIsReverse && targetIsReverse) { qp = (queryLen - 1) - repPos; tp = (mLen - 1) - mPos; qRev = false; }
+                else if (!repIsReverse && targetIsReverse) { qp = (queryLen - 1) - repPos; tp = (mLen - 1) - mPos; qRev = true; }
+                else { qp = repPos; tp = mPos; qRev = false; }
+                qp = (int) (short) qp; tp = (int) (short) tp;     // positions are truncated to T exactly like the reference's T queryPos/targetPos
+                diagonal = qp - tp;
+                rId = qRev ? (rId & ~BIT63) : (rId | BIT63);
+            }
+            const bool canBeExtended = diagonal < 0 || (diagonal > (queryLen - mLen));
+            const bool cov = canBeCovered(a.covThr, a.covMode, (float) queryLen, (float) mLen);
+            const bool keep = (!a.includeOnlyExtendable && cov) || (canBeExtended && a.includeOnlyExtendable);
+            o.kmer = rId; o.id = r.id; o.len = r.len; o.pos = (int16_t) diagonal;
+            if (NUCL) embedOrd(o, r.kmer);
+            if (keep) maxRT = max(maxRT, (unsigned long long) (((rId & ~BIT63) << 32) | (unsigned long long) r.id));
+            return keep;
+        };
         // phase C on one record: (rep, member, diagonal) if the run has at least two members and the filter keeps it
         auto phaseC = [&](const R &r, uint32_t nSub, uint32_t sub) {
             bool keep = false; R o; o.kmer = 0; o.id = 0; o.len = 0; o.pos = 0;
-            if (!isSentinel(r)) {
-                const unsigned long long K = NUCL ? (r.kmer | BIT63) : r.kmer;
-                const uint64_t hh = K * 0xD6E8FEB86659FD93ULL;
-                if (!(nSub > 1 && (uint32_t) ((hh >> 40) % nSub) != sub)) {
-                    uint32_t slot = (uint32_t) (hh >> 32) & (HT - 1);
-                    while (hKey[slot] != K) slot = (slot + 1) & (HT - 1);
-                    if ((hMulti[slot >> 5] >> (slot & 31)) & 1u) {
-                        const unsigned long long best = hBest[slot];
-                        const uint32_t repId = (uint32_t) (best >> 16);
-                        const int repPos = (int) ((best >> 1) & 0x7FFFu);
-                        const int queryLen = (int) (0x7FFFu - (uint32_t) (best >> 48));
-                        const int mLen = (int) r.len, mPos = (int) r.pos;
-                        int diagonal = repPos - mPos;
-                        unsigned long long rId = repId;
-                        if (NUCL) {
-                            bool repIsReverse = ((best & 1ULL) == 0);
-                            if (K == firstRunKey) repIsReverse = false;       // kmermatcher.cpp:463 (never refreshed for run 0)
-                            const bool targetIsReverse = ((r.kmer & BIT63) == 0);
-                            int qp, tp; bool qRev;
-                            if (repIsReverse && !targetIsReverse) { qp = repPos; tp = mPos; qRev = true; }
-                            else if (repIsReverse && targetIsReverse) { qp = (queryLen - 1) - repPos; tp = (mLen - 1) - mPos; qRev = false; }
-                            else if (!repIsReverse && targetIsReverse) { qp = (queryLen - 1) - repPos; tp = (mLen - 1) - mPos; qRev = true; }
-                            else { qp = repPos; tp = mPos; qRev = false; }
-                            qp = (int) (short) qp; tp = (int) (short) tp;     // positions are truncated to T exactly like the reference's T queryPos/targetPos
-                            diagonal = qp - tp;
-                            rId = qRev ? (rId & ~BIT63) : (rId | BIT63);
-                        }
-                        const bool canBeExtended = diagonal < 0 || (diagonal > (queryLen - mLen));
-                        const bool cov = canBeCovered(a.covThr, a.covMode, (float) queryLen, (float) mLen);
-                        keep = (!a.includeOnlyExtendable && cov) || (canBeExtended && a.includeOnlyExtendable);
-                        o.kmer = rId; o.id = r.id; o.len = r.len; o.pos = (int16_t) diagonal;
-                        if (NUCL) embedOrd(o, r.kmer);
-                        if (keep) maxRT = max(maxRT, (unsigned long long) (((rId & ~BIT63) << 32) | (unsigned long long) r.id));
-                    }
-                }
+            const unsigned long long K = keyOf(r);
+            const uint64_t hh = K * 0xD6E8FEB86659FD93ULL;
+            if (inSub(r, hh, nSub, sub)) {
+                uint32_t slot = (uint32_t) (hh >> 32) & (HT - 1);
+                while (hKey[slot] != K) slot = (slot + 1) & (HT - 1);
+                if ((hMulti[slot >> 5] >> (slot & 31)) & 1u) keep = member(r, K, hBest[slot], o);
             }
             const unsigned long long mk = __ballot(keep);
             const uint32_t wr = (uint32_t) __popcll(mk & ((1ULL << laneId()) - 1ULL));
@@ -319,6 +356,31 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, WPE)
             }
             if (keep) out[arena + written + wbase + wr] = o;
         };
+        // phase C on register j.  nN: record positions of the next bucket when this is the bucket's last sub-pass and the next one fits the registers,
+        // else 0: the register takes its next record (list entries from LDS) as soon as its output record stands, ahead of the cursor atomic and the
+        // store, so that the load travels under the rest of the phase.
+        auto phaseCReg = [&](int j, uint32_t nSub, uint32_t sub, uint32_t nN) {
+            bool keep = false; R o;
+            if ((uint32_t) j * BLOCK < n) {
+                const unsigned long long K = keyOf(rg[j]);
+                const uint64_t hh = K * 0xD6E8FEB86659FD93ULL;
+                if (inSub(rg[j], hh, nSub, sub)) {
+                    uint32_t slot = (uint32_t) (hh >> 32) & (HT - 1);
+                    while (hKey[slot] != K) slot = (slot + 1) & (HT - 1);
+                    if ((hMulti[slot >> 5] >> (slot & 31)) & 1u) keep = member(rg[j], K, hBest[slot], o);
+                }
+            }
+            if (nN) { const uint32_t i = (uint32_t) j * BLOCK + threadIdx.x; rg[j] = (i < nN) ? in[(uint64_t) sList[i / RPL] * RPL + (i % RPL)] : none; }
+            if ((uint32_t) j * BLOCK < n) {
+                const unsigned long long mk = __ballot(keep);
+                uint32_t wbase = 0;
+                if (mk) {
+                    if (laneId() == 0) wbase = atomicAdd(&sCursor[par], (uint32_t) __popcll(mk));
+                    wbase = __builtin_amdgcn_readfirstlane(wbase);     // every lane of the wavefront is here, lane 0 is the first: no trip through the LDS crossbar
+                }
+                if (keep) out[arena + written + wbase + (uint32_t) __popcll(mk & ((1ULL << laneId()) - 1ULL))] = o;
+            }
+        };
         uint32_t nSub = 1;                           // sub-passes by a secondary hash when too many distinct k-mers
         const unsigned long long writtenAtBucketStart = written;
         for (;;) {
@@ -327,30 +389,24 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, WPE)
                 for (uint32_t i = threadIdx.x; i < HT; i += BLOCK) { hKey[i] = ~0ULL; hBest[i] = ~0ULL; if (i < HT / 32) hMulti[i] = 0; }
                 if (threadIdx.x == 0) { sFlag[0] = 0; sFlag[1] = 0; sCursor[par] = 0; }   // (the other cursor may still be being read)
                 __syncthreads();
-                if (inRegs) {
-#pragma unroll
-                    for (int j = 0; j < GL_RMAX; j++) if ((uint32_t) j * BLOCK < n) phaseA(rg[j], nSub, sub);
-                } else for (uint32_t i0 = 0; i0 < n; i0 += BLOCK) { const uint32_t i = i0 + threadIdx.x; phaseA(i < n ? recAt(i) : none, nSub, sub); }
+                if (inRegs) phaseARegs(nSub, sub);
+                else for (uint32_t i0 = 0; i0 < n; i0 += BLOCK) { const uint32_t i = i0 + threadIdx.x; phaseA(i < n ? recAt(i) : none, nSub, sub); }
                 if (!aheadStored) { if (threadIdx.x < GL_RMAX * BLOCK / RPL) sList[threadIdx.x] = leAhead; aheadStored = true; }
                 __syncthreads();
                 if (sFlag[1] || sFlag[0] > MAXKEYS) { redo = true; __syncthreads(); break; }
                 if (inRegs && sub + 1 == nSub) {
-                    // last sub-pass: a record register is dead once its phase C is through — the next bucket's record takes it at once (list entries from
-                    // LDS), so the loads of registers 0..6 travel under the rest of this phase instead of starting behind it
+                    // last sub-pass: a record register is dead once its output record stands — the next bucket's record takes it at once
                     const uint32_t nN = (b + 1 < bEnd) ? a.lineCnt[b + 1] * RPL : 0u, lbN = (b + 1 < bEnd) ? a.lineBeg[b + 1] : 0u;
-                    const bool nextRegs = nN && nN <= (uint32_t) GL_RMAX * BLOCK;
+                    const uint32_t nRefill = (nN && nN <= (uint32_t) GL_RMAX * BLOCK) ? nN : 0u;
 #pragma unroll
-                    for (int j = 0; j < GL_RMAX; j++) {
-                        if ((uint32_t) j * BLOCK < n) phaseC(rg[j], nSub, sub);
-                        if (nextRegs) { const uint32_t i = (uint32_t) j * BLOCK + threadIdx.x; rg[j] = (i < nN) ? in[(uint64_t) sList[i / RPL] * RPL + (i % RPL)] : none; }
-                    }
+                    for (int j = 0; j < GL_RMAX; j++) phaseCReg(j, nSub, sub, nRefill);
                     nNext = nN; lbNext = lbN; fetched = true;
                 } else {
-                if (inRegs) {
+                    if (inRegs) {
 #pragma unroll
-                    for (int j = 0; j < GL_RMAX; j++) if ((uint32_t) j * BLOCK < n) phaseC(rg[j], nSub, sub);
-                } else for (uint32_t i0 = 0; i0 < n; i0 += BLOCK) { const uint32_t i = i0 + threadIdx.x; phaseC(i < n ? recAt(i) : none, nSub, sub); }
-                if (sub + 1 == nSub) { fetch(b + 1, true); fetched = true; }     // last sub-pass: nothing reads this bucket's registers again
+                        for (int j = 0; j < GL_RMAX; j++) phaseCReg(j, nSub, sub, 0u);
+                    } else for (uint32_t i0 = 0; i0 < n; i0 += BLOCK) { const uint32_t i = i0 + threadIdx.x; phaseC(i < n ? recAt(i) : none, nSub, sub); }
+                    if (sub + 1 == nSub) { fetch(b + 1, true); fetched = true; }     // last sub-pass: nothing reads this bucket's registers again
                 }
                 __syncthreads();
                 written += sCursor[par];
