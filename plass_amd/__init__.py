@@ -7,8 +7,8 @@ in-tree HIP library (plass_amd/libplasship.so) or without a GPU every entry poin
 """
 from ._lib import (  # noqa: F401
     PlasshipError, Context, SeqDB, Candidates, Alignments, Clusters, MergedClusters, ClustStats, CcStats,
-    KmermatchParams, RescoreParams, AssembleParams, OrfParams, OrfHeaders, SynthParams, MergeParams, MergeStats, CreatedbStats, lib_path, clust_lib_path, linclust_lib_path, subst_lib_path, cc_lib_path, load_library, resume_point,
+    KmermatchParams, RescoreParams, AssembleParams, OrfParams, OrfHeaders, SynthParams, MergeParams, MergeStats, CreatedbStats, lib_path, clust_lib_path, linclust_lib_path, subst_lib_path, cc_lib_path, gencode_lib_path, gencode_info, load_library, resume_point,
 )
 
 __all__ = ["PlasshipError", "Context", "SeqDB", "Candidates", "Alignments", "Clusters", "MergedClusters", "ClustStats", "CcStats", "KmermatchParams",
-           "RescoreParams", "AssembleParams", "OrfParams", "OrfHeaders", "SynthParams", "MergeParams", "MergeStats", "CreatedbStats", "lib_path", "clust_lib_path", "linclust_lib_path", "subst_lib_path", "cc_lib_path", "load_library", "resume_point"]
+           "RescoreParams", "AssembleParams", "OrfParams", "OrfHeaders", "SynthParams", "MergeParams", "MergeStats", "CreatedbStats", "lib_path", "clust_lib_path", "linclust_lib_path", "subst_lib_path", "cc_lib_path", "gencode_lib_path", "gencode_info", "load_library", "resume_point"]

@@ -27,6 +27,11 @@ def subst_lib_path():
     return os.path.join(os.path.dirname(lib_path()), "libplasship_subst.so")
 
 
+def gencode_lib_path():
+    """the extension library with extractorfs / translatenucs for any genetic code (include/plasship_ext/gencode.h), beside the others"""
+    return os.path.join(os.path.dirname(lib_path()), "libplasship_gencode.so")
+
+
 def cc_lib_path():
     """the extension library with connected-component clustering (clust --cluster-mode 1, include/plasship_ext/cc.h), beside the others"""
     return os.path.join(os.path.dirname(lib_path()), "libplasship_cc.so")
@@ -274,6 +279,12 @@ CC_SYMBOLS = [
     ("plasship_clust_connected_cands", C.c_int, [P, P, P, C.c_int, C.POINTER(P), C.POINTER(CcStats)]),
     ("plasship_clust_connected_alns", C.c_int, [P, P, P, C.c_int, C.POINTER(P), C.POINTER(CcStats)]),
 ]
+# include/plasship_ext/gencode.h (the extension library libplasship_gencode.so: extractorfs / translatenucs with any genetic code)
+GENCODE_SYMBOLS = [
+    ("plasship_extract_orfs_gc", C.c_int, [P, P, C.POINTER(_OrfParams), C.POINTER(P), C.POINTER(P), C.POINTER(OrfStats)]),
+    ("plasship_translate_nucs_gc", C.c_int, [P, P, P, C.POINTER(_TranslateParams), C.POINTER(P), C.POINTER(OrfStats)]),
+    ("plasship_gencode_info", C.c_int, [C.c_int, C.c_char_p, C.c_char_p]),
+]
 # include/plasship_rccl.h (native RCCL communicator of a sharded run)
 RCCL_SYMBOLS = [
     ("plasship_rccl_get_unique_id", C.c_int, [P]),
@@ -369,6 +380,32 @@ def load_cc_library():
             fn.argtypes = args
         lib.cc = ext
     return lib.cc
+
+
+def load_gencode_library():
+    """the extension library with the other genetic codes, loaded when it is first asked for (Context.extractorfs_gencode, gencode_info) behind
+    the library it takes its handles from: its entry points are then reached as load_library().gencode.<name>.  A missing library is an error,
+    there is no fall-back."""
+    lib = load_library()
+    if getattr(lib, "gencode", None) is None:
+        gpath = gencode_lib_path()
+        if not os.path.exists(gpath):
+            raise PlasshipError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`" % gpath)
+        ext = C.CDLL(gpath)
+        for name, res, args in GENCODE_SYMBOLS:
+            fn = getattr(ext, name)
+            fn.restype = res
+            fn.argtypes = args
+        lib.gencode = ext
+    return lib.gencode
+
+
+def gencode_info(table):
+    """(residues, starts) of --translation-table `table`: two 64-letter strings over the codons in T, C, A, G order; an id the reference does not
+    accept raises"""
+    res, sta = C.create_string_buffer(65), C.create_string_buffer(65)
+    _check(load_gencode_library().plasship_gencode_info(int(table), res, sta), "plasship_gencode_info")
+    return res.value.decode(), sta.value.decode()
 
 
 def resume_point(dir, num_iterations, name="assembly_"):
@@ -702,6 +739,19 @@ class Context:
         _check(self.lib.plasship_translate_nucs(self.h, orfs.h, hdr.h if hdr is not None else None, C.byref(cp), C.byref(h), C.byref(st)), "plasship_translate_nucs")
         return SeqDB(self, h), st
 
+    def extractorfs_gencode(self, reads, par=None):
+        """extractorfs with any --translation-table the reference accepts and --use-all-table-starts (libplasship_gencode.so)"""
+        par = par or OrfParams()
+        h = P(); hh = P(); st = OrfStats(); cp = par._c()
+        _check(load_gencode_library().plasship_extract_orfs_gc(self.h, reads.h, C.byref(cp), C.byref(h), C.byref(hh), C.byref(st)), "plasship_extract_orfs_gc")
+        return SeqDB(self, h), OrfHeaders(self, hh), st
+
+    def translatenucs_gencode(self, orfs, hdr=None, add_orf_stop=False, max_seq_len=65535, translation_table=1):
+        """translatenucs with any --translation-table the reference accepts (libplasship_gencode.so)"""
+        h = P(); st = OrfStats(); cp = _TranslateParams(int(translation_table), int(add_orf_stop), max_seq_len)
+        _check(load_gencode_library().plasship_translate_nucs_gc(self.h, orfs.h, hdr.h if hdr is not None else None, C.byref(cp), C.byref(h), C.byref(st)), "plasship_translate_nucs_gc")
+        return SeqDB(self, h), st
+
     def concatdbs(self, a, b, preserve_keys=False):
         """reference module concatdbs (keys of A kept, B renumbered behind them; preserve_keys: B's kept as well — the union); sequence DBs or header DBs"""
         h = P()
@@ -719,14 +769,20 @@ class Context:
         _check(self.lib.plasship_orfhdr_read(self.h, os.fsencode(path), C.byref(h)), "plasship_orfhdr_read")
         return OrfHeaders(self, h)
 
-    def plass_fragments(self, reads, keep=False):
+    def plass_fragments(self, reads, keep=False, translation_table=1, use_all_table_starts=False):
         """the whole preprocessing chain of `plass assemble` on a read DB: two extractorfs passes, translatenucs --add-orf-stop,
-        concatdbs -> aa_6f_start_long, the DB iteration 0 starts from (data/assemble.sh:41-77)"""
-        o_long, h_long, _ = self.extractorfs(reads, OrfParams(**PLASS_ORFS_LONG))
-        aa_long, _ = self.translatenucs(o_long, h_long, add_orf_stop=True)
+        concatdbs -> aa_6f_start_long, the DB iteration 0 starts from (data/assemble.sh:41-77).  Another genetic code than the standard
+        one with ATG (plass assemble --translation-table N --use-all-table-starts 1) goes through the *_gencode entry points"""
+        if translation_table == 1 and not use_all_table_starts:
+            code, extract, translate = {}, self.extractorfs, self.translatenucs
+        else:
+            code, extract = dict(translation_table=translation_table, use_all_table_starts=bool(use_all_table_starts)), self.extractorfs_gencode
+            translate = lambda o, h, add_orf_stop: self.translatenucs_gencode(o, h, add_orf_stop=add_orf_stop, translation_table=translation_table)      # noqa: E731
+        o_long, h_long, _ = extract(reads, OrfParams(**PLASS_ORFS_LONG, **code))
+        aa_long, _ = translate(o_long, h_long, add_orf_stop=True)
         o_long.free(); h_long.free()
-        o_start, h_start, _ = self.extractorfs(reads, OrfParams(**PLASS_ORFS_START))
-        aa_start, _ = self.translatenucs(o_start, h_start, add_orf_stop=True)
+        o_start, h_start, _ = extract(reads, OrfParams(**PLASS_ORFS_START, **code))
+        aa_start, _ = translate(o_start, h_start, add_orf_stop=True)
         o_start.free(); h_start.free()
         out = self.concatdbs(aa_long, aa_start)
         aa_long.free(); aa_start.free()

@@ -14,6 +14,7 @@
 #include "../../include/plasship_ext/linclust.h"
 #include "../../include/plasship_ext/subst.h"
 #include "../../include/plasship_ext/cc.h"
+#include "../../include/plasship_ext/gencode.h"
 #include <chrono>
 #include <unistd.h>
 #include <cstdarg>
@@ -181,6 +182,9 @@ enum : unsigned {
     ANY_ASSEMBLERESULTS = ASSEMBLERESULTS | NUCLASSEMBLERESULTS | GUIDEDASSEMBLERESULTS, CHAINS = ASSEMBLE_CHAIN | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN,
     CLUST_GREEDY = 1u << 17, LINCLUST_PRE = 1u << 18, RESCOREDIAGONAL_LOCAL = 1u << 19, MERGECLUSTERS_GREEDY = 1u << 20, LINCLUST_UNGAPPED = 1u << 21,
     RESCOREDIAGONAL_SUBST = 1u << 22, LINCLUST_UNGAPPED_PROT = 1u << 23, CLUST_REPSEQ = 1u << 24, CLUST_CONNECTED = 1u << 25,
+    EXTRACTORFS_GENCODE = 1u << 26, TRANSLATENUCS_GENCODE = 1u << 27,      // (extractorfs' and translatenucs' flag sets)
+    ANY_EXTRACTORFS = EXTRACTORFS | EXTRACTORFS_GENCODE, ANY_TRANSLATENUCS = TRANSLATENUCS | TRANSLATENUCS_GENCODE,
+    ORF_CHAINS = ASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN,                     // the workflows that translate: they hand the table to both modules
     // (rescorediagonal-hamming, rescorediagonal-local and rescorediagonal-subst take rescorediagonal's flag set, clust-greedy clust's; linclust-pre the union of its three steps',
     //  linclust-ungapped the union of linclust-pre's and rescorediagonal-local's; mergeclusters-greedy has the reference's: --threads, --compressed, -v;
     //  linclust-ungapped-prot has linclust-ungapped's set, clust-repseq result2repseq's: --db-load-mode, --compressed, --threads, -v; clust-connected clust's)
@@ -188,7 +192,7 @@ enum : unsigned {
     ANY_KMERMATCHER = KMERMATCHER | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
     ANY_RESCOREDIAGONAL = RESCOREDIAGONAL | RESCOREDIAGONAL_HAMMING | RESCOREDIAGONAL_LOCAL | RESCOREDIAGONAL_SUBST | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
     ANY_CLUST = CLUST_GREEDY | CLUST_CONNECTED | LINCLUST_PRE | ANY_LINCLUST_UNGAPPED,
-    ALL = 0x3FFFFFFu
+    ALL = 0xFFFFFFFu
 };
 
 // ---- the flags: each once, with the modules that own it (its parameter vector in the reference; for the fused drivers the workflow's own),
@@ -238,8 +242,8 @@ static const Flag kFlags[] = {
     {"--ignore-multi-kmer", ANY_KMERMATCHER | CHAINS, BOOL, M(ignoreMulti)}, {"--rescore-mode", ANY_RESCOREDIAGONAL | ANY_ASSEMBLERESULTS | CHAINS, VALUE, M(rescoreMode)},
     {"-e", ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(evalThr)}, {"--min-aln-len", ANY_RESCOREDIAGONAL | CHAINS, BOTH_GUIDED, M(minAlnLen), M(minAlnLenNucl)},
     {"--seq-id-mode", ANY_RESCOREDIAGONAL | CHAINS, VALUE, M(seqIdMode)}, {"--keep-target", ANY_ASSEMBLERESULTS | CHAINS, BOOL, M(keepTarget)},
-    {"--chop-cycle", CYCLECHECK | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN, BOOL, M(chopCycle)}, {"--translation-table", EXTRACTORFS | TRANSLATENUCS, VALUE, M(translationTable)},
-    {"--id-offset", EXTRACTORFS | CREATEDB_READS, CUSTOM, {}, {}, idOffsetFlag},
+    {"--chop-cycle", CYCLECHECK | NUCLASSEMBLE_CHAIN | GUIDEDASSEMBLE_CHAIN, BOOL, M(chopCycle)}, {"--translation-table", ANY_EXTRACTORFS | ANY_TRANSLATENUCS | ORF_CHAINS, VALUE, M(translationTable)},
+    {"--id-offset", ANY_EXTRACTORFS | CREATEDB_READS, CUSTOM, {}, {}, idOffsetFlag},
     // one module's own
     {"--spaced-kmer-mode", ANY_KMERMATCHER, ZERO}, {"--spaced-kmer-pattern", ANY_KMERMATCHER, EMPTY}, {"--adjust-kmer-len", ANY_KMERMATCHER, ZERO_BOOL}, {"--mask", ANY_KMERMATCHER, ZERO},
     {"--mask-lower-case", ANY_KMERMATCHER, ZERO}, {"--split-memory-limit", ANY_KMERMATCHER, IGNORED}, {"--include-only-extendable", ANY_KMERMATCHER, BOOL, M(onlyExt)},
@@ -248,10 +252,10 @@ static const Flag kFlags[] = {
     {"--score-per-col-thr", RESCOREDIAGONAL_LOCAL | RESCOREDIAGONAL_SUBST | ANY_LINCLUST_UNGAPPED, VALUE, M(scorePerColThr)}, {"--rep-out", ANY_LINCLUST_UNGAPPED, VALUE, M(repOut)},
     {"--cluster-mode", ANY_CLUST, VALUE, M(clusterMode)}, {"--max-iterations", ANY_CLUST, VALUE, M(maxIterations)}, {"--similarity-type", ANY_CLUST, IGNORED},
     {"--gap-open", PROTEINALN2NUCL, NUCL, M(gapOpenNucl)}, {"--gap-extend", PROTEINALN2NUCL, NUCL, M(gapExtendNucl)},
-    {"--min-length", EXTRACTORFS, VALUE, M(orfMin)}, {"--max-length", EXTRACTORFS, VALUE, M(orfMax)}, {"--max-gaps", EXTRACTORFS, VALUE, M(orfGaps)},
-    {"--contig-start-mode", EXTRACTORFS, VALUE, M(contigStart)}, {"--contig-end-mode", EXTRACTORFS, VALUE, M(contigEnd)}, {"--orf-start-mode", EXTRACTORFS, VALUE, M(orfStart)},
-    {"--forward-frames", EXTRACTORFS, FRAMES, M(fwdFrames)}, {"--reverse-frames", EXTRACTORFS, FRAMES, M(revFrames)}, {"--translate", EXTRACTORFS, VALUE, M(translate)},
-    {"--use-all-table-starts", EXTRACTORFS, BOOL, M(allStarts)}, {"--create-lookup", EXTRACTORFS, ZERO}, {"--add-orf-stop", TRANSLATENUCS, BOOL, M(addOrfStop)},
+    {"--min-length", ANY_EXTRACTORFS, VALUE, M(orfMin)}, {"--max-length", ANY_EXTRACTORFS, VALUE, M(orfMax)}, {"--max-gaps", ANY_EXTRACTORFS, VALUE, M(orfGaps)},
+    {"--contig-start-mode", ANY_EXTRACTORFS, VALUE, M(contigStart)}, {"--contig-end-mode", ANY_EXTRACTORFS, VALUE, M(contigEnd)}, {"--orf-start-mode", ANY_EXTRACTORFS, VALUE, M(orfStart)},
+    {"--forward-frames", ANY_EXTRACTORFS, FRAMES, M(fwdFrames)}, {"--reverse-frames", ANY_EXTRACTORFS, FRAMES, M(revFrames)}, {"--translate", ANY_EXTRACTORFS, VALUE, M(translate)},
+    {"--use-all-table-starts", ANY_EXTRACTORFS | ORF_CHAINS, BOOL, M(allStarts)}, {"--create-lookup", ANY_EXTRACTORFS, ZERO}, {"--add-orf-stop", ANY_TRANSLATENUCS, BOOL, M(addOrfStop)},
     {"--preserve-keys", CONCATDBS, BOOL, M(preserveKeys)}, {"--take-larger-entry", CONCATDBS, BOOL, M(takeLarger)},
     {"--shuffle", CREATEDB_READS, BOOL, M(shuffle)}, {"--dbtype", CREATEDB_READS, VALUE, M(dbtypeArg)}, {"--createdb-mode", CREATEDB_READS, VALUE, M(createdbMode)},
     {"--write-lookup", CREATEDB_READS, VALUE, M(writeLookup)},
@@ -459,6 +463,7 @@ static Manifest chainManifest(const std::string &mod, const Flags &f, const std:
         {"-c", M(covThr)}, {"--cov-mode", M(covMode)}, {"--min-aln-len", M(minAlnLen)}, {"--seq-id-mode", M(seqIdMode)}, {"--rescore-mode", M(rescoreMode)},
         {"--ignore-multi-kmer", M(ignoreMulti)}, {"--include-only-extendable", M(onlyExt)}, {"--keep-target", M(keepTarget)}, {"--max-seq-len", M(maxSeqLen)},
         {"--chop-cycle", M(chopCycle)}, {"--from-reads", M(fromReads)}, {"--single-end", M(singleEnd)},
+        {"--translation-table", M(translationTable)}, {"--use-all-table-starts", M(allStarts)},
     };
     const Dest scale = mod == "nuclassemble-chain" ? M(scaleNucl) : M(scaleAA);      // (the half of --kmer-per-seq-scale the chain's alphabet reads)
     for (const auto &p : params) m.emplace_back(p.key, (p.dest.type == Dest::NONE ? scale : p.dest).str(f));
@@ -528,6 +533,12 @@ static int takeReadFiles(Call &c, size_t nOutputs) {        // every positional 
         if (q.size() >= 4 && q.compare(q.size() - 4, 4, ".bz2") == 0) return unsupported("plass-hip %s: bzip2 input (%s) is left to the reference\n", c.m->name, q.c_str());
     }
     return 0;
+}
+// an id outside TranslateNucl.h:82-108 ends the reference ("Invalid translation table selected!", TranslateNucl.h:242-245): an error of the call here too
+static int validateGencode(Call &c) {
+    if (plasship_gencode_info(c.f.translationTable, nullptr, nullptr) == 0) return 0;
+    fprintf(stdout, "Invalid translation table selected! (--translation-table %d)\n", c.f.translationTable);
+    return EXIT_FAILURE;
 }
 static int validateKmermatcher(Call &c) {
     // the module's own defaults for these two are "choose automatically" (k = 0: from the DB size, kmermatcher.cpp:607-613; --kmer-per-seq 0): not
@@ -674,6 +685,7 @@ static int validateMergereads(Call &c) {
 }
 static int validateChain(Call &c) {
     const Flags &f = c.f; const std::vector<std::string> &pos = c.pos; const char *mod = c.m->name; const size_t nOut = nChainOut(c);
+    if (c.m->id & ORF_CHAINS) if (const int rc = validateGencode(c)) return rc;      // --translation-table: the workflows hand it to extractorfs and translatenucs
     if (f.singleEnd) {      // every positional before the output(s) is an unpaired read file (data/assemble.sh:27-38: createdb in place of mergereads)
         if (pos.size() < nOut + 1) { fprintf(stdout, "%s: --single-end 1 needs at least one read file before the output\n", mod); return EXIT_FAILURE; }
     } else if (pos.size() > nOut + 1 && (pos.size() - nOut) % 2) { fprintf(stdout, "%s: one DB or pairs of FASTQ files before the output\n", mod); return EXIT_FAILURE; }
@@ -966,22 +978,30 @@ static int runCyclecheck(Call &c) {
     fprintf(stdout, "circular: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_cyclic, st.ms_kernel);
     return KW(plasship_seqdb_write(ctx, o, c.pos[1].c_str())) ? fail("cyclecheck") : EXIT_SUCCESS;
 }
-static int runExtractorfs(Call &c) {              // writes <out> and <out>_h like the reference (extractorfs.cpp:28-32)
-    plasship_ctx *ctx = c.ctx; SeqDb db(ctx), o(ctx); OrfHdr h(ctx);
-    if (K(plasship_seqdb_read(ctx, c.pos[0].c_str(), db.out()))) return fail("extractorfs");
+// the genetic code of a call: the standard one with ATG goes through the entry points that know nothing else, any other through libplasship_gencode.so
+static bool standardCode(int table, int allStarts) { return table == 1 && !allStarts; }
+static int extractOrfs(plasship_ctx *ctx, const plasship_seqdb *reads, const plasship_orf_params &p, plasship_seqdb **orfs, plasship_orfhdr **hdr, plasship_orf_stats *st) {
+    return standardCode(p.translation_table, p.use_all_table_starts) ? plasship_extract_orfs(ctx, reads, &p, orfs, hdr, st) : plasship_extract_orfs_gc(ctx, reads, &p, orfs, hdr, st);
+}
+static int translateNucs(plasship_ctx *ctx, const plasship_seqdb *orfs, const plasship_orfhdr *hdr, const plasship_translate_params &p, plasship_seqdb **aa, plasship_orf_stats *st) {
+    return p.translation_table == 1 ? plasship_translate_nucs(ctx, orfs, hdr, &p, aa, st) : plasship_translate_nucs_gc(ctx, orfs, hdr, &p, aa, st);
+}
+static int runExtractorfs(Call &c) {              // writes <out> and <out>_h like the reference (extractorfs.cpp:28-32); extractorfs-gencode: with any genetic code
+    plasship_ctx *ctx = c.ctx; SeqDb db(ctx), o(ctx); OrfHdr h(ctx); const char *name = c.m->name;
+    if (K(plasship_seqdb_read(ctx, c.pos[0].c_str(), db.out()))) return fail(name);
     const plasship_orf_params p = orfParams(c.f); plasship_orf_stats st = {};
-    if (K(plasship_extract_orfs(ctx, db, &p, o.out(), h.out(), &st))) return fail("extractorfs");
+    if (K(c.m->id == EXTRACTORFS_GENCODE ? plasship_extract_orfs_gc(ctx, db, &p, o.out(), h.out(), &st) : plasship_extract_orfs(ctx, db, &p, o.out(), h.out(), &st))) return fail(name);
     fprintf(stdout, "orfs: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_out, st.ms_kernel);
-    return KW(plasship_seqdb_write(ctx, o, c.pos[1].c_str())) || KW(plasship_orfhdr_write(ctx, h, (c.pos[1] + "_h").c_str())) ? fail("extractorfs") : EXIT_SUCCESS;
+    return KW(plasship_seqdb_write(ctx, o, c.pos[1].c_str())) || KW(plasship_orfhdr_write(ctx, h, (c.pos[1] + "_h").c_str())) ? fail(name) : EXIT_SUCCESS;
 }
 static int runTranslatenucs(Call &c) {
-    plasship_ctx *ctx = c.ctx; SeqDb db(ctx), o(ctx); OrfHdr h(ctx);
-    if (K(plasship_seqdb_read(ctx, c.pos[0].c_str(), db.out()))) return fail("translatenucs");
-    if (c.f.addOrfStop && K(plasship_orfhdr_read(ctx, (c.pos[0] + "_h").c_str(), h.out()))) return fail("translatenucs");      // translatenucs.cpp:29-34
+    plasship_ctx *ctx = c.ctx; SeqDb db(ctx), o(ctx); OrfHdr h(ctx); const char *name = c.m->name;
+    if (K(plasship_seqdb_read(ctx, c.pos[0].c_str(), db.out()))) return fail(name);
+    if (c.f.addOrfStop && K(plasship_orfhdr_read(ctx, (c.pos[0] + "_h").c_str(), h.out()))) return fail(name);      // translatenucs.cpp:29-34
     plasship_translate_params p; p.translation_table = c.f.translationTable; p.add_orf_stop = c.f.addOrfStop; p.max_seq_len = c.f.maxSeqLen; plasship_orf_stats st = {};
-    if (K(plasship_translate_nucs(ctx, db, h, &p, o.out(), &st))) return fail("translatenucs");
+    if (K(c.m->id == TRANSLATENUCS_GENCODE ? plasship_translate_nucs_gc(ctx, db, h, &p, o.out(), &st) : plasship_translate_nucs(ctx, db, h, &p, o.out(), &st))) return fail(name);
     fprintf(stdout, "translated: %llu | kernel ms: %.3f\n", (unsigned long long) st.n_out, st.ms_kernel);
-    return KW(plasship_seqdb_write(ctx, o, c.pos[1].c_str())) ? fail("translatenucs") : EXIT_SUCCESS;
+    return KW(plasship_seqdb_write(ctx, o, c.pos[1].c_str())) ? fail(name) : EXIT_SUCCESS;
 }
 static int runConcatdbs(Call &c) {                // sequence DBs, or the header DBs of ORF DBs (dbtype 12: data/assemble.sh:75); other types: validateConcatdbs
     plasship_ctx *ctx = c.ctx; const std::vector<std::string> &pos = c.pos;
@@ -1019,10 +1039,10 @@ static int runMergereads(Call &c) {               // writes <out> and <out>_h li
 // ---- fused drivers: the iteration loop of a workflow script with every DB of the loop resident in HBM; only the first DB is read from disk and
 //      only the last one written (plus, with --write-intermediate DIR, every iteration's assembly by a host thread on a second context while
 //      the next iteration runs, with the workflow's .done sentinels) ----
-static plasship_orf_params chainOrfParams(bool start) {       // the two extractorfs passes (Assembler.cpp:116-130, GuidedNuclassembler.cpp:133-145)
+static plasship_orf_params chainOrfParams(bool start, const Flags &f) {       // the two extractorfs passes (Assembler.cpp:116-130, GuidedNuclassembler.cpp:133-145)
     plasship_orf_params p; memset(&p, 0, sizeof(p));
     p.min_length = start ? 20 : 45; p.max_length = start ? 45 : 32734; p.max_gaps = 0; p.contig_start_mode = start ? 1 : 2; p.contig_end_mode = start ? 0 : 2;
-    p.orf_start_mode = 0; p.forward_frames = 7; p.reverse_frames = 7; p.translation_table = 1; p.max_seq_len = 65535;
+    p.orf_start_mode = 0; p.forward_frames = 7; p.reverse_frames = 7; p.translation_table = f.translationTable; p.use_all_table_starts = f.allStarts; p.max_seq_len = 65535;
     return p;
 }
 // the input of a chain — a DB, FASTQ pairs (the workflows' mergereads step) or unpaired read files (their createdb step, data/assemble.sh:27-38) —
@@ -1046,16 +1066,16 @@ static int prepareChainInput(Call &c, ChainLoop &L, SeqDb &in, bool keepReads, d
     const int dbtype = dbtypeOf(in);
     if (gd || (prot && (f.fromReads || dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES))) {
         if (dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { fprintf(stdout, "%s: the input must be a nucleotide read DB\n", mod); return EXIT_FAILURE; }
-        plasship_translate_params tp; tp.translation_table = 1; tp.add_orf_stop = 1; tp.max_seq_len = 65535;
+        plasship_translate_params tp; tp.translation_table = f.translationTable; tp.add_orf_stop = 1; tp.max_seq_len = 65535;
         SeqDb ol(ctx), os(ctx); OrfHdr hl(ctx), hs(ctx); plasship_orf_stats ost;
-        const plasship_orf_params pl = chainOrfParams(false), ps = chainOrfParams(true);
-        if (K(plasship_extract_orfs(ctx, in, &pl, ol.out(), hl.out(), &ost)) || K(plasship_extract_orfs(ctx, in, &ps, os.out(), hs.out(), &ost))) return fail(mod);
+        const plasship_orf_params pl = chainOrfParams(false, f), ps = chainOrfParams(true, f);
+        if (K(extractOrfs(ctx, in, pl, ol.out(), hl.out(), &ost)) || K(extractOrfs(ctx, in, ps, os.out(), hs.out(), &ost))) return fail(mod);
         if (gd) {      // concatdbs of ORFs and headers, then one translatenucs (data/guidedNuclAssemble.sh:56-75): db = nucleotide ORFs, aa = their twins
             OrfHdr hh(ctx);
-            if (K(plasship_seqdb_concat(ctx, ol, os, L.db.out())) || K(plasship_orfhdr_concat(ctx, hl, hs, hh.out())) || K(plasship_translate_nucs(ctx, L.db, hh, &tp, L.aa.out(), &ost))) return fail(mod);
+            if (K(plasship_seqdb_concat(ctx, ol, os, L.db.out())) || K(plasship_orfhdr_concat(ctx, hl, hs, hh.out())) || K(translateNucs(ctx, L.db, hh, tp, L.aa.out(), &ost))) return fail(mod);
         } else {       // translatenucs x2, then concatdbs (data/assemble.sh:41-77)
             SeqDb al(ctx), as(ctx);
-            if (K(plasship_translate_nucs(ctx, ol, hl, &tp, al.out(), &ost)) || K(plasship_translate_nucs(ctx, os, hs, &tp, as.out(), &ost)) || K(plasship_seqdb_concat(ctx, al, as, L.db.out()))) return fail(mod);
+            if (K(translateNucs(ctx, ol, hl, tp, al.out(), &ost)) || K(translateNucs(ctx, os, hs, tp, as.out(), &ost)) || K(plasship_seqdb_concat(ctx, al, as, L.db.out()))) return fail(mod);
         }
         if (!keepReads) in.reset();      // (the guided tail concatenates the reads: guidedNuclAssemble.sh:161-165)
     } else if ((prot && dbtype != PLASSHIP_DBTYPE_AMINO_ACIDS) || (nuc && dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES)) {
@@ -1202,6 +1222,9 @@ static const Module kModules[] = {
     {"extractorfs", EXTRACTORFS, 2, "extractorfs <i:sequenceDB> <o:sequenceDB>", nullptr, nullptr, runExtractorfs},
     {"translatenucs", TRANSLATENUCS, 2, "translatenucs <i:sequenceDB> <o:sequenceDB>", nullptr, nullptr, runTranslatenucs},
     {"concatdbs", CONCATDBS, 3, "concatdbs <i:DB> <i:DB> <o:DB>", nullptr, validateConcatdbs, runConcatdbs},
+    // the two with any genetic code of the reference (our own names: `extractorfs` and `translatenucs` keep their answers, the standard code only)
+    {"extractorfs-gencode", EXTRACTORFS_GENCODE, 2, "extractorfs-gencode <i:sequenceDB> <o:sequenceDB> [--translation-table N] [--use-all-table-starts 1]", nullptr, validateGencode, runExtractorfs},
+    {"translatenucs-gencode", TRANSLATENUCS_GENCODE, 2, "translatenucs-gencode <i:sequenceDB> <o:sequenceDB> [--translation-table N]", nullptr, validateGencode, runTranslatenucs},
     // the fused drivers (not reference modules: the iteration loops of data/assemble.sh:85-156, nuclassemble.sh:95-137 and guidedNuclAssemble.sh:77-126
     // with the DBs chained in HBM)
     {"assemble-chain", ASSEMBLE_CHAIN, 2, "assemble-chain: wrong number of databases",

@@ -10,6 +10,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <map>
 #include <vector>
 #include "../../include/plasship.h"
 
@@ -169,6 +170,9 @@ struct plasship_ctx {
     // cyclecheck.hip: generation of the last "rest" DB plasship_cyclecheck made on this context (every entry of it is known not to be
     // circular at that --max-seq-len); a later call on a DB that descends from it checks only the entries rewritten since
     uint64_t cycKnownGen = 0, cycKnownMaxLen = 0;
+    // orfs.hip: the device tables (complement, gap, base codes, residue LUT) of every genetic code but the standard one that this context
+    // has extracted or translated with, by --translation-table id; uploaded on first use
+    std::map<int, plasship::DevBuf> gencodeTables;
 };
 
 namespace plasship {
@@ -349,6 +353,10 @@ int stagedCopyToDevice(plasship_ctx *ctx, void *dDst, const void *hSrc, uint64_t
 int stagedCopyToHost(plasship_ctx *ctx, void *hDst, const void *dSrc, uint64_t bytes);
 // sets *differ when two key arrays (device, n entries) are not identical
 int deviceKeysDiffer(plasship_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t n, bool *differ);
+// orfs.hip: extractorfs / translatenucs with any genetic code and the codes' strings; libplasship_gencode.so exports them (include/plasship_ext/gencode.h)
+int gencodeInfo(int table, char residues[65], char starts[65]);
+int extractOrfsGencode(plasship_ctx *ctx, const plasship_seqdb *reads, const plasship_orf_params *par, plasship_seqdb **out_orfs, plasship_orfhdr **out_hdr, plasship_orf_stats *stats);
+int translateNucsGencode(plasship_ctx *ctx, const plasship_seqdb *orfs, const plasship_orfhdr *hdr, const plasship_translate_params *par, plasship_seqdb **out_aa, plasship_orf_stats *stats);
 // The flagged records of a CSR list (scan.hip): outRecs = the records with dKeep[i] != 0, in input order; outQoff[q] = the number of kept
 // records before dInQoff[q], q in [0, nQ].  recBytes is 16 (CandHit) or 64 (AlnRec).  nKept is what the caller counted: it sizes outRecs
 // (max(nKept, 1) records) and is checked against the scan's total.  Waits for the stream exactly once, at its end (on an

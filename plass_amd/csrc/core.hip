@@ -335,7 +335,7 @@ extern "C" void plasship_ctx_destroy(plasship_ctx *ctx) {
     // trimmed: a slab is returned to the driver only when nothing in it is live (round 4: the cache lines kept the 250 GB slab of a
     // closed context alive, and the next process on the GPU — bench.py's fused-driver child, a test's subprocess — ran out of memory)
     { std::unique_lock<std::mutex> lk(g_reserveMu); g_reserveCv.wait(lk, [] { return g_reserving == 0; }); }      // (a reservation in flight must land first)
-    ctx->kmCache.lines.release(); ctx->d_cmpCache.release(); ctx->d_ambKeys.release(); ctx->d_ambVals.release();
+    ctx->kmCache.lines.release(); ctx->d_cmpCache.release(); ctx->d_ambKeys.release(); ctx->d_ambVals.release(); ctx->gencodeTables.clear();
     if (ctx->stream) { poolForgetStream(ctx->stream); (void) hipStreamDestroy(ctx->stream); }
     bool last; { std::lock_guard<std::mutex> g(g_poolMu); last = (--g_ctxCount <= 0); }
     if (last) {

@@ -72,8 +72,63 @@ int baseCodeHost(unsigned char ch) {
     }
     return tab[ch];
 }
-char codonResidueHost(int i, int j, int k) {                     // TranslateNucl.h:392-480, canonical code
-    static const char *ncbieaa = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+// The genetic codes of NCBI's gc.prt that the reference accepts (TranslateNucl.h:82-108: ids 1-6, 9-16, 21-31), each as its residue string and
+// its start / stop string over the 64 codons in T, C, A, G order (index 16 * first + 4 * second + third).
+struct GenCodeStrings { int id; const char *residues, *starts; };
+const GenCodeStrings kGenCodes[] = {
+    {1,  "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Standard
+         "---M------**--*----M---------------M----------------------------"},
+    {2,  "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSS**VVVVAAAADDEEGGGG",      // Vertebrate Mitochondrial
+         "----------**--------------------MMMM----------**---M------------"},
+    {3,  "FFLLSSSSYY**CCWWTTTTPPPPHHQQRRRRIIMMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Yeast Mitochondrial
+         "----------**----------------------MM----------------------------"},
+    {4,  "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Mold, Protozoan and Coelenterate Mitochondrial; Mycoplasma; Spiroplasma
+         "--MM------**-------M------------MMMM---------------M------------"},
+    {5,  "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSSSVVVVAAAADDEEGGGG",      // Invertebrate Mitochondrial
+         "---M------**--------------------MMMM---------------M------------"},
+    {6,  "FFLLSSSSYYQQCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Ciliate, Dasycladacean and Hexamita Nuclear
+         "--------------*--------------------M----------------------------"},
+    {9,  "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG",      // Echinoderm and Flatworm Mitochondrial
+         "----------**-----------------------M---------------M------------"},
+    {10, "FFLLSSSSYY**CCCWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Euplotid Nuclear
+         "----------**-----------------------M----------------------------"},
+    {11, "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Bacterial, Archaeal and Plant Plastid
+         "---M------**--*----M------------MMMM---------------M------------"},
+    {12, "FFLLSSSSYY**CC*WLLLSPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Alternative Yeast Nuclear
+         "----------**--*----M---------------M----------------------------"},
+    {13, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSSGGVVVVAAAADDEEGGGG",      // Ascidian Mitochondrial
+         "---M------**----------------------MM---------------M------------"},
+    {14, "FFLLSSSSYYY*CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNNKSSSSVVVVAAAADDEEGGGG",      // Alternative Flatworm Mitochondrial
+         "-----------*-----------------------M----------------------------"},
+    {15, "FFLLSSSSYY*QCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Blepharisma Macronuclear
+         "----------*---*--------------------M----------------------------"},
+    {16, "FFLLSSSSYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Chlorophycean Mitochondrial
+         "----------*---*--------------------M----------------------------"},
+    {21, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNNKSSSSVVVVAAAADDEEGGGG",      // Trematode Mitochondrial
+         "----------**-----------------------M---------------M------------"},
+    {22, "FFLLSS*SYY*LCC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Scenedesmus obliquus Mitochondrial
+         "------*---*---*--------------------M----------------------------"},
+    {23, "FF*LSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Thraustochytrium Mitochondrial
+         "--*-------**--*-----------------M--M---------------M------------"},
+    {24, "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSSKVVVVAAAADDEEGGGG",      // Pterobranchia Mitochondrial (Rhabdopleuridae)
+         "---M------**-------M---------------M---------------M------------"},
+    {25, "FFLLSSSSYY**CCGWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Candidate Division SR1 and Gracilibacteria
+         "---M------**-----------------------M---------------M------------"},
+    {26, "FFLLSSSSYY**CC*WLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Pachysolen tannophilus Nuclear
+         "----------**--*----M---------------M----------------------------"},
+    {27, "FFLLSSSSYYQQCCWWLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Karyorelict Nuclear
+         "--------------*--------------------M----------------------------"},
+    {28, "FFLLSSSSYYQQCCWWLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Condylostoma Nuclear
+         "----------**--*--------------------M----------------------------"},
+    {29, "FFLLSSSSYYYYCC*WLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Mesodinium Nuclear
+         "--------------*--------------------M----------------------------"},
+    {30, "FFLLSSSSYYEECC*WLLLAPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Peritrich Nuclear
+         "--------------*--------------------M----------------------------"},
+    {31, "FFLLSSSSYYEECCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",      // Blastocrithidia Nuclear
+         "----------**-----------------------M----------------------------"},
+};
+const GenCodeStrings *genCodeOf(int id) { for (const GenCodeStrings &g : kGenCodes) if (g.id == id) return &g; return nullptr; }
+char codonResidueHost(const char *ncbieaa, int i, int j, int k) {  // TranslateNucl.h:392-480
     static const int expansions[4] = {1, 2, 4, 8};               // A, C, G, T
     static const int codonIdx[9] = {0, 2, 1, 0, 3, 0, 0, 0, 0};  // T = 0, C = 1, A = 2, G = 3
     char aa = '\0';
@@ -91,18 +146,18 @@ char codonResidueHost(int i, int j, int k) {                     // TranslateNuc
             } } }
     return aa == '\0' ? 'X' : aa;
 }
+void fillOrfTables(OrfTables &t, const char *ncbieaa) {
+    for (int c = 0; c < 256; c++) {
+        const char r = iupacComplementHost((char) c);
+        t.comp[c] = (unsigned char) (r == '.' ? 'N' : r);
+        t.gap[c] = (unsigned char) ((c == 'N' || r == '.') ? 1 : 0);
+        t.base[c] = (unsigned char) baseCodeHost((unsigned char) c);
+    }
+    for (int i = 0; i < 16; i++) for (int j = 0; j < 16; j++) for (int k = 0; k < 16; k++) t.aa[(i << 8) | (j << 4) | k] = (unsigned char) codonResidueHost(ncbieaa, i, j, k);
+}
 const OrfTables &orfTables() {
     static OrfTables t; static bool init = false;
-    if (!init) {
-        for (int c = 0; c < 256; c++) {
-            const char r = iupacComplementHost((char) c);
-            t.comp[c] = (unsigned char) (r == '.' ? 'N' : r);
-            t.gap[c] = (unsigned char) ((c == 'N' || r == '.') ? 1 : 0);
-            t.base[c] = (unsigned char) baseCodeHost((unsigned char) c);
-        }
-        for (int i = 0; i < 16; i++) for (int j = 0; j < 16; j++) for (int k = 0; k < 16; k++) t.aa[(i << 8) | (j << 4) | k] = (unsigned char) codonResidueHost(i, j, k);
-        init = true;
-    }
+    if (!init) { fillOrfTables(t, kGenCodes[0].residues); init = true; }
     return t;
 }
 }  // namespace
@@ -119,6 +174,7 @@ struct OrfArgs {
     uint32_t *cnt; uint32_t *bytes;
     const uint64_t *orfBase, *byteBase;
     char *outData; uint64_t *outOff; uint32_t *outLen, *outKey; OrfInfo *info;
+    uint64_t stopMask, startMask;    // orfKernel<PASS, true> only: bit c = codon c (T, C, A, G order) ends / starts an ORF
 };
 
 // raw letters of one strand as Orf::setSequence leaves them, CHAR_MAX behind the end; eight bytes per global load
@@ -137,7 +193,10 @@ struct StrandReader {
     }
 };
 
-template <int PASS>
+// MASKS false: the standard code with ATG as the one start, compared letter by letter (what plasship_extract_orfs runs); true: stops and starts
+// of any genetic code as two 64-bit sets over the codons of exact letters (Orf.cpp:55-91: the reference compares the three upper-cased letters
+// with its lists of up to eight codons, so a codon with any other letter is in neither)
+template <int PASS, bool MASKS>
 __global__ __launch_bounds__(256) void orfKernel(OrfArgs a) {
     __shared__ unsigned char sComp[256], sGap[256], sBase[256];
     for (int i = threadIdx.x; i < 256; i += 256) { sComp[i] = a.comp[i]; sGap[i] = a.gap[i]; sBase[i] = a.base[i]; }
@@ -166,8 +225,17 @@ __global__ __launch_bounds__(256) void orfKernel(OrfArgs a) {
                 if (frames & (1u << frame)) {
                     const bool thisIncomplete = w[0] == CHAR_MAX || w[1] == CHAR_MAX || w[2] == CHAR_MAX;
                     const bool isLast = !thisIncomplete && (w[3] == CHAR_MAX || w[4] == CHAR_MAX || w[5] == CHAR_MAX);
-                    const bool isStart = w[0] == 'A' && w[1] == 'T' && w[2] == 'G';                 // --use-all-table-starts 0
-                    const bool stop = w[0] == 'T' && ((w[1] == 'A' && (w[2] == 'A' || w[2] == 'G')) || (w[1] == 'G' && w[2] == 'A'));   // table 1
+                    bool isStart, stop;
+                    if constexpr (MASKS) {
+                        auto tcag = [](unsigned char c) { return c == 'T' ? 0u : c == 'C' ? 1u : c == 'A' ? 2u : c == 'G' ? 3u : 64u; };    // 64: not a letter of a codon
+                        const uint32_t codon = 16u * tcag(w[0]) + 4u * tcag(w[1]) + tcag(w[2]);
+                        const bool exact = codon < 64u;
+                        isStart = exact && ((a.startMask >> (codon & 63u)) & 1ull);
+                        stop = exact && ((a.stopMask >> (codon & 63u)) & 1ull);
+                    } else {
+                        isStart = w[0] == 'A' && w[1] == 'T' && w[2] == 'G';                 // --use-all-table-starts 0
+                        stop = w[0] == 'T' && ((w[1] == 'A' && (w[2] == 'A' || w[2] == 'G')) || (w[1] == 'G' && w[2] == 'A'));   // table 1
+                    }
                     // state of this frame (indexing registers by a runtime frame would spill: select explicitly)
                     bool in = frame == 0 ? inside[0] : (frame == 1 ? inside[1] : inside[2]);
                     bool hs = frame == 0 ? hasStart[0] : (frame == 1 ? hasStart[1] : hasStart[2]);
@@ -347,36 +415,58 @@ static int finishSeqdb(plasship_ctx *ctx, plasship_seqdb *o, size_t n, uint64_t 
 }  // namespace plasship
 using namespace plasship;
 
-static int uploadTables(plasship_ctx *ctx, DevBuf &d, const unsigned char **comp, const unsigned char **gap, const unsigned char **base, const unsigned char **aa) {
-    const OrfTables &t = orfTables();
-    if (d.alloc(sizeof(OrfTables)) != hipSuccess) { setError("out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    PH_CHECK(hipMemcpyAsync(d.p, &t, sizeof(OrfTables), hipMemcpyHostToDevice, ctx->stream));
-    const unsigned char *p = d.as<unsigned char>();
+// gencode == nullptr: the standard code, uploaded into `d` for this call (the narrow entry points, as ever); otherwise that code's tables, uploaded
+// once per (context, table) and kept in ctx->gencodeTables
+static int uploadTables(plasship_ctx *ctx, DevBuf &d, const GenCodeStrings *gencode, const unsigned char **comp, const unsigned char **gap, const unsigned char **base, const unsigned char **aa) {
+    const unsigned char *p;
+    if (!gencode) {
+        const OrfTables &t = orfTables();
+        if (d.alloc(sizeof(OrfTables)) != hipSuccess) { setError("out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        PH_CHECK(hipMemcpyAsync(d.p, &t, sizeof(OrfTables), hipMemcpyHostToDevice, ctx->stream));
+        p = d.as<unsigned char>();
+    } else {
+        DevBuf &c = ctx->gencodeTables[gencode->id];
+        if (!c.p) {
+            OrfTables t; fillOrfTables(t, gencode->residues);
+            if (c.allocLong(sizeof(OrfTables)) != hipSuccess) { setError("out of device memory"); return PLASSHIP_ERR_DEVICE; }
+            const hipError_t e = hipMemcpy(c.p, &t, sizeof(OrfTables), hipMemcpyHostToDevice);      // (t is a local: the copy is complete on return)
+            if (e != hipSuccess) { c.release(); PH_CHECK(e); }
+        }
+        p = c.as<unsigned char>();
+    }
     *comp = p + offsetof(OrfTables, comp); *gap = p + offsetof(OrfTables, gap); *base = p + offsetof(OrfTables, base); *aa = p + offsetof(OrfTables, aa);
     return PLASSHIP_OK;
 }
 
-extern "C" int plasship_extract_orfs(plasship_ctx *ctx, const plasship_seqdb *reads, const plasship_orf_params *par, plasship_seqdb **out_orfs,
-                                     plasship_orfhdr **out_hdr, plasship_orf_stats *stats) {
-    if (!ctx || !reads || !par || !out_orfs) { setError("plasship_extract_orfs: bad argument"); return PLASSHIP_ERR_ARG; }
-    if (reads->dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { setError("plasship_extract_orfs: needs a nucleotide sequence DB"); return PLASSHIP_ERR_ARG; }
-    if (par->translation_table != 1 || par->use_all_table_starts) { setError("plasship_extract_orfs: only --translation-table 1 --use-all-table-starts 0 are supported"); return PLASSHIP_ERR_UNSUPPORTED; }
+// the sets of codons that end and that start an ORF (Orf.cpp:55-91): the stops are the codons TranslateNucl::initTranslationTable collects while it
+// fills its residue table, i.e. the '*' of the RESIDUE string (TranslateNucl.h:429-436) - a code whose residue string has none (27, 28, 31) ends no
+// ORF, whatever its start / stop string says; the starts are ATG, or with --use-all-table-starts the 'M' of the start / stop string (TranslateNucl.h:454-463)
+static void codonMasks(const GenCodeStrings &g, bool allStarts, uint64_t *stopMask, uint64_t *startMask) {
+    uint64_t stop = 0, start = 0;
+    for (int c = 0; c < 64; c++) { if (g.residues[c] == '*') stop |= 1ull << c; if (g.starts[c] == 'M') start |= 1ull << c; }
+    *stopMask = stop; *startMask = allStarts ? start : 1ull << 35;       // ATG: 16 * 2 + 4 * 0 + 3
+}
+// gencode == nullptr: --translation-table 1 --use-all-table-starts 0 through orfKernel<PASS, false> (plasship_extract_orfs)
+static int extractOrfs(const char *fn, plasship_ctx *ctx, const plasship_seqdb *reads, const plasship_orf_params *par, const GenCodeStrings *gencode, plasship_seqdb **out_orfs,
+                       plasship_orfhdr **out_hdr, plasship_orf_stats *stats) {
+    const std::string what(fn);
     if (par->orf_start_mode == 1 && par->contig_start_mode < 2) {                                   // extractorfs.cpp:38-41
         setError("Parameter combination is illegal, orf-start-mode 1 can only go with contig-start-mode 2"); return PLASSHIP_ERR_ARG;
     }
     if (par->orf_start_mode < 0 || par->orf_start_mode > 2 || par->min_length < 0 || par->max_length < 0 || par->max_gaps < 0 ||
-        (par->forward_frames & ~7) || (par->reverse_frames & ~7) || (par->translate && par->max_seq_len == 0)) { setError("plasship_extract_orfs: bad parameter"); return PLASSHIP_ERR_ARG; }
+        (par->forward_frames & ~7) || (par->reverse_frames & ~7) || (par->translate && par->max_seq_len == 0)) { setError(what + ": bad parameter"); return PLASSHIP_ERR_ARG; }
     PH_ENTER(ctx);
     hipStream_t st = ctx->stream;
     const uint32_t N = (uint32_t) reads->n;
     const uint64_t nSlots = 2ull * N;
-    if (nSlots >= 0xFFFFFFFFull) { setError("plasship_extract_orfs: too many sequences"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (nSlots >= 0xFFFFFFFFull) { setError(what + ": too many sequences"); return PLASSHIP_ERR_UNSUPPORTED; }
     DevBuf dTab, dCnt, dBytes, dOrfBase, dByteBase, dTmp;
     const size_t tmpBytes = exclusiveScanTmpBytes((size_t) nSlots + 2);
     OrfArgs a; memset(&a, 0, sizeof(a));
-    int rc = uploadTables(ctx, dTab, &a.comp, &a.gap, &a.base, &a.aa); if (rc) return rc;
+    int rc = uploadTables(ctx, dTab, gencode, &a.comp, &a.gap, &a.base, &a.aa); if (rc) return rc;
+    if (gencode) codonMasks(*gencode, par->use_all_table_starts != 0, &a.stopMask, &a.startMask);
     if (dCnt.alloc((nSlots + 1) * 4) != hipSuccess || dBytes.alloc((nSlots + 1) * 4) != hipSuccess || dOrfBase.alloc((nSlots + 2) * 8) != hipSuccess ||
-        dByteBase.alloc((nSlots + 2) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess) { setError("plasship_extract_orfs: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        dByteBase.alloc((nSlots + 2) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess) { setError(what + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
     a.s = reads->view(); a.key = reads->d_key.as<uint32_t>();
     a.minLength = (uint32_t) par->min_length; a.maxLength = (uint32_t) par->max_length; a.maxGaps = (uint32_t) par->max_gaps;
     a.contigStartMode = par->contig_start_mode; a.contigEndMode = par->contig_end_mode; a.orfStartMode = par->orf_start_mode;
@@ -385,25 +475,31 @@ extern "C" int plasship_extract_orfs(plasship_ctx *ctx, const plasship_seqdb *re
     a.cnt = dCnt.as<uint32_t>(); a.bytes = dBytes.as<uint32_t>();
     PH_CHECK(hipEventRecord(ctx->ev[0], st));
     const unsigned grid = flatGrid(nSlots, ctx->numCU);
-    if (nSlots) hipLaunchKernelGGL((orfKernel<0>), dim3(grid), dim3(256), 0, st, a);
+    if (nSlots) {
+        if (gencode) hipLaunchKernelGGL((orfKernel<0, true>), dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((orfKernel<0, false>), dim3(grid), dim3(256), 0, st, a);
+    }
     if (exclusiveScanU32(st, dCnt.as<uint32_t>(), dOrfBase.as<uint64_t>(), nSlots, dTmp.p, tmpBytes) ||
-        exclusiveScanU32(st, dBytes.as<uint32_t>(), dByteBase.as<uint64_t>(), nSlots, dTmp.p, tmpBytes)) { setError("plasship_extract_orfs: scan failed"); return PLASSHIP_ERR_DEVICE; }
+        exclusiveScanU32(st, dBytes.as<uint32_t>(), dByteBase.as<uint64_t>(), nSlots, dTmp.p, tmpBytes)) { setError(what + ": scan failed"); return PLASSHIP_ERR_DEVICE; }
     uint64_t tot[2] = {0, 0};
     PH_CHECK(hipMemcpyAsync(&tot[0], dOrfBase.as<uint64_t>() + nSlots, 8, hipMemcpyDeviceToHost, st));
     PH_CHECK(hipMemcpyAsync(&tot[1], dByteBase.as<uint64_t>() + nSlots, 8, hipMemcpyDeviceToHost, st));
     PH_CHECK(plasship::streamSync(st));
     PH_CHECK(hipGetLastError());
     const uint64_t M = tot[0], dataBytes = tot[1];
-    if (M >= 0xFFFFFFFFull) { setError("plasship_extract_orfs: too many ORFs"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (M >= 0xFFFFFFFFull) { setError(what + ": too many ORFs"); return PLASSHIP_ERR_UNSUPPORTED; }
     std::unique_ptr<plasship_seqdb> o(new plasship_seqdb());
     std::unique_ptr<plasship_orfhdr> h(new plasship_orfhdr());
     if (o->d_data.allocLong(dataBytes + 64) != hipSuccess || o->d_off.allocLong((M + 1) * 8) != hipSuccess || o->d_len.allocLong((M + 1) * 4) != hipSuccess ||
-        o->d_key.allocLong((M + 1) * 4) != hipSuccess || h->d_info.alloc((M + 1) * sizeof(OrfInfo)) != hipSuccess) { setError("plasship_extract_orfs: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        o->d_key.allocLong((M + 1) * 4) != hipSuccess || h->d_info.alloc((M + 1) * sizeof(OrfInfo)) != hipSuccess) { setError(what + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
     PH_CHECK(hipMemsetAsync((char *) o->d_data.p + dataBytes, 0, 64, st));
     PH_CHECK(hipMemcpyAsync(o->d_off.as<uint64_t>() + M, &dataBytes, 8, hipMemcpyHostToDevice, st));
     a.orfBase = dOrfBase.as<uint64_t>(); a.byteBase = dByteBase.as<uint64_t>();
     a.outData = o->d_data.as<char>(); a.outOff = o->d_off.as<uint64_t>(); a.outLen = o->d_len.as<uint32_t>(); a.outKey = o->d_key.as<uint32_t>(); a.info = h->d_info.as<OrfInfo>();
-    if (nSlots) hipLaunchKernelGGL((orfKernel<1>), dim3(grid), dim3(256), 0, st, a);
+    if (nSlots) {
+        if (gencode) hipLaunchKernelGGL((orfKernel<1, true>), dim3(grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((orfKernel<1, false>), dim3(grid), dim3(256), 0, st, a);
+    }
     PH_CHECK(hipEventRecord(ctx->ev[1], st));
     rc = finishSeqdb(ctx, o.get(), (size_t) M, dataBytes, par->translate ? PLASSHIP_DBTYPE_AMINO_ACIDS : PLASSHIP_DBTYPE_NUCLEOTIDES, o->d_len.as<uint32_t>());
     if (rc) return rc;
@@ -419,15 +515,21 @@ extern "C" int plasship_extract_orfs(plasship_ctx *ctx, const plasship_seqdb *re
     return PLASSHIP_OK;
 }
 
-extern "C" int plasship_translate_nucs(plasship_ctx *ctx, const plasship_seqdb *orfs, const plasship_orfhdr *hdr, const plasship_translate_params *par,
-                                       plasship_seqdb **out_aa, plasship_orf_stats *stats) {
-    if (!ctx || !orfs || !par || !out_aa) { setError("plasship_translate_nucs: bad argument"); return PLASSHIP_ERR_ARG; }
-    if (orfs->dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { setError("plasship_translate_nucs: needs a nucleotide sequence DB"); return PLASSHIP_ERR_ARG; }
-    if (par->translation_table != 1) { setError("plasship_translate_nucs: only --translation-table 1 is supported"); return PLASSHIP_ERR_UNSUPPORTED; }
-    if (par->max_seq_len == 0) { setError("plasship_translate_nucs: bad --max-seq-len"); return PLASSHIP_ERR_ARG; }
-    if (par->add_orf_stop && (!hdr || hdr->n != orfs->n)) { setError("plasship_translate_nucs: --add-orf-stop needs the header DB of the ORF DB (same keys)"); return PLASSHIP_ERR_ARG; }
+extern "C" int plasship_extract_orfs(plasship_ctx *ctx, const plasship_seqdb *reads, const plasship_orf_params *par, plasship_seqdb **out_orfs,
+                                     plasship_orfhdr **out_hdr, plasship_orf_stats *stats) {
+    if (!ctx || !reads || !par || !out_orfs) { setError("plasship_extract_orfs: bad argument"); return PLASSHIP_ERR_ARG; }
+    if (reads->dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { setError("plasship_extract_orfs: needs a nucleotide sequence DB"); return PLASSHIP_ERR_ARG; }
+    if (par->translation_table != 1 || par->use_all_table_starts) { setError("plasship_extract_orfs: only --translation-table 1 --use-all-table-starts 0 are supported"); return PLASSHIP_ERR_UNSUPPORTED; }
+    return extractOrfs("plasship_extract_orfs", ctx, reads, par, nullptr, out_orfs, out_hdr, stats);
+}
+
+static int translateNucs(const char *fn, plasship_ctx *ctx, const plasship_seqdb *orfs, const plasship_orfhdr *hdr, const plasship_translate_params *par, const GenCodeStrings *gencode,
+                         plasship_seqdb **out_aa, plasship_orf_stats *stats) {
+    const std::string what(fn);
+    if (par->max_seq_len == 0) { setError(what + ": bad --max-seq-len"); return PLASSHIP_ERR_ARG; }
+    if (par->add_orf_stop && (!hdr || hdr->n != orfs->n)) { setError(what + ": --add-orf-stop needs the header DB of the ORF DB (same keys)"); return PLASSHIP_ERR_ARG; }
     // Orf::parseOrfHeader leaves the two flags uninitialised when a header is not in ORF format (Orf.cpp:401-405): no defined result to reproduce
-    if (par->add_orf_stop && hdr->nUnparsable) { setError("plasship_translate_nucs: --add-orf-stop with headers that are not ORF headers is undefined in the reference; refused"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (par->add_orf_stop && hdr->nUnparsable) { setError(what + ": --add-orf-stop with headers that are not ORF headers is undefined in the reference; refused"); return PLASSHIP_ERR_UNSUPPORTED; }
     PH_ENTER(ctx);
     hipStream_t st = ctx->stream;
     const uint32_t N = (uint32_t) orfs->n;
@@ -435,14 +537,14 @@ extern "C" int plasship_translate_nucs(plasship_ctx *ctx, const plasship_seqdb *
     const size_t tmpBytes = exclusiveScanTmpBytes((size_t) N + 2);
     TransArgs a; memset(&a, 0, sizeof(a));
     const unsigned char *comp, *gap;
-    int rc = uploadTables(ctx, dTab, &comp, &gap, &a.base, &a.aa); if (rc) return rc;
+    int rc = uploadTables(ctx, dTab, gencode, &comp, &gap, &a.base, &a.aa); if (rc) return rc;
     if (dBytes.alloc(((size_t) N + 1) * 4) != hipSuccess || dFlag.alloc(((size_t) N + 1) * 4) != hipSuccess || dByteBase.alloc(((size_t) N + 2) * 8) != hipSuccess ||
-        dIdxBase.alloc(((size_t) N + 2) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess) { setError("plasship_translate_nucs: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        dIdxBase.alloc(((size_t) N + 2) * 8) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess) { setError(what + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
     if (par->add_orf_stop && N) {                  // the header of ORF i must be the header OF ORF i (translatenucs looks it up by key)
-        DevBuf dHK; if (dHK.alloc((size_t) N * 4) != hipSuccess) { setError("plasship_translate_nucs: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        DevBuf dHK; if (dHK.alloc((size_t) N * 4) != hipSuccess) { setError(what + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
         PH_CHECK(hipMemcpy2DAsync(dHK.p, 4, hdr->d_info.p, sizeof(OrfInfo), 4, N, hipMemcpyDeviceToDevice, st));      // column `key`
         bool differ = false; rc = deviceKeysDiffer(ctx, dHK.as<uint32_t>(), orfs->d_key.as<uint32_t>(), N, &differ); if (rc) return rc;
-        if (differ) { setError("plasship_translate_nucs: header DB and ORF DB hold different keys"); return PLASSHIP_ERR_ARG; }
+        if (differ) { setError(what + ": header DB and ORF DB hold different keys"); return PLASSHIP_ERR_ARG; }
     }
     a.s = orfs->view(); a.key = orfs->d_key.as<uint32_t>(); a.info = hdr ? hdr->d_info.as<OrfInfo>() : nullptr;
     a.addOrfStop = par->add_orf_stop ? 1 : 0; a.maxSeqLen = par->max_seq_len; a.bytes = dBytes.as<uint32_t>();
@@ -453,7 +555,7 @@ extern "C" int plasship_translate_nucs(plasship_ctx *ctx, const plasship_seqdb *
         hipLaunchKernelGGL(nonZeroKernel, dim3(grid), dim3(256), 0, st, dBytes.as<uint32_t>(), N, dFlag.as<uint32_t>());
     }
     if (exclusiveScanU32(st, dBytes.as<uint32_t>(), dByteBase.as<uint64_t>(), N, dTmp.p, tmpBytes) ||
-        exclusiveScanU32(st, dFlag.as<uint32_t>(), dIdxBase.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError("plasship_translate_nucs: scan failed"); return PLASSHIP_ERR_DEVICE; }
+        exclusiveScanU32(st, dFlag.as<uint32_t>(), dIdxBase.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError(what + ": scan failed"); return PLASSHIP_ERR_DEVICE; }
     uint64_t tot[2] = {0, 0};
     PH_CHECK(hipMemcpyAsync(&tot[0], dIdxBase.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
     PH_CHECK(hipMemcpyAsync(&tot[1], dByteBase.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
@@ -462,7 +564,7 @@ extern "C" int plasship_translate_nucs(plasship_ctx *ctx, const plasship_seqdb *
     const uint64_t M = tot[0], dataBytes = tot[1];
     std::unique_ptr<plasship_seqdb> o(new plasship_seqdb());
     if (o->d_data.allocLong(dataBytes + 64) != hipSuccess || o->d_off.allocLong((M + 1) * 8) != hipSuccess || o->d_len.allocLong((M + 1) * 4) != hipSuccess ||
-        o->d_key.allocLong((M + 1) * 4) != hipSuccess) { setError("plasship_translate_nucs: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        o->d_key.allocLong((M + 1) * 4) != hipSuccess) { setError(what + ": out of device memory"); return PLASSHIP_ERR_DEVICE; }
     PH_CHECK(hipMemsetAsync((char *) o->d_data.p + dataBytes, 0, 64, st));
     PH_CHECK(hipMemcpyAsync(o->d_off.as<uint64_t>() + M, &dataBytes, 8, hipMemcpyHostToDevice, st));
     a.byteBase = dByteBase.as<uint64_t>(); a.idxBase = dIdxBase.as<uint64_t>();
@@ -480,6 +582,44 @@ extern "C" int plasship_translate_nucs(plasship_ctx *ctx, const plasship_seqdb *
     *out_aa = o.release();
     return PLASSHIP_OK;
 }
+
+extern "C" int plasship_translate_nucs(plasship_ctx *ctx, const plasship_seqdb *orfs, const plasship_orfhdr *hdr, const plasship_translate_params *par,
+                                       plasship_seqdb **out_aa, plasship_orf_stats *stats) {
+    if (!ctx || !orfs || !par || !out_aa) { setError("plasship_translate_nucs: bad argument"); return PLASSHIP_ERR_ARG; }
+    if (orfs->dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { setError("plasship_translate_nucs: needs a nucleotide sequence DB"); return PLASSHIP_ERR_ARG; }
+    if (par->translation_table != 1) { setError("plasship_translate_nucs: only --translation-table 1 is supported"); return PLASSHIP_ERR_UNSUPPORTED; }
+    return translateNucs("plasship_translate_nucs", ctx, orfs, hdr, par, nullptr, out_aa, stats);
+}
+
+// ---- any genetic code: what libplasship_gencode.so exports as plasship_extract_orfs_gc / plasship_translate_nucs_gc / plasship_gencode_info
+//      (include/plasship_ext/gencode.h).  An id the reference does not know ("Invalid translation table selected!", TranslateNucl.h:242-245) is an
+//      argument error here. ----
+namespace plasship {
+int gencodeInfo(int table, char residues[65], char starts[65]) {
+    const GenCodeStrings *g = genCodeOf(table);
+    if (!g) { setError("plasship_gencode_info: invalid translation table " + std::to_string(table)); return PLASSHIP_ERR_ARG; }
+    if (residues) memcpy(residues, g->residues, 65);
+    if (starts) memcpy(starts, g->starts, 65);
+    return PLASSHIP_OK;
+}
+int extractOrfsGencode(plasship_ctx *ctx, const plasship_seqdb *reads, const plasship_orf_params *par, plasship_seqdb **out_orfs, plasship_orfhdr **out_hdr, plasship_orf_stats *stats) {
+    if (!ctx || !reads || !par || !out_orfs) { setError("plasship_extract_orfs_gc: bad argument"); return PLASSHIP_ERR_ARG; }
+    if (reads->dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { setError("plasship_extract_orfs_gc: needs a nucleotide sequence DB"); return PLASSHIP_ERR_ARG; }
+    const GenCodeStrings *g = genCodeOf(par->translation_table);
+    if (!g) { setError("plasship_extract_orfs_gc: invalid translation table " + std::to_string(par->translation_table)); return PLASSHIP_ERR_ARG; }
+    // the standard code with ATG alone is what orfKernel<PASS, false> states letter by letter: the same kernels as plasship_extract_orfs
+    if (g->id == 1 && !par->use_all_table_starts) g = nullptr;
+    return extractOrfs("plasship_extract_orfs_gc", ctx, reads, par, g, out_orfs, out_hdr, stats);
+}
+int translateNucsGencode(plasship_ctx *ctx, const plasship_seqdb *orfs, const plasship_orfhdr *hdr, const plasship_translate_params *par, plasship_seqdb **out_aa, plasship_orf_stats *stats) {
+    if (!ctx || !orfs || !par || !out_aa) { setError("plasship_translate_nucs_gc: bad argument"); return PLASSHIP_ERR_ARG; }
+    if (orfs->dbtype != PLASSHIP_DBTYPE_NUCLEOTIDES) { setError("plasship_translate_nucs_gc: needs a nucleotide sequence DB"); return PLASSHIP_ERR_ARG; }
+    const GenCodeStrings *g = genCodeOf(par->translation_table);
+    if (!g) { setError("plasship_translate_nucs_gc: invalid translation table " + std::to_string(par->translation_table)); return PLASSHIP_ERR_ARG; }
+    if (g->id == 1) g = nullptr;
+    return translateNucs("plasship_translate_nucs_gc", ctx, orfs, hdr, par, g, out_aa, stats);
+}
+}  // namespace plasship
 
 // concatdbs <A> <B> <out> (DBConcat.cpp:63-135 with preserveKeysA, !preserveKeysB, DBConcat.cpp:379-382): A's entries with their keys,
 // followed by B's with keys max(keyA) + 1 + i where i runs over B in DATA FILE order (B is opened LINEAR_ACCCESS: DBConcat.cpp:46-47,
