@@ -127,6 +127,15 @@ struct AlnRec {
 };
 constexpr int32_t ALN_SELF_PENDING = 3;
 
+// the selection parameters of one plasship_kmermatch call (host only): what two calls must share for the later one to reuse what the
+// earlier one selected.  alph: the alphabet the k-mer index is built over (5 for nucleotides); lng: the 24-byte record layout
+struct KmSelect {
+    int k = 0, alph = 0, kps = 0; float scale = 0; int ignoreMulti = 0, hashShift = 0; bool lng = false;
+    bool operator==(const KmSelect &o) const {
+        return k == o.k && alph == o.alph && kps == o.kps && scale == o.scale && ignoreMulti == o.ignoreMulti && hashShift == o.hashShift && lng == o.lng;
+    }
+};
+
 }  // namespace plasship
 
 struct plasship_ctx {
@@ -156,15 +165,15 @@ struct plasship_ctx {
     // sequence its DB inherited unchanged from that call's DB when the selection parameters (hash seed included) are the same
     struct KmCache {
         plasship::DevBuf lines; uint64_t n = 0, gen = 0; bool valid = false, seenEligible = false;      // seenEligible: an earlier call on this context could have used lines (they are allocated from the second such call on, or for a derived DB)
-        int k = 0, alph = 0, kps = 0, ignoreMulti = 0, hashShift = 0;
+        plasship::KmSelect sel;         // of the call that wrote the lines
     } kmCache;
     // kmermatcher's position cache of nucleotide runs (kmermatch_extract.hpp section 2d): per record slot of the LAST nucleotide
     // plasship_kmermatch call on this context the window position it selected (the identity slot: the count), that call's slot offsets
     // and identity hashes.  `gen` (that call's DB) is the ANCHOR: every DB buildOutputDB derives from it, directly or through other derived
     // DBs, carries per entry the id it had in the anchor (plasship_seqdb::d_origin) — entries may be dropped on the way.
     struct KmPosCache {
-        plasship::DevBuf pos, slotOff, idHash; uint64_t n = 0, gen = 0; bool valid = false, seen = false, lng = false;
-        int k = 0, kps = 0, ignoreMulti = 0, hashShift = 0; float scale = 0;
+        plasship::DevBuf pos, slotOff, idHash; uint64_t n = 0, gen = 0; bool valid = false, seen = false;
+        plasship::KmSelect sel;         // of the call that wrote the positions
     } kmPosCache;
     uint64_t kmermatchCalls = 0;       // plasship_kmermatch calls this context has seen (a second call suggests a chain: the caches are written from then on)
     // cyclecheck.hip: generation of the last "rest" DB plasship_cyclecheck made on this context (every entry of it is known not to be

@@ -46,12 +46,6 @@ using namespace plasship;
 // ---- host orchestration --------------------------------------------------------------------------------
 namespace {
 
-struct Timer {
-    plasship_ctx *ctx; int slot;
-    void start(int s) { slot = s; (void) hipEventRecord(ctx->ev[s], ctx->stream); }
-    float stop(int s2) { (void) hipEventRecord(ctx->ev[s2], ctx->stream); (void) hipEventSynchronize(ctx->ev[s2]); float ms = 0; (void) hipEventElapsedTime(&ms, ctx->ev[slot], ctx->ev[s2]); return ms; }
-};
-
 static inline unsigned gridFor(uint64_t n, unsigned block, unsigned cap = 65535u * 8) {
     uint64_t g = (n + block - 1) / block; if (g < 1) g = 1; if (g > cap) g = cap; return (unsigned) g;
 }
@@ -143,11 +137,6 @@ static LineGeo lineGeometry(uint64_t totalSlots, bool lng, int numCU, uint64_t s
         g.PL2 = 0xFFFFFFFFu; g.maxP2 = g.nb1; g.cap2 = g.cap1 + (uint64_t) g.nb1 * g.nb2;     // (sharded run: cap2 follows from what the exchange delivers)
     }
     return g;
-}
-// lines a range partition of `nRec` records in `nSeg` dense segments can need (level 1) and a second level on top of it
-static uint64_t repLevel1Cap(uint64_t nRec, uint64_t nSeg, uint32_t PL, uint32_t nb) {
-    const uint64_t lines = (nRec + RPL - 1) / RPL + nSeg;
-    return lines + (lines / PL + nSeg + 1) * (uint64_t) nb;
 }
 
 __global__ void arenaStartKernel(const uint32_t *__restrict__ lineBeg, uint32_t bpb, uint32_t gGrid, uint32_t nBuckets, uint64_t *__restrict__ arenaStart) {
@@ -268,7 +257,7 @@ static bool shardOwnerFiltered(int W) { const int m = tuneInt("SHARD_EXTRACT", 0
 
 constexpr int KM_RETRY_EARLY_OVERFLOW_CHECK = -1000;     // internal: kmermatchImpl is to be called again, waiting for the extraction's overflow count
 // What the line path hands to the run reduction
-struct LinesOut { void *triples = nullptr; uint64_t nTriples = 0, Nk = 0, Nm = 0; std::vector<int64_t> stalePos; uint32_t staleT = 0; float msSort1 = 0, msGroup = 0, msSort2 = 0, msPart = 0; int nPart = 1;
+struct LinesOut { void *triples = nullptr; uint64_t nTriples = 0, Nk = 0, Nm = 0; std::vector<int64_t> stalePos; uint32_t staleT = 0; float msPart = 0; int nPart = 1;
                   uint64_t exchangedRecordBytes = 0, exchangedTripleBytes = 0; };
 
 constexpr uint64_t HALO_SLACK = 1u << 16;
@@ -504,6 +493,21 @@ static int repSortLines(plasship_ctx *ctx, const void *in, const std::vector<std
 
 static void moveBuf(DevBuf &dst, DevBuf &src) { dst.release(); dst.p = src.p; dst.bytes = src.bytes; src.p = nullptr; src.bytes = 0; }
 
+// the slots of ctx->ev this file records: stage boundaries, read when the call is over (kmermatchStats) — nobody waits for the stream just
+// to time a stage.  EXTRACT_END is also where the hash partition (ms_sort1) begins, SORT2_END where the run reduction begins.
+enum KmEvent { KM_EV_BEGIN = 0, KM_EV_EXTRACT_END, KM_EV_SHORT_BEGIN, KM_EV_SHORT_END, KM_EV_WAVE_BEGIN, KM_EV_WAVE_END, KM_EV_PART_END, KM_EV_GROUP_END,
+               KM_EV_L1_BEGIN, KM_EV_L1_END, KM_EV_L2_BEGIN, KM_EV_L2_END, KM_EV_SORT2_BEGIN, KM_EV_SORT2_END, KM_EV_REDUCE_END };
+static float eventMs(plasship_ctx *ctx, KmEvent a, KmEvent b) { float v = 0; (void) hipEventElapsedTime(&v, ctx->ev[a], ctx->ev[b]); return v; }
+// NUCL: the globally smallest key (first-run quirk of the group kernel) from every rank's own
+static int allReduceMinKey(plasship_ctx *ctx, DevBuf &dMinKey) {
+    hipStream_t st = ctx->stream;
+    uint64_t mk = 0; PH_COPY_SYNC(st, &mk, dMinKey.p, 8, hipMemcpyDeviceToHost);
+    const int rc = commAllReduceMinU64(ctx, &mk, 1); if (rc) return rc;
+    PH_COPY_SYNC(st, dMinKey.p, &mk, 8, hipMemcpyHostToDevice);
+    return PLASSHIP_OK;
+}
+
+
 // extraction has filled dA (`total` record slots of this rank's sequences, sentinels in unused slots).  Buffers dA / dB hold geo.cap2
 // resp. geo.cap1 lines (single GPU) or geo.cap1 lines each (sharded run).
 // Sharded run (commOf(ctx) != nullptr; `totalAll` = slots of all ranks): the bucket geometry is that of the WHOLE run, rank r owns the
@@ -513,7 +517,7 @@ static void moveBuf(DevBuf &dst, DevBuf &src) { dst.release(); dst.p = src.p; ds
 // every rank first runs the whole rep sort on the grouped records of its own buckets — and the owner of a representative merges the
 // triples of all ranks with the same kernels (aggSortKernel<TRIPLES>).
 template <bool NUCL, bool LONG>
-static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_kmermatch_params *par, const LineGeo &geo, uint64_t total,
+static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_kmermatch_params *par, const LineGeo &geo,
                           DevBuf &dA, DevBuf &dB, const DevBuf &dSlotOff, const DevBuf &dKStats, const ExtractArgs &ea, int keyBits, LinesOut &res,
                           const uint32_t *dLateOverflow, bool filtered) {
     typedef Rec<LONG> R;
@@ -526,7 +530,7 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
     // stage boundaries are events read when the call is over (kmermatchImpl): nobody waits for the stream just to time a stage
     const int valueShift = std::max(0, keyBits - 11);         // VH_BINS = 2^11 monotone bins
     // ---- hash partition (replaces sort #1): level 1 over the slot array, level 2 over every level-1 bucket's line list ----
-    PH_CHECK(hipEventRecord(ctx->ev[1], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_EXTRACT_END], st));
     const uint32_t bLo = cm ? (uint32_t) ownedBegin(geo.nb1, rk, W) : 0u, bHi = cm ? (uint32_t) ownedBegin(geo.nb1, rk + 1, W) : geo.nb1;
     const uint32_t nbL = bHi - bLo;                           // level-1 buckets this rank groups (all of them on a single GPU)
     DevBuf dVHist, dMinKey, dTag1, dList1, dCnt1, dStart1, dCur1, dTag2, dList2, dPieces2, dNP2, dRegBeg, dRegEnd, dTot2, dFineBeg, dFineCnt;
@@ -548,20 +552,16 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
         a.key.shift = geo.b1 ? 64 - geo.b1 : 63; a.key.rangeBits = 0; a.key.repBase = 0;
         a.minKey = NUCL ? dMinKey.as<unsigned long long>() : nullptr; a.valueHist = dVHist.as<uint32_t>(); a.valueShift = valueShift;
         if (cm && filtered) { a.keepLo = bLo; a.keepHi = bHi; }      // every rank has extracted everything: keep the records of the own buckets
-        PH_CHECK(hipEventRecord(ctx->ev[8], st));
+        PH_CHECK(hipEventRecord(ctx->ev[KM_EV_L1_BEGIN], st));
         const int rc = launchLinePart<NUCL, LONG, KEY_HASH, false, true>(ctx, a, geo.nP1); if (rc) return rc;
-        PH_CHECK(hipEventRecord(ctx->ev[9], st));
+        PH_CHECK(hipEventRecord(ctx->ev[KM_EV_L1_END], st));
     }
     int rc = buildLineLists(ctx, "hash", dTag1.as<uint32_t>(), geo.cap1, geo.nb1, dCnt1.as<uint32_t>(), dStart1.as<uint32_t>(), dCur1.as<uint32_t>(), dList1.as<uint32_t>()); if (rc) return rc;
     // what level 2 (or, with a single level, the group kernel) reads: records, their line list, the list offsets of the nbL buckets
     void *l1Recs = dB.p; const uint32_t *l1List = dList1.as<uint32_t>(); const uint32_t *l1Start = dStart1.as<uint32_t>() + bLo; uint64_t l1Lines = geo.cap1;
     const uint32_t *l1Tags = dTag1.as<uint32_t>();
     uint64_t NkAll = 0;
-    if (cm && filtered && NUCL) {              // the globally smallest key (first-run quirk of the group kernel): every rank saw its own buckets' records
-        uint64_t mk = 0; PH_COPY_SYNC(st, &mk, dMinKey.p, 8, hipMemcpyDeviceToHost);
-        rc = commAllReduceMinU64(ctx, &mk, 1); if (rc) return rc;
-        PH_COPY_SYNC(st, dMinKey.p, &mk, 8, hipMemcpyHostToDevice);
-    }
+    if (cm && filtered && NUCL) { rc = allReduceMinKey(ctx, dMinKey); if (rc) return rc; }      // every rank saw its own buckets' records
     if (exch) {
         // ---- exchange 1: the lines of every level-1 bucket to the bucket's owner ----
         std::vector<uint32_t> hStart1(geo.nb1 + 1);
@@ -617,11 +617,7 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
         PH_COPY_SYNC(st, dRxSegs.p, segs.data(), segs.size() * sizeof(RxSeg), hipMemcpyHostToDevice);
         PH_COPY_SYNC(st, dRxStart.p, rxStart.data(), ((size_t) nbL + 1) * 4, hipMemcpyHostToDevice);
         if (!segs.empty()) hipLaunchKernelGGL(rxListKernel, dim3((unsigned) std::min<size_t>(segs.size(), (size_t) numCU * 8)), dim3(256), 0, st, (const RxSeg *) dRxSegs.p, (uint32_t) segs.size(), dRxList.as<uint32_t>());
-        if (NUCL) {              // the globally smallest key (first-run quirk of the group kernel)
-            uint64_t mk = 0; PH_COPY_SYNC(st, &mk, dMinKey.p, 8, hipMemcpyDeviceToHost);
-            rc = commAllReduceMinU64(ctx, &mk, 1); if (rc) return rc;
-            PH_COPY_SYNC(st, dMinKey.p, &mk, 8, hipMemcpyHostToDevice);
-        }
+        if (NUCL) { rc = allReduceMinKey(ctx, dMinKey); if (rc) return rc; }
         l1Recs = dRx.p; l1List = dRxList.as<uint32_t>(); l1Start = dRxStart.as<uint32_t>(); l1Lines = gotLines; l1Tags = nullptr;
     }
     void *finalRecs = l1Recs; const uint32_t *finalTags = l1Tags, *finalList = l1List; uint64_t finalCap = l1Lines;
@@ -637,16 +633,16 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
         LinePartArgs a; memset(&a, 0, sizeof(a));
         a.in = l1Recs; a.list = l1List; a.out = l2Out; a.tags = dTag2.as<uint32_t>(); a.pieces = dPieces2.as<LinePiece>(); a.nPieces = dNP2.as<uint32_t>(); a.nb = geo.nb2;
         a.key.shift = 64 - geo.b1 - geo.b2;
-        PH_CHECK(hipEventRecord(ctx->ev[10], st));
+        PH_CHECK(hipEventRecord(ctx->ev[KM_EV_L2_BEGIN], st));
         rc = launchLinePart<NUCL, LONG, KEY_HASH, true, false>(ctx, a, geo.maxP2); if (rc) return rc;
-        PH_CHECK(hipEventRecord(ctx->ev[11], st));
+        PH_CHECK(hipEventRecord(ctx->ev[KM_EV_L2_END], st));
         rc = buildRegionLists(ctx, "hash", dTag2.as<uint32_t>(), dNP2.as<uint32_t>(), dRegBeg.as<uint64_t>(), dRegEnd.as<uint64_t>(), nbL, geo.nb2, dList2.as<uint32_t>(), dFineBeg.as<uint32_t>(), dFineCnt.as<uint32_t>()); if (rc) return rc;
         finalRecs = l2Out; finalTags = dTag2.as<uint32_t>(); finalList = dList2.as<uint32_t>(); finalCap = cap2;
         res.nPart = 2;
     } else {
         hipLaunchKernelGGL(listRangesKernel, dim3(4), dim3(256), 0, st, l1Start, nbL, dFineBeg.as<uint32_t>(), dFineCnt.as<uint32_t>());
     }
-    PH_CHECK(hipEventRecord(ctx->ev[6], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_PART_END], st));
     PH_TRACE(st, "kmermatch: hash partition (line store)");
     PH_CHECK(hipGetLastError());
 
@@ -726,7 +722,7 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
     res.Nk = NkLocal;                                         // sharded run: the records THIS rank extracted (the ranks' sum is the run's N_k)
     if (cm && filtered) { res.Nk = 0; for (uint32_t b = 0; b < VH_BINS; b++) res.Nk += hVHist[b]; }      // ... owner-filtered: the records it KEPT (level 1 counts each in its value histogram)
     res.Nm = NmLocal;
-    PH_CHECK(hipEventRecord(ctx->ev[7], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_GROUP_END], st));
     PH_TRACE(st, "kmermatch: group (line store)");
 
     // ---- stale records behind the compaction point that continue the last run (see section 7 above) ----
@@ -784,7 +780,7 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
     }
 
     // ---- sort #2: range partition of the grouped records by rep id over the line store + aggregation / sort per bucket ----
-    PH_CHECK(hipEventRecord(ctx->ev[12], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_SORT2_BEGIN], st));
     // the hash-bucketed records are dead now (the group kernel's arenas live in another buffer): free them for the rep side
     if (exch) { dL2.release(); if (!geo.nb2) dRx.release(); }
     else (finalRecs == dA.p ? dA : dB).release();
@@ -818,11 +814,11 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
         moveBuf(dA, dMerged);                                 // the caller's dA owns the result
         nTriples = nMerged;
     } else moveBuf(dA, dTriples);
-    PH_CHECK(hipEventRecord(ctx->ev[13], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_SORT2_END], st));
     PH_TRACE(st, "kmermatch: rep sort (line store)");
     PH_CHECK(hipGetLastError());
     res.triples = dA.p; res.nTriples = nTriples;
-    { float msS = 0, msS2 = 0; (void) hipEventElapsedTime(&msS, ctx->ev[8], ctx->ev[9]); if (res.nPart == 2) (void) hipEventElapsedTime(&msS2, ctx->ev[10], ctx->ev[11]); res.msPart = msS + msS2; }
+    res.msPart = eventMs(ctx, KM_EV_L1_BEGIN, KM_EV_L1_END) + (res.nPart == 2 ? eventMs(ctx, KM_EV_L2_BEGIN, KM_EV_L2_END) : 0.0f);
     return PLASSHIP_OK;
 }
 
@@ -831,15 +827,13 @@ static int kmermatchLines(plasship_ctx *ctx, const plasship_seqdb *db, const pla
 // `cur`: nTriples triples in (rep, target, diagonal) order (sharded run: room for HALO_SLACK more behind them)
 template <bool NUCL, bool LONG>
 static int reduceToCandidates(plasship_ctx *ctx, const plasship_seqdb *db, void *cur, uint64_t nTriples, const std::vector<int64_t> &stalePos, uint32_t staleT,
-                              std::unique_ptr<plasship_cands> &holder, uint64_t &Nc, float &msReduce, bool lazyClock = false) {
+                              std::unique_ptr<plasship_cands> &holder, uint64_t &Nc) {
     hipStream_t st = ctx->stream;
     const uint32_t N = (uint32_t) db->n;
-    Timer tm{ctx, 0};
     const plasship_comm *cm = commOf(ctx);
     const int W = cm ? cm->world : 1, rk = cm ? cm->rank : 0;
     const uint64_t repBase = ownedBegin(N, rk, W), ownedN = ownedBegin(N, rk + 1, W) - repBase;
     // ---- per-(rep,target) reduction + CSR ----
-    if (!lazyClock) tm.start(0);                             // (lazyClock: the caller recorded ev[13] and reads ev[13] .. ev[14] when the call is over)
     DevBuf dTmpHits, dEmit, dEpos, dPerRep, dQoff;
     if (dTmpHits.alloc(std::max<uint64_t>(nTriples, 1) * sizeof(CandHit)) != hipSuccess || dEmit.alloc((nTriples / 64 + 2) * 4) != hipSuccess ||
         dEpos.alloc((nTriples / 64 + 3) * 8) != hipSuccess || dPerRep.alloc(((size_t) N + 1) * 4) != hipSuccess) { setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE; }
@@ -918,7 +912,7 @@ static int reduceToCandidates(plasship_ctx *ctx, const plasship_seqdb *db, void 
     if (c->d_hits.alloc(std::max<uint64_t>(c->nHits, 1) * sizeof(CandHit)) != hipSuccess) { setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE; }
     if (qHi > qLo) hipLaunchKernelGGL(placeSelfKernel, dim3(gridFor(qHi - qLo, 256, 4096)), dim3(256), 0, st, c->d_qoff.as<uint64_t>(), qLo, qHi, c->d_hits.as<CandHit>());
     if (nTriples) hipLaunchKernelGGL(placeHitsKernel, dim3(gridFor(nTriples, 256, 65535)), dim3(256), 0, st, dTmpHits.as<CandHit>(), dEpos.as<uint64_t>(), nTriples, qLo, c->d_hits.as<CandHit>());
-    if (lazyClock) PH_CHECK(hipEventRecord(ctx->ev[14], st)); else msReduce = tm.stop(1);
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_REDUCE_END], st));      // (the caller reads SORT2_END .. REDUCE_END when the call is over)
     PH_TRACE(st, "kmermatch: reduce");
     PH_CHECK(plasship::streamSync(st));
     PH_CHECK(hipGetLastError());
@@ -967,6 +961,41 @@ static int reduceToCandidates(plasship_ctx *ctx, const plasship_seqdb *db, void 
     return PLASSHIP_OK;
 }
 
+// the head every extraction kernel's argument struct shares with ExtractArgs, filled from `ea` in this one place
+template <class A> static A argsFrom(const ExtractArgs &ea) {
+    A a; memset(&a, 0, sizeof(a));
+    a.s = ea.s; a.slotOff = ea.slotOff; a.arr = ea.arr; a.map = ea.map; a.k = ea.k; a.seed = ea.seed; a.kstats = ea.kstats;
+    return a;
+}
+
+
+// the row tier (kmermatch_extract.hpp section 2e): one list of a wave tier sorted into four lists by window count, one launch per list
+typedef void (*RowKernel)(RowArgs);
+struct RowLadder { uint32_t bins[3]; RowKernel kernel[4]; uint32_t seqsPerWave[4]; };      // bins: the last window counts of the first three lists
+// four sequences per wavefront for the sequences of the 4-scores tier
+static constexpr RowLadder ROWS_16 = {{96u, 128u, 192u}, {extractRowKernel<6>, extractRowKernel<8>, extractRowKernel<12>, extractRowKernel<16>}, {4u, 4u, 4u, 4u}};
+// two sequences or one per wavefront for the sequences of the 16-scores tier (257-1024 windows; groups of 32 and 64 lanes)
+static constexpr RowLadder ROWS_WIDE = {{ROW_WIDE_BINS[0], ROW_WIDE_BINS[1], ROW_WIDE_BINS[2]},
+                                        {extractRowKernel<10, 32>, extractRowKernel<12, 32>, extractRowKernel<16, 32>, extractRowKernel<16, 64>}, {2u, 2u, 2u, 1u}};
+// sorts listIn into lists[4][N + 1] (counts[0 .. 3]) and runs the ladder's four launches; what a launch cannot finish (surplus in the
+// threshold bin, a possible repeat) is queued in fallList / fallCount, which the wave tier behind the ladder reads instead of listIn
+static void launchRowLadder(plasship_ctx *ctx, const plasship_seqdb *db, const ExtractArgs &ea, uint32_t nMine, const uint32_t *listIn, const uint32_t *countIn, const RowLadder &lad,
+                            uint32_t *lists, uint32_t *counts, uint32_t *fallList, uint32_t *fallCount) {
+    hipStream_t st = ctx->stream;
+    const uint32_t rs = (uint32_t) db->n + 1;
+    hipLaunchKernelGGL(binWaveListKernel, dim3(std::min<uint32_t>((nMine + 2047) / 2048, (uint32_t) ctx->numCU * 8)), dim3(256), 0, st, listIn, countIn,
+                       (const uint32_t *) db->d_len.as<uint32_t>(), (uint32_t) ea.k, lad.bins[0], lad.bins[1], lad.bins[2], lists, rs, counts);
+    RowArgs ra = argsFrom<RowArgs>(ea);
+    ra.xCode = ea.xCode; ra.kps = ea.kps; ra.ignoreMulti = ea.ignoreMulti; ra.base = (uint32_t) ea.powers[1]; ra.base7 = (uint32_t) ea.powers[7]; ra.slotBias = ea.slotBias;
+    ra.fallList = fallList; ra.fallCount = fallCount;
+    for (int b = 0; b < 4; b++) {
+        ra.list = lists + (size_t) b * rs; ra.count = counts + b;
+        const dim3 grid(std::min<uint32_t>((nMine + lad.seqsPerWave[b] - 1) / lad.seqsPerWave[b], (uint32_t) ctx->numCU * 32u));
+        hipLaunchKernelGGL((lad.kernel[b]), grid, dim3(64), 0, st, ra);
+    }
+}
+
+
 template <bool NUCL, bool LONG>
 int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_kmermatch_params *par, plasship_cands **out,
                   plasship_kmermatch_stats *stats, bool overflowCheckEarly) {
@@ -974,7 +1003,8 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     hipStream_t st = ctx->stream;
     const uint32_t N = (uint32_t) db->n;
     const int k = par->kmer_size;
-    float msExtract = 0;
+    KmSelect sel; sel.k = k; sel.alph = NUCL ? 5 : par->alphabet_size; sel.kps = par->kmers_per_seq; sel.scale = par->kmers_per_seq_scale;
+    sel.ignoreMulti = par->ignore_multi_kmer; sel.hashShift = par->hash_shift; sel.lng = LONG;
     // sharded run (plasship_ctx_set_comm): this rank extracts the sequences [sLo, sHi), owns the k-mer hash buckets that map to
     // it, and owns the representatives / queries [repBase, repBase + ownedN)
     const plasship_comm *cm = commOf(ctx);
@@ -986,7 +1016,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     if (dBound.alloc(((size_t) N + 1) * 4) != hipSuccess || dSlotOff.alloc(((size_t) N + 2) * 8) != hipSuccess || dScanTmp.alloc(scanTmpBytes) != hipSuccess) {
         setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE;
     }
-    PH_CHECK(hipEventRecord(ctx->ev[0], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_BEGIN], st));
     if (N) hipLaunchKernelGGL(boundsKernel, dim3(gridFor(N, 256, 4096)), dim3(256), 0, st, db->d_len.as<uint32_t>(), N, k, par->kmers_per_seq, par->kmers_per_seq_scale, dBound.as<uint32_t>());
     if (exclusiveScanU32(st, dBound.as<uint32_t>(), dSlotOff.as<uint64_t>(), N, dScanTmp.p, scanTmpBytes)) { setError("kmermatch: scan failed"); return PLASSHIP_ERR_DEVICE; }
     uint64_t total = 0;
@@ -1049,8 +1079,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     const bool fastIndex = !NUCL && k <= 14 && ea.powers[1] <= 16;      // kmerIndexCore
     const bool cacheEligible = !NUCL && !LONG && (!cm || filtered) && fastIndex && k <= 16 && par->kmers_per_seq >= 1 && par->kmers_per_seq <= (int) KMC_POS + 1 && par->kmers_per_seq_scale == 0.0f &&
                                tuneInt("KMCACHE", 1) == 1;      // PLASSHIP_TUNE_KMCACHE=2 switches the cache off
-    const bool cacheReuse = cacheEligible && kc.valid && kc.n == N && kc.gen == db->parentGen && db->d_changed.p && kc.k == k && kc.alph == par->alphabet_size &&
-                            kc.kps == par->kmers_per_seq && kc.ignoreMulti == par->ignore_multi_kmer && kc.hashShift == par->hash_shift && !overflowCheckEarly;
+    const bool cacheReuse = cacheEligible && kc.valid && kc.n == N && kc.gen == db->parentGen && db->d_changed.p && kc.sel == sel && !overflowCheckEarly;
     kc.valid = false;                                         // (set again when this call has succeeded)
     DevBuf dCachedList, dCachedCount;
     unsigned long long cacheLinesPtr = 0;                    // -> kstats[4] (see ExtractArgs)
@@ -1071,8 +1100,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     typedef typename std::conditional<LONG, uint32_t, unsigned short>::type PosT;
     plasship_ctx::KmPosCache &pc = ctx->kmPosCache;
     const bool posEligible = NUCL && !cm && N && tuneInt("KMCACHE", 1) == 1;      // PLASSHIP_TUNE_KMCACHE=2 switches it off
-    bool posReuse = posEligible && pc.valid && pc.gen != 0 && db->originGen == pc.gen && db->d_origin.p && pc.lng == LONG && pc.k == k && pc.kps == par->kmers_per_seq &&
-                          pc.scale == par->kmers_per_seq_scale && pc.ignoreMulti == par->ignore_multi_kmer && pc.hashShift == par->hash_shift;
+    bool posReuse = posEligible && pc.valid && pc.gen != 0 && db->originGen == pc.gen && db->d_origin.p && pc.sel == sel;
     // (like the lines of section 2c, the positions are only written when a later call can use them: a derived DB, or a context that has run kmermatcher before)
     bool posWanted = posEligible && (posReuse || db->parentGen != 0 || db->ancestorGen != 0 || db->originGen != 0 || pc.seen || ctx->kmermatchCalls > 0);
     if (posEligible) pc.seen = true;
@@ -1090,14 +1118,13 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         }
     }
     PH_CHECK(hipMemcpyAsync(dKStats.as<unsigned long long>() + 4, cachePtrs, 24, hipMemcpyHostToDevice, st));      // (cachePtrs lives until the function's last wait)
-    PH_CHECK(hipEventRecord(ctx->ev[2], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_SHORT_BEGIN], st));
     if (!NUCL && k <= 16 && nMine) {
         // short sequences: one thread each; everything else is queued for the wave-per-sequence kernels, in two lists by length
-        ShortArgs sa; memset(&sa, 0, sizeof(sa));
-        sa.s = ea.s; sa.slotOff = ea.slotOff; sa.arr = ea.arr; sa.map = ea.map; sa.k = k; sa.xCode = ea.xCode; sa.kps = ea.kps; sa.ignoreMulti = ea.ignoreMulti;
-        sa.scale = ea.scale; sa.seed = ea.seed; sa.base = (uint64_t) (alph - 1); sa.top = ea.powers[k - 1];
+        ShortArgs sa = argsFrom<ShortArgs>(ea);
+        sa.xCode = ea.xCode; sa.kps = ea.kps; sa.ignoreMulti = ea.ignoreMulti; sa.scale = ea.scale; sa.base = (uint64_t) (alph - 1); sa.top = ea.powers[k - 1];
         { uint64_t b = sa.base; int tz = 0; while ((b & 1) == 0) { b >>= 1; tz++; } uint64_t inv = b; for (int i = 0; i < 6; i++) inv *= 2 - b * inv; sa.tz = tz; sa.inv = inv; }
-        sa.waveList = dWaveList.as<uint32_t>(); sa.waveCount = dWaveCount.as<uint32_t>(); sa.kstats = dKStats.as<unsigned long long>();
+        sa.waveList = dWaveList.as<uint32_t>(); sa.waveCount = dWaveCount.as<uint32_t>();
         sa.longList = dLongList.as<uint32_t>(); sa.longCount = dLongCount.as<uint32_t>(); sa.longWindows = TIER0_WINDOWS;
         // more than 16 scores per lane: straight into the queue the 48-scores tier reads (tiers 0 and 1 append their rare overflows
         // to the same queue, one atomic per sequence)
@@ -1131,10 +1158,10 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         else hipLaunchKernelGGL((extractShortKernel<LONG>), shortGrid, dim3(64), 0, st, sa);   // 18 wavefronts fit a CU; on large sets a finer grid evens out the tail (50 M reads, round 3: 35.7 -> 34.4 ms at 72 per CU; round 4, after the residency cap: another 0.3-1.1 ms per iteration at 144, nothing more at 288 / 576)
         ea.waveList = dWaveList.as<uint32_t>(); ea.waveCount = dWaveCount.as<uint32_t>();
         if (cacheReuse) {
-            CachedArgs ca; memset(&ca, 0, sizeof(ca));
-            ca.s = ea.s; ca.slotOff = ea.slotOff; ca.arr = ea.arr; ca.map = ea.map; ca.lines = kc.lines.as<unsigned char>();
-            ca.list = dCachedList.as<uint32_t>(); ca.count = dCachedCount.as<uint32_t>(); ca.k = k; ca.xCode = ea.xCode;
-            ca.base = (uint32_t) ea.powers[1]; ca.base7 = (uint32_t) ea.powers[7]; ca.slotBias = slotBias; ca.seed = ea.seed; ca.kstats = dKStats.as<unsigned long long>();
+            CachedArgs ca = argsFrom<CachedArgs>(ea);
+            ca.lines = kc.lines.as<unsigned char>();
+            ca.list = dCachedList.as<uint32_t>(); ca.count = dCachedCount.as<uint32_t>(); ca.xCode = ea.xCode;
+            ca.base = (uint32_t) ea.powers[1]; ca.base7 = (uint32_t) ea.powers[7]; ca.slotBias = slotBias;
             hipLaunchKernelGGL(extractCachedKernel, dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * 32u)), dim3(64), 0, st, ca);
         }
     }
@@ -1145,16 +1172,16 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         ea.waveList = dWaveList.as<uint32_t>(); ea.waveCount = dWaveCount.as<uint32_t>();
         if constexpr (NUCL) {
             if (posReuse) {      // entries the position cache describes: their records rebuilt from the cached window positions
-                CachedPosArgs<LONG> ca; memset(&ca, 0, sizeof(ca));
-                ca.s = ea.s; ca.slotOff = ea.slotOff; ca.arr = ea.arr; ca.map = ea.map; ca.posOld = pc.pos.p; ca.slotOffOld = pc.slotOff.as<uint64_t>();
+                CachedPosArgs<LONG> ca = argsFrom<CachedPosArgs<LONG>>(ea);
+                ca.posOld = pc.pos.p; ca.slotOffOld = pc.slotOff.as<uint64_t>();
                 ca.idHashOld = pc.idHash.as<unsigned long long>(); ca.origin = db->d_origin.as<uint32_t>(); ca.posNew = dPosNew.p; ca.idHashNew = dIdHashNew.as<unsigned long long>();
-                ca.list = dCachedList.as<uint32_t>(); ca.count = dCachedCount.as<uint32_t>(); ca.k = k; ca.seed = ea.seed; ca.kstats = dKStats.as<unsigned long long>();
+                ca.list = dCachedList.as<uint32_t>(); ca.count = dCachedCount.as<uint32_t>();
                 hipLaunchKernelGGL((extractCachedPosKernel<LONG>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * 32u)), dim3(64), 0, st, ca);
             }
         }
     }
-    PH_CHECK(hipEventRecord(ctx->ev[3], st));
-    PH_CHECK(hipEventRecord(ctx->ev[4], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_SHORT_END], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_WAVE_BEGIN], st));
     // one-wavefront workgroups per CU of the register tiers' grids.  32 was measured best of 12..64 on the 1 M-read set; on the 50 M-read chain
     // (round 6, profiles/r06_ab_knobs.txt call 7) a CU holds 20 / 16 of them at once and a grid of 32 leaves a second, 60 %-filled round: 40: 57.5 ms
     // for the wave tiers per iteration, 64: 55.8, 96: 54.5, 128: 54.1, 192: 53.7, 256: 53.7, 512: 54.7 against 58.1 at 32 -> 192 for large sets
@@ -1169,7 +1196,6 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     // Tiers 0 and 1 take their sequences from the two lists of the thread-per-sequence kernel; what either cannot hold goes to
     // one queue for tier 2, and on to tier 3.
     DevBuf dOv2Ids, dOv2Cnt;
-    DevBuf *lastIds = &dOvIds, *lastCnt = &dOvCnt;
     if (nMine) {
         if (dOv2Ids.alloc(((size_t) N + 1) * 4) != hipSuccess || dOv2Cnt.alloc(4) != hipSuccess) { setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE; }
         PH_CHECK(hipMemsetAsync(dOv2Cnt.p, 0, 4, st));
@@ -1191,20 +1217,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
             }
             PH_CHECK(hipMemsetAsync(dRowCounts.p, 0, 48, st));
             PH_CHECK(hipMemsetAsync(dRowFallCnt.p, 0, 4, st));
-            hipLaunchKernelGGL(binWaveListKernel, dim3(std::min<uint32_t>((nMine + 2047) / 2048, (uint32_t) ctx->numCU * 8)), dim3(256), 0, st, (const uint32_t *) dWaveList.as<uint32_t>(), (const uint32_t *) dWaveCount.as<uint32_t>(),
-                               (const uint32_t *) db->d_len.as<uint32_t>(), (uint32_t) k, 96u, 128u, 192u, dRowLists.as<uint32_t>(), rs, dRowCounts.as<uint32_t>());
-            RowArgs ra; memset(&ra, 0, sizeof(ra));
-            ra.s = ea.s; ra.slotOff = ea.slotOff; ra.arr = ea.arr; ra.map = ea.map; ra.fallList = dRowFall.as<uint32_t>(); ra.fallCount = dRowFallCnt.as<uint32_t>();
-            ra.k = k; ra.xCode = ea.xCode; ra.kps = ea.kps; ra.ignoreMulti = ea.ignoreMulti; ra.seed = ea.seed; ra.base = (uint32_t) ea.powers[1]; ra.base7 = (uint32_t) ea.powers[7];
-            ra.slotBias = slotBias; ra.kstats = dKStats.as<unsigned long long>();
-            const dim3 rowGrid(std::min<uint32_t>((nMine + 3) / 4, (uint32_t) ctx->numCU * 32u));
-            for (int b = 0; b < 4; b++) {
-                ra.list = dRowLists.as<uint32_t>() + (size_t) b * rs; ra.count = dRowCounts.as<uint32_t>() + b;
-                if (b == 0) hipLaunchKernelGGL((extractRowKernel<6>), rowGrid, dim3(64), 0, st, ra);
-                else if (b == 1) hipLaunchKernelGGL((extractRowKernel<8>), rowGrid, dim3(64), 0, st, ra);
-                else if (b == 2) hipLaunchKernelGGL((extractRowKernel<12>), rowGrid, dim3(64), 0, st, ra);
-                else hipLaunchKernelGGL((extractRowKernel<16>), rowGrid, dim3(64), 0, st, ra);
-            }
+            launchRowLadder(ctx, db, ea, nMine, dWaveList.as<uint32_t>(), dWaveCount.as<uint32_t>(), ROWS_16, dRowLists.as<uint32_t>(), dRowCounts.as<uint32_t>(), dRowFall.as<uint32_t>(), dRowFallCnt.as<uint32_t>());
             e0.waveList = dRowFall.as<uint32_t>(); e0.waveCount = dRowFallCnt.as<uint32_t>();
         }
         // tiers 0 and 1 both queue into dOvIds
@@ -1220,20 +1233,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
             const uint32_t rs = N + 1;
             if (dWideLists.alloc((size_t) 4 * rs * 4) != hipSuccess || dWideFall.alloc((size_t) rs * 4) != hipSuccess) { setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE; }
             uint32_t *wideCounts = dRowCounts.as<uint32_t>() + 4, *wideFallCnt = dRowCounts.as<uint32_t>() + 8;
-            hipLaunchKernelGGL(binWaveListKernel, dim3(std::min<uint32_t>((nMine + 2047) / 2048, (uint32_t) ctx->numCU * 8)), dim3(256), 0, st, (const uint32_t *) dLongList.as<uint32_t>(), (const uint32_t *) dLongCount.as<uint32_t>(),
-                               (const uint32_t *) db->d_len.as<uint32_t>(), (uint32_t) k, ROW_WIDE_BINS[0], ROW_WIDE_BINS[1], ROW_WIDE_BINS[2], dWideLists.as<uint32_t>(), rs, wideCounts);
-            RowArgs ra; memset(&ra, 0, sizeof(ra));
-            ra.s = ea.s; ra.slotOff = ea.slotOff; ra.arr = ea.arr; ra.map = ea.map; ra.fallList = dWideFall.as<uint32_t>(); ra.fallCount = wideFallCnt;
-            ra.k = k; ra.xCode = ea.xCode; ra.kps = ea.kps; ra.ignoreMulti = ea.ignoreMulti; ra.seed = ea.seed; ra.base = (uint32_t) ea.powers[1]; ra.base7 = (uint32_t) ea.powers[7];
-            ra.slotBias = slotBias; ra.kstats = dKStats.as<unsigned long long>();
-            const dim3 pairGrid(std::min<uint32_t>((nMine + 1) / 2, (uint32_t) ctx->numCU * 32u)), oneGrid(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * 32u));
-            for (int b = 0; b < 4; b++) {
-                ra.list = dWideLists.as<uint32_t>() + (size_t) b * rs; ra.count = wideCounts + b;
-                if (b == 0) hipLaunchKernelGGL((extractRowKernel<10, 32>), pairGrid, dim3(64), 0, st, ra);
-                else if (b == 1) hipLaunchKernelGGL((extractRowKernel<12, 32>), pairGrid, dim3(64), 0, st, ra);
-                else if (b == 2) hipLaunchKernelGGL((extractRowKernel<16, 32>), pairGrid, dim3(64), 0, st, ra);
-                else hipLaunchKernelGGL((extractRowKernel<16, 64>), oneGrid, dim3(64), 0, st, ra);
-            }
+            launchRowLadder(ctx, db, ea, nMine, dLongList.as<uint32_t>(), dLongCount.as<uint32_t>(), ROWS_WIDE, dWideLists.as<uint32_t>(), wideCounts, dWideFall.as<uint32_t>(), wideFallCnt);
             e1.waveList = dWideFall.as<uint32_t>(); e1.waveCount = wideFallCnt;
         }
         hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP, false, 16, 992>), dim3(wide), dim3(64), 0, st, e1);
@@ -1265,8 +1265,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         hipLaunchKernelGGL((extractKernel<NUCL, LONG, CAP2, false, 0, 8160>), dim3(std::min<uint32_t>(nMine, (uint32_t) ctx->numCU * (NUCL ? 2u : 5u))), dim3(64), 0, st, e3);
     }
     // what the last stage could not hold either (candidate sets beyond LDS)
-    DevBuf &dLastIds = *lastIds, &dLastCnt = *lastCnt;
-    PH_CHECK(hipEventRecord(ctx->ev[5], st));
+    PH_CHECK(hipEventRecord(ctx->ev[KM_EV_WAVE_END], st));
     uint32_t nOv = 0;
     // protein DBs: a candidate set hardly ever exceeds the tiers' 128 entries (59 considered k-mers), and the last tier keeps up to
     // 8160 residues in LDS.  "Hardly ever": every window whose score is <= the threshold score is a candidate, and equal k-mers
@@ -1276,16 +1275,16 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     // out non-zero the call starts over with the wait in place (`overflowCheckEarly`).
     const bool overflowPossible = overflowCheckEarly || cm != nullptr || NUCL || db->maxEntryLen > 8160u || par->kmers_per_seq > 120 || par->kmers_per_seq_scale != 0.0f;
     if (nMine && overflowPossible) {
-        PH_CHECK(hipMemcpyAsync(&nOv, dLastCnt.p, 4, hipMemcpyDeviceToHost, st));
+        PH_CHECK(hipMemcpyAsync(&nOv, dOvCnt.p, 4, hipMemcpyDeviceToHost, st));
         PH_CHECK(plasship::streamSync(st));
-    } else if (nMine) hipLaunchKernelGGL((fillOverflowSlotsKernel<LONG>), dim3(64), dim3(64), 0, st, (const uint32_t *) dLastIds.as<uint32_t>(), (const uint32_t *) dLastCnt.as<uint32_t>(),
+    } else if (nMine) hipLaunchKernelGGL((fillOverflowSlotsKernel<LONG>), dim3(64), dim3(64), 0, st, (const uint32_t *) dOvIds.as<uint32_t>(), (const uint32_t *) dOvCnt.as<uint32_t>(),
                                          (const uint64_t *) dSlotOff.as<uint64_t>(), slotBias, dA.p);
     PH_CHECK(hipGetLastError());
     if (nOv) {   // sequences whose candidate set did not fit LDS: same kernel, candidates in HBM scratch
         std::vector<uint32_t> ids(nOv), lens(nOv);
         DevBuf dLens, dSOff, dSCap, dScratch;
         if (dLens.alloc((size_t) nOv * 4) != hipSuccess) { setError("kmermatch: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-        hipLaunchKernelGGL(gatherU32Kernel, dim3(gridFor(nOv, 256, 1024)), dim3(256), 0, st, db->d_len.as<uint32_t>(), dLastIds.as<uint32_t>(), nOv, dLens.as<uint32_t>());
+        hipLaunchKernelGGL(gatherU32Kernel, dim3(gridFor(nOv, 256, 1024)), dim3(256), 0, st, db->d_len.as<uint32_t>(), dOvIds.as<uint32_t>(), nOv, dLens.as<uint32_t>());
         PH_CHECK(hipMemcpyAsync(lens.data(), dLens.p, (size_t) nOv * 4, hipMemcpyDeviceToHost, st));
         PH_CHECK(plasship::streamSync(st));
         std::vector<uint64_t> soff(nOv); std::vector<uint32_t> scap(nOv); uint64_t tot = 0;
@@ -1295,7 +1294,7 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
         }
         PH_CHECK(hipMemcpyAsync(dSOff.p, soff.data(), (size_t) nOv * 8, hipMemcpyHostToDevice, st));
         PH_CHECK(hipMemcpyAsync(dSCap.p, scap.data(), (size_t) nOv * 4, hipMemcpyHostToDevice, st));
-        ExtractArgs fa = ea; fa.idList = dLastIds.as<uint32_t>(); fa.nIds = nOv; fa.scratch = dScratch.as<Cand>(); fa.scratchOff = dSOff.as<uint64_t>(); fa.scratchCap = dSCap.as<uint32_t>();
+        ExtractArgs fa = ea; fa.idList = dOvIds.as<uint32_t>(); fa.nIds = nOv; fa.scratch = dScratch.as<Cand>(); fa.scratchOff = dSOff.as<uint64_t>(); fa.scratchCap = dSCap.as<uint32_t>();
         hipLaunchKernelGGL((extractKernel<NUCL, LONG, 1, true>), dim3(std::min<uint32_t>(nOv, (uint32_t) ctx->numCU * 8)), dim3(64), 0, st, fa);
         PH_CHECK(plasship::streamSync(st));
         PH_CHECK(hipGetLastError());
@@ -1303,47 +1302,41 @@ int kmermatchImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_km
     PH_TRACE(st, "kmermatch: extraction");
     traceBadIds<LONG>(ctx, "kmermatch: extracted slots", dA.p, total, N);
 
-    {
-        int keyBitsL = 0;
-        if (NUCL) keyBitsL = 2 * k; else { long double v = 1; for (int i = 0; i < k; i++) v *= (long double) (alph - 1); while (keyBitsL < 63 && (long double) (1ULL << keyBitsL) < v) keyBitsL++; }
-        LinesOut lo;
-        int rcL = kmermatchLines<NUCL, LONG>(ctx, db, par, geo, total, dA, dB, dSlotOff, dKStats, ea, keyBitsL, lo, (nMine && !overflowPossible) ? dLastCnt.as<uint32_t>() : nullptr, filtered);
-        if (rcL) return rcL;                                  // (KM_RETRY_EARLY_OVERFLOW_CHECK: the caller starts over)
-        std::unique_ptr<plasship_cands> holderL; uint64_t NcL = 0; float msReduceL = 0;
-        rcL = reduceToCandidates<NUCL, LONG>(ctx, db, lo.triples, lo.nTriples, lo.stalePos, lo.staleT, holderL, NcL, msReduceL, true);
-        if (rcL) return rcL;
-        {   // the stage boundaries (all recorded, all complete: reduceToCandidates ended with a wait for the stream)
-            auto ms = [&](int a, int b) { float v = 0; (void) hipEventElapsedTime(&v, ctx->ev[a], ctx->ev[b]); return v; };
-            msExtract = ms(0, 1); lo.msSort1 = ms(1, 6); lo.msGroup = ms(6, 7); lo.msSort2 = ms(12, 13); msReduceL = ms(13, 14);
-        }
-        if (stats) {
-            stats->n_kmer_records = lo.Nk; stats->n_grouped = lo.Nm; stats->n_candidates = NcL; stats->record_bytes = LONG ? 20 : 16;
-            float ms = 0, ms2 = 0; (void) hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]); (void) hipEventElapsedTime(&ms2, ctx->ev[4], ctx->ev[5]);
-            stats->ms_extract_short_kernel = ms; stats->ms_extract_wave_kernel = ms2; stats->ms_extract_kernel = ms + ms2;
-            stats->ms_part_scatter = lo.msPart; stats->n_part_scatter = lo.nPart;
-            unsigned long long ks[4] = {0, 0, 0, 0}; uint32_t nCachedSeqs = 0;
-            if (cacheReuse || posReuse) PH_CHECK(hipMemcpyAsync(&nCachedSeqs, dCachedCount.p, 4, hipMemcpyDeviceToHost, st));
-            PH_COPY_SYNC(st, ks, dKStats.p, 32, hipMemcpyDeviceToHost);
-            stats->n_cached_sequences = nCachedSeqs; stats->reserved0 = 0;
-            stats->short_residues = ks[0]; stats->short_records = ks[1]; stats->wave_residues = ks[2]; stats->wave_records = ks[3];
-            stats->residues = db->residues;
-            stats->ms_extract = msExtract; stats->ms_sort1 = lo.msSort1; stats->ms_group = lo.msGroup; stats->ms_sort2 = lo.msSort2; stats->ms_reduce = msReduceL;
-            stats->n_scratch_sequences = nOv; stats->n_restarts = overflowCheckEarly ? 1u : 0u;
-        }
-        if (cacheWanted) {     // the lines now describe THIS DB (the wave kernels rewrote what changed, the rest was kept)
-            kc.valid = true; kc.n = N; kc.gen = db->gen; kc.k = k; kc.alph = par->alphabet_size; kc.kps = par->kmers_per_seq; kc.ignoreMulti = par->ignore_multi_kmer; kc.hashShift = par->hash_shift;
-        }
-        if (posWanted) {       // the positions now describe THIS DB: it becomes the anchor the derived DBs' d_origin refers to
-            if (pc.slotOff.allocLong(((size_t) N + 2) * 8) != hipSuccess) { pc.valid = false; setError("kmermatch: out of device memory for the position cache"); return PLASSHIP_ERR_DEVICE; }
-            PH_CHECK(hipMemcpyAsync(pc.slotOff.p, dSlotOff.p, ((size_t) N + 1) * 8, hipMemcpyDeviceToDevice, st));
-            PH_CHECK(plasship::streamSync(st));
-            std::swap(pc.pos.p, dPosNew.p); std::swap(pc.pos.bytes, dPosNew.bytes); std::swap(pc.idHash.p, dIdHashNew.p); std::swap(pc.idHash.bytes, dIdHashNew.bytes);
-            pc.valid = true; pc.n = N; pc.gen = db->gen; pc.lng = LONG; pc.k = k; pc.kps = par->kmers_per_seq; pc.scale = par->kmers_per_seq_scale;
-            pc.ignoreMulti = par->ignore_multi_kmer; pc.hashShift = par->hash_shift;
-        }
-        *out = holderL.release();
-        return PLASSHIP_OK;
+    int keyBits = 0;
+    if (NUCL) keyBits = 2 * k; else { long double v = 1; for (int i = 0; i < k; i++) v *= (long double) (alph - 1); while (keyBits < 63 && (long double) (1ULL << keyBits) < v) keyBits++; }
+    LinesOut lo;
+    int rc = kmermatchLines<NUCL, LONG>(ctx, db, par, geo, dA, dB, dSlotOff, dKStats, ea, keyBits, lo, (nMine && !overflowPossible) ? dOvCnt.as<uint32_t>() : nullptr, filtered);
+    if (rc) return rc;                                  // (KM_RETRY_EARLY_OVERFLOW_CHECK: the caller starts over)
+    std::unique_ptr<plasship_cands> holder; uint64_t Nc = 0;
+    rc = reduceToCandidates<NUCL, LONG>(ctx, db, lo.triples, lo.nTriples, lo.stalePos, lo.staleT, holder, Nc);
+    if (rc) return rc;
+    if (stats) {   // the stage boundaries are all recorded and complete: reduceToCandidates ended with a wait for the stream
+        stats->n_kmer_records = lo.Nk; stats->n_grouped = lo.Nm; stats->n_candidates = Nc; stats->record_bytes = LONG ? 20 : 16;
+        const float ms = eventMs(ctx, KM_EV_SHORT_BEGIN, KM_EV_SHORT_END), ms2 = eventMs(ctx, KM_EV_WAVE_BEGIN, KM_EV_WAVE_END);
+        stats->ms_extract_short_kernel = ms; stats->ms_extract_wave_kernel = ms2; stats->ms_extract_kernel = ms + ms2;
+        stats->ms_part_scatter = lo.msPart; stats->n_part_scatter = lo.nPart;
+        unsigned long long ks[4] = {0, 0, 0, 0}; uint32_t nCachedSeqs = 0;
+        if (cacheReuse || posReuse) PH_CHECK(hipMemcpyAsync(&nCachedSeqs, dCachedCount.p, 4, hipMemcpyDeviceToHost, st));
+        PH_COPY_SYNC(st, ks, dKStats.p, 32, hipMemcpyDeviceToHost);
+        stats->n_cached_sequences = nCachedSeqs; stats->reserved0 = 0;
+        stats->short_residues = ks[0]; stats->short_records = ks[1]; stats->wave_residues = ks[2]; stats->wave_records = ks[3];
+        stats->residues = db->residues;
+        stats->ms_extract = eventMs(ctx, KM_EV_BEGIN, KM_EV_EXTRACT_END); stats->ms_sort1 = eventMs(ctx, KM_EV_EXTRACT_END, KM_EV_PART_END); stats->ms_group = eventMs(ctx, KM_EV_PART_END, KM_EV_GROUP_END);
+        stats->ms_sort2 = eventMs(ctx, KM_EV_SORT2_BEGIN, KM_EV_SORT2_END); stats->ms_reduce = eventMs(ctx, KM_EV_SORT2_END, KM_EV_REDUCE_END);
+        stats->n_scratch_sequences = nOv; stats->n_restarts = overflowCheckEarly ? 1u : 0u;
     }
+    if (cacheWanted) {     // the lines now describe THIS DB (the wave kernels rewrote what changed, the rest was kept)
+        kc.valid = true; kc.n = N; kc.gen = db->gen; kc.sel = sel;
+    }
+    if (posWanted) {       // the positions now describe THIS DB: it becomes the anchor the derived DBs' d_origin refers to
+        if (pc.slotOff.allocLong(((size_t) N + 2) * 8) != hipSuccess) { pc.valid = false; setError("kmermatch: out of device memory for the position cache"); return PLASSHIP_ERR_DEVICE; }
+        PH_CHECK(hipMemcpyAsync(pc.slotOff.p, dSlotOff.p, ((size_t) N + 1) * 8, hipMemcpyDeviceToDevice, st));
+        PH_CHECK(plasship::streamSync(st));
+        std::swap(pc.pos.p, dPosNew.p); std::swap(pc.pos.bytes, dPosNew.bytes); std::swap(pc.idHash.p, dIdHashNew.p); std::swap(pc.idHash.bytes, dIdHashNew.bytes);
+        pc.valid = true; pc.n = N; pc.gen = db->gen; pc.sel = sel;
+    }
+    *out = holder.release();
+    return PLASSHIP_OK;
 }
 }  // namespace
 
