@@ -51,7 +51,7 @@ struct AsmArgs {
     uint64_t *newStart;                         // [n] absolute arena offset of the extended query
     const signed char *mat;
     double lambda, logK, ln2;
-    float seqIdThr; uint64_t maxSeqLen; int rescoreMode;
+    float seqIdThr; uint64_t maxSeqLen; int reserved0;     // (reserved0: no kernel reads it; it keeps ownLaneMin's offset in the kernels' argument block)
     uint32_t ownLaneMin;                        // wide register queues: at least this many deferred hits of a round are re-scored each by its own lane, fewer one after the other by the whole group
     unsigned long long *stats;                  // [0] extended, [1] rescored hits, [2] rescored overlap residues
     uint32_t *bigList; uint32_t nBig;   // queries with more than 64 alignments (HBM-resident queue)
@@ -1551,122 +1551,6 @@ __global__ __launch_bounds__(256) void nuclClassScatterKernel(const uint32_t *__
     }
 }
 
-__global__ void outLenKernel(SeqView s, const uint32_t *__restrict__ flags, const uint32_t *__restrict__ newLen, int keepTarget,
-                             uint64_t *__restrict__ outBytes, uint32_t *__restrict__ keep, uint64_t *__restrict__ appBytes) {
-    for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < s.n; id += gridDim.x * blockDim.x) {
-        const uint32_t f = flags[id];
-        uint64_t b = 0, ap = 0; uint32_t k = 0;
-        if (f & 0x20u) { b = (uint64_t) newLen[id] + 2; k = 1; ap = b; }
-        else if (keepTarget || !(f & 0x80u)) { b = (uint64_t) s.len[id] + 2; k = 1; }
-        outBytes[id] = b; keep[id] = k;
-        if (appBytes) appBytes[id] = ap;                      // what the entry adds to a shared heap: only rewritten entries have new bytes
-    }
-}
-
-// The output DB as an INDEX over the heap the input DB lives in (SeqHeap, common.hpp): an entry that is carried over keeps its bytes
-// where they are, a rewritten one (flag 0x20: extended, cut, chopped) is copied from the arena to heapBase + appOff[id] behind
-// everything the heap held.  G lanes per entry; what moves per iteration is the rewritten 10-20 % of the sequences instead of
-// 2 x all residues (writeOutKernel below: 15 ms per iteration at 50 M reads, the same again on every rank of a sharded run).
-// Round 5: ONE THREAD per entry for the index (coalesced: rounds 4's eight lanes per entry read every index word eight times over and moved
-// 14.6 + 5.4 GB per launch for ~3 GB of rewritten entries), then the wavefront copies the rewritten entries of its 64 ids one after the other
-// with all 64 lanes, 8 bytes per lane and step (a rewritten entry is a contig of a few hundred residues: one to three steps).
-__global__ __launch_bounds__(256) void appendOutKernel(SeqView s, const uint32_t *__restrict__ flags, const uint32_t *__restrict__ newLen,
-                                                       const uint64_t *__restrict__ newStart, const char *arena,
-                                                       const uint64_t *__restrict__ appOff, uint64_t heapBase, const uint32_t *__restrict__ keep,
-                                                       const uint64_t *__restrict__ keepPos, const uint32_t *__restrict__ inKey,
-                                                       char *heap, uint64_t *__restrict__ outOffArr, uint32_t *__restrict__ outLen, uint32_t *__restrict__ outKey,
-                                                       unsigned char *__restrict__ changedOut) {
-    // (arena and heap are NOT restrict: cyclecheck and findassemblystart pass the heap itself as the arena — disjoint ranges of one buffer)
-    const int lane = laneId();
-    for (uint32_t id0 = (blockIdx.x * 256 + (threadIdx.x & ~63u)); id0 < s.n; id0 += gridDim.x * 256) {
-        const uint32_t id = id0 + (uint32_t) lane;
-        bool ext = false; uint32_t L = 0; uint64_t srcOff = 0, o = 0;
-        if (id < s.n && keep[id]) {
-            ext = (flags[id] & 0x20u) != 0;
-            if (ext) { L = newLen[id]; o = heapBase + appOff[id]; srcOff = newStart[id]; }
-            else { L = s.len[id]; o = s.off[id]; }
-            const uint64_t j = keepPos[id];
-            outOffArr[j] = o; outLen[j] = L; outKey[j] = inKey[id];
-            if (changedOut) changedOut[j] = ext ? 1 : 0;
-        }
-        unsigned long long m = __ballot(ext);
-        while (m) {
-            const int src = __ffsll((long long) m) - 1;
-            m &= m - 1;
-            const uint32_t cl = (uint32_t) __shfl((int) L, src, 64);
-            const uint64_t co = (uint64_t) __shfl((unsigned long long) o, src, 64), cs = (uint64_t) __shfl((unsigned long long) srcOff, src, 64);
-            const char *from = arena + cs; char *dst = heap + co;
-            for (unsigned p = 8u * (unsigned) lane; p < cl; p += 512u) {
-                const uint64_t x = loadU64Unaligned(from + p);                           // buffers are padded past their ends
-                if (p + 8 <= cl) storeU64Unaligned(dst + p, x); else storeTail(dst + p, x, cl - p);
-            }
-            if (lane == 0) { dst[cl] = '\n'; dst[cl + 1] = '\0'; }
-        }
-    }
-}
-
-// origin of every entry of an output DB in the anchor DB of kmermatcher's position cache (plasship_seqdb::d_origin; round 6): a carried-over
-// entry keeps the id its source had there (the source's own id when the source IS the anchor), a rewritten entry has none
-__global__ __launch_bounds__(256) void originOutKernel(uint32_t n, const uint32_t *__restrict__ flags, const uint32_t *__restrict__ keep, const uint64_t *__restrict__ keepPos,
-                                                       const uint32_t *__restrict__ srcOrigin, uint32_t *__restrict__ outOrigin) {
-    for (uint32_t id = blockIdx.x * 256 + threadIdx.x; id < n; id += gridDim.x * 256)
-        if (keep[id]) outOrigin[keepPos[id]] = (flags[id] & 0x20u) ? 0xFFFFFFFFu : (srcOrigin ? srcOrigin[id] : id);
-}
-
-template <int G, int U>
-__global__ __launch_bounds__(256) void writeOutKernel(SeqView s, const uint32_t *__restrict__ flags, const uint32_t *__restrict__ newLen,
-                                                      const uint64_t *__restrict__ newStart, const char *__restrict__ arena,
-                                                      const uint64_t *__restrict__ outOff, const uint32_t *__restrict__ keep,
-                                                      const uint64_t *__restrict__ keepPos, const uint32_t *__restrict__ inKey,
-                                                      char *__restrict__ outData, uint64_t *__restrict__ outOffArr, uint32_t *__restrict__ outLen, uint32_t *__restrict__ outKey,
-                                                      unsigned char *__restrict__ changedOut) {
-    // G lanes per sequence, 8 bytes per lane and step: 8 lanes take a read fragment (~46 residues) in one step with most lanes busy,
-    // eight sequences per wavefront; contigs take a few steps of contiguous 64-byte pieces.  A sequence is a chain of dependent
-    // round trips (what to copy -> the bytes -> the store) and the kernel is bound by the number of chains in flight (round 3: the
-    // wavefronts were parked on memory 89 % of their cycles at 2 TB/s), so a group works on U sequences at a time: the U sets of
-    // metadata are requested together, then the U first pieces.
-    const int gl = threadIdx.x & (G - 1);
-    constexpr int groupsPerBlock = 256 / G;
-    const uint32_t stride = gridDim.x * groupsPerBlock;
-    for (uint32_t id0 = blockIdx.x * groupsPerBlock + (threadIdx.x / G); id0 < s.n; id0 += stride * U) {
-        uint32_t L[U]; const char *src[U]; uint64_t o[U]; bool k[U]; uint64_t w[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t id = id0 + (uint32_t) u * stride;
-            k[u] = id < s.n && keep[id] != 0;
-            L[u] = 0; src[u] = s.data; o[u] = 0;
-            if (k[u]) {
-                const uint32_t f = flags[id]; const uint32_t l0 = s.len[id]; const uint64_t o0 = s.off[id];
-                o[u] = outOff[id];
-                const bool ext = (f & 0x20u) != 0;
-                L[u] = ext ? newLen[id] : l0;
-                src[u] = ext ? (arena + newStart[id]) : (s.data + o0);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) w[u] = (k[u] && 8u * (unsigned) gl < L[u]) ? loadU64Unaligned(src[u] + 8 * gl) : 0ULL;     // buffers are padded past their ends
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (!k[u]) continue;
-            const uint32_t id = id0 + (uint32_t) u * stride;
-            const unsigned i = 8u * (unsigned) gl;
-            char *dst = outData + o[u];
-            if (i + 8 <= L[u]) storeU64Unaligned(dst + i, w[u]);
-            else if (i < L[u]) storeTail(dst + i, w[u], L[u] - i);
-            for (unsigned p = i + 8u * G; p < L[u]; p += 8u * G) {                       // the rest of a contig
-                const uint64_t x = loadU64Unaligned(src[u] + p);
-                if (p + 8 <= L[u]) storeU64Unaligned(dst + p, x);
-                else storeTail(dst + p, x, L[u] - p);
-            }
-            if (gl == 0) {
-                dst[L[u]] = '\n'; dst[L[u] + 1] = '\0';
-                const uint64_t j = keepPos[id];
-                outOffArr[j] = o[u]; outLen[j] = L[u]; outKey[j] = inKey[id];
-                if (changedOut) changedOut[j] = (flags[id] & 0x20u) ? 1 : 0;
-            }
-        }
-    }
-}
 // ---- sharded run: the extended sequences of the owned queries travel to every rank (all-gather), see mergeExtended below ----
 struct __attribute__((aligned(16))) ExtMeta { uint32_t id, len, aaLen, pad; };
 __global__ void extMarkKernel(uint32_t n, const uint32_t *__restrict__ flags, const uint32_t *__restrict__ newLen, const uint32_t *__restrict__ aaNewLen,
@@ -1712,13 +1596,6 @@ __global__ void orFlagsKernel(const uint32_t *__restrict__ all, uint32_t n, int 
     }
 }
 
-__global__ void maxU32Kernel(const uint32_t *__restrict__ v, uint64_t n, uint32_t *__restrict__ out) {
-    uint32_t m = 0;
-    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t) gridDim.x * blockDim.x) m = max(m, v[i]);
-    m = (uint32_t) waveReduceMax((int) m);
-    if (laneId() == 0) atomicMax(out, m);
-}
-
 }  // namespace plasship
 using namespace plasship;
 
@@ -1756,144 +1633,32 @@ static int ambTableInsert(plasship_ctx *ctx, const uint32_t *tuples, uint32_t n)
     return PLASSHIP_OK;
 }
 
-// builds one output DB (extended entries from the arena + carried-over entries of `db`), entries in key order.
-// mode 0: the DB shares `db`'s heap when it has one with room (appendOutKernel: only the rewritten entries move); else its entries are
-//         written back to back into a NEW heap with room for the iterations to come (as much again as the data, at most PLASSHIP_TUNE_DBHEAP_GB = 16 GB;
-//         PLASSHIP_TUNE_DBHEAP=2: no heaps, every DB in an exact buffer of its own as in rounds 1-3)
-// mode 1: a packed copy in an exact buffer (packedCopyOf)
-static int buildOutputDBImpl(plasship_ctx *ctx, const plasship_seqdb *db, const uint32_t *dFlags, const uint32_t *dNewLen, const uint64_t *dNewStart,
-                             const char *dArena, int keepTarget, void *dTmp, size_t tmpBytes, plasship_seqdb **out,
-                             const void *dExtra, void *hExtra, size_t extraBytes, hipEvent_t doneEvent, int mode, bool noAppend = false) {
-    hipStream_t st = ctx->stream;
-    const uint32_t N = (uint32_t) db->n;
-    const SeqView sv = db->view();
-    const bool useHeaps = mode == 0 && tuneInt("DBHEAP", 1) == 1;
-    // noAppend (the protein-guided path, round 5): the DB is written back to back in key order — the layout of the DB file.  The
-    // reference's proteinaln2nucl and guidedassembleresults read PAST the end of an entry when a protein twin and its ORF / 3 differ in
-    // length, i.e. into the entry that FOLLOWS in the data file; behind an entry appended to a shared heap lies
-    // whatever was appended next.  tests/test_gpu_deep.py::test_four_guided_iterations (round 5) found the difference in the third
-    // guided iteration, the first one whose input DB had appended entries: 3 bytes of one alignment DB in 382 MB.
-    const bool mayAppend = useHeaps && db->heap != nullptr && !noAppend;
-    DevBuf dOutBytes, dKeep, dOutOff, dKeepPos, dMaxLen, dAppBytes, dAppOff;
-    if (dOutBytes.alloc(((size_t) N + 1) * 8) != hipSuccess || dKeep.alloc(((size_t) N + 1) * 4) != hipSuccess || dOutOff.alloc(((size_t) N + 2) * 8) != hipSuccess ||
-        dKeepPos.alloc(((size_t) N + 2) * 8) != hipSuccess || dMaxLen.alloc(4) != hipSuccess ||
-        (mayAppend && (dAppBytes.alloc(((size_t) N + 1) * 8) != hipSuccess || dAppOff.alloc(((size_t) N + 2) * 8) != hipSuccess))) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    if (N) hipLaunchKernelGGL(outLenKernel, dim3(std::min<uint32_t>((N + 255) / 256, 8192)), dim3(256), 0, st, sv, dFlags, dNewLen, keepTarget, dOutBytes.as<uint64_t>(), dKeep.as<uint32_t>(),
-                              mayAppend ? dAppBytes.as<uint64_t>() : (uint64_t *) nullptr);
-    if (exclusiveScanU64(st, dOutBytes.as<uint64_t>(), dOutOff.as<uint64_t>(), N, dTmp, tmpBytes) ||
-        exclusiveScanU32(st, dKeep.as<uint32_t>(), dKeepPos.as<uint64_t>(), N, dTmp, tmpBytes) ||
-        (mayAppend && exclusiveScanU64(st, dAppBytes.as<uint64_t>(), dAppOff.as<uint64_t>(), N, dTmp, tmpBytes))) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
-    uint64_t outBytes = 0, outN = 0, appTotal = 0;
-    PH_CHECK(hipMemcpyAsync(&outBytes, dOutOff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    PH_CHECK(hipMemcpyAsync(&outN, dKeepPos.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    if (mayAppend) PH_CHECK(hipMemcpyAsync(&appTotal, dAppOff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    PH_CHECK(plasship::streamSync(st));
-    PH_CHECK(hipGetLastError());
-    std::unique_ptr<plasship_seqdb> holder(new plasship_seqdb());   // released to the caller on success only
-    plasship_seqdb *o = holder.get();
-    o->dbtype = db->dbtype; o->n = (size_t) outN; o->dataBytes = outBytes; o->residues = outBytes - 2 * outN; o->hostIndexValid = false;
-    if (o->d_off.allocLong((outN + 1) * 8) != hipSuccess || o->d_len.allocLong((outN + 1) * 4) != hipSuccess || o->d_key.allocLong((outN + 1) * 4) != hipSuccess) {
-        setError("plasship_assemble: out of device memory for the output DB's index"); return PLASSHIP_ERR_DEVICE;
-    }
-    // lineage: the extended / cut entries marked (one byte per NEW id); same ids as `db` if nothing was dropped (kmermatcher's
-    // selected-window cache needs that), else only "an unmarked entry is an entry of `db`" (cyclecheck's known-linear entries)
-    if (outN && mode == 0) {
-        if (o->d_changed.allocLong((size_t) outN) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-        o->ancestorGen = db->gen;
-        if (outN == N) o->parentGen = db->gen;
-    }
-    // ... and, when `db` is the anchor of kmermatcher's position cache or descends from it, the id every carried-over entry had in the anchor
-    if (outN && mode == 0 && ctx->kmPosCache.valid && ctx->kmPosCache.gen != 0) {
-        const uint64_t anchor = ctx->kmPosCache.gen;
-        const bool isAnchor = db->gen == anchor, descends = !isAnchor && db->originGen == anchor && db->d_origin.p != nullptr;
-        if (isAnchor || descends) {
-            if (o->d_origin.allocLong((size_t) outN * 4) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-            o->originGen = anchor;
-            hipLaunchKernelGGL(originOutKernel, dim3(std::min<uint32_t>((N + 255) / 256, 4096)), dim3(256), 0, st, N, dFlags, (const uint32_t *) dKeep.as<uint32_t>(), (const uint64_t *) dKeepPos.as<uint64_t>(),
-                               descends ? (const uint32_t *) db->d_origin.as<uint32_t>() : (const uint32_t *) nullptr, o->d_origin.as<uint32_t>());
-        }
-    }
-    // room in the shared heap?  (the reservation is atomic: two DBs derived from one parent get disjoint ranges)
-    bool append = false; uint64_t heapBase = 0;
-    if (mayAppend) {                                          // (the reservation commits only if it fits: a DB that does not fit leaves the heap's room to its siblings)
-        uint64_t cur = db->heap->used.load();
-        while (cur + appTotal + 64 <= db->heap->buf.bytes) {
-            if (db->heap->used.compare_exchange_weak(cur, cur + appTotal)) { heapBase = cur; append = true; break; }
-        }
-    }
-    if (append) {
-        o->heap = db->heap; o->contiguous = false;
-        if (N) hipLaunchKernelGGL(appendOutKernel, dim3(std::min<uint32_t>((N + 255) / 256, (uint32_t) ctx->numCU * 16u)), dim3(256), 0, st, sv, dFlags, dNewLen, dNewStart, dArena,
-                                  (const uint64_t *) dAppOff.as<uint64_t>(), heapBase, (const uint32_t *) dKeep.as<uint32_t>(), (const uint64_t *) dKeepPos.as<uint64_t>(), (const uint32_t *) db->d_key.as<uint32_t>(),
-                                  db->heap->buf.as<char>(), o->d_off.as<uint64_t>(), o->d_len.as<uint32_t>(), o->d_key.as<uint32_t>(), o->d_changed.as<unsigned char>());
-    } else {
-        char *dst = nullptr;
-        if (useHeaps && !noAppend) {                           // (noAppend: nobody will ever append behind this DB — an exact buffer, no slack: ADVICE r5)
-            o->heap = std::make_shared<SeqHeap>();
-            // room for the entries the next iterations rewrite (25-35 % of the data per iteration at 50 M reads): as much again as the
-            // data, but no more than PLASSHIP_TUNE_DBHEAP_GB (default 16; round 4: 8 — the sparse alignment lists of round 5 freed 14 GB) — kmermatcher's record arrays need 170 of the 288 GB there
-            const uint64_t cap = outBytes + std::min<uint64_t>(outBytes, (uint64_t) tuneInt("DBHEAP_GB", 16) << 30) + 4096;
-            if (o->heap->buf.allocLong(cap) == hipSuccess) { o->heap->used = outBytes; dst = o->heap->buf.as<char>(); }
-            else o->heap.reset();                             // no room for the slack: an exact buffer will do
-        }
-        if (!dst) {
-            if (o->d_data.allocLong(outBytes + 64) != hipSuccess) {
-                size_t fr = 0, tt = 0; (void) hipMemGetInfo(&fr, &tt);
-                setError("plasship_assemble: out of device memory for the output DB (" + std::to_string(outBytes) + " bytes, " + std::to_string(outN) + " sequences; device free " + std::to_string(fr) + " of " + std::to_string(tt) + ")"); return PLASSHIP_ERR_DEVICE;
-            }
-            dst = o->d_data.as<char>();
-        }
-        o->contiguous = true;
-        PH_CHECK(hipMemsetAsync(dst + outBytes, 0, 64, st));
-        if (N) {
-            // (2 and 4 sequences in flight per lane group changed nothing — profiles/r03_ab_knobs.txt: the kernel is not bound by its chains of round trips)
-            const unsigned woGrid = std::min<uint32_t>((N + 15) / 16, (uint32_t) ctx->numCU * 16u);
-            hipLaunchKernelGGL((writeOutKernel<8, 1>), dim3(woGrid), dim3(256), 0, st, sv, dFlags, dNewLen,
-                               dNewStart, dArena, dOutOff.as<uint64_t>(), dKeep.as<uint32_t>(), dKeepPos.as<uint64_t>(), db->d_key.as<uint32_t>(),
-                               dst, o->d_off.as<uint64_t>(), o->d_len.as<uint32_t>(), o->d_key.as<uint32_t>(), o->d_changed.as<unsigned char>());
-        }
-    }
-    PH_CHECK(hipMemcpyAsync(o->d_off.as<uint64_t>() + outN, &outBytes, 8, hipMemcpyHostToDevice, st));
-    PH_CHECK(hipMemsetAsync(dMaxLen.p, 0, 4, st));
-    if (outN) hipLaunchKernelGGL(maxU32Kernel, dim3(std::min<uint64_t>((outN + 255) / 256, 1024)), dim3(256), 0, st, o->d_len.as<uint32_t>(), outN, dMaxLen.as<uint32_t>());
-    uint32_t maxLen = 0;
-    if (doneEvent) PH_CHECK(hipEventRecord(doneEvent, st));
-    PH_CHECK(hipMemcpyAsync(&maxLen, dMaxLen.p, 4, hipMemcpyDeviceToHost, st));
-    if (dExtra) PH_CHECK(hipMemcpyAsync(hExtra, dExtra, extraBytes, hipMemcpyDeviceToHost, st));      // the caller's counters ride along
-    PH_CHECK(plasship::streamSync(st));
-    PH_CHECK(hipGetLastError());
-    o->maxEntryLen = maxLen + 2;
-    o->buildAppendedBytes = append ? appTotal : 0; o->buildCopiedBytes = append ? 0 : outBytes;
-    *out = holder.release();
-    return PLASSHIP_OK;
-}
-int plasship::buildOutputDB(plasship_ctx *ctx, const plasship_seqdb *db, const uint32_t *dFlags, const uint32_t *dNewLen, const uint64_t *dNewStart,
-                            const char *dArena, int keepTarget, void *dTmp, size_t tmpBytes, plasship_seqdb **out,
-                            const void *dExtra, void *hExtra, size_t extraBytes, hipEvent_t doneEvent, bool noAppend) {
-    return buildOutputDBImpl(ctx, db, dFlags, dNewLen, dNewStart, dArena, keepTarget, dTmp, tmpBytes, out, dExtra, hExtra, extraBytes, doneEvent, 0, noAppend);
-}
-int plasship::packedCopyOf(plasship_ctx *ctx, const plasship_seqdb *db, std::unique_ptr<plasship_seqdb> &out) {
-    const uint32_t N = (uint32_t) db->n;
-    DevBuf dFlags, dTmp; const size_t tmpBytes = exclusiveScanTmpBytes((size_t) N + 2);
-    if (dFlags.alloc(((size_t) N + 1) * 4) != hipSuccess || dTmp.alloc(tmpBytes) != hipSuccess) { setError("plasship: out of device memory while packing a sequence DB"); return PLASSHIP_ERR_DEVICE; }
-    PH_CHECK(hipMemsetAsync(dFlags.p, 0, ((size_t) N + 1) * 4, ctx->stream));
-    plasship_seqdb *o = nullptr;
-    const int rc = buildOutputDBImpl(ctx, db, dFlags.as<uint32_t>(), nullptr, nullptr, nullptr, 1, dTmp.p, tmpBytes, &o, nullptr, nullptr, 0, nullptr, 1);
-    if (rc) return rc;
-    o->maxEntryLen = db->maxEntryLen;
-    out.reset(o);
-    return PLASSHIP_OK;
+// ctx->ev slots of an assembleresults call.  The three timed tiers: queues of at most 16 alignments (a nucleotide DB: all its passes, every
+// tier's kernel and the re-runs after a missing comparator tuple, as ONE interval), of 17..64, and of more than 64 (plasship_assemble_stats::ms_tier_kernel);
+// tier t's interval is the pair of slots at ASM_EV_T16_BEGIN + 2 * t
+enum AsmEvent { ASM_EV_BEGIN = 0, ASM_EV_END, ASM_EV_T16_BEGIN, ASM_EV_T16_END, ASM_EV_T64_BEGIN, ASM_EV_T64_END, ASM_EV_QUEUE_BEGIN, ASM_EV_QUEUE_END };
+
+namespace {
+// one side of an extension: the sequences of the DB itself, or (guidedassembleresults) their protein twins
+struct ExtSide {
+    DevBuf leftCap, bytes, arenaOff;      // per query: bytes reserved left of the original query, arena bytes, arena offset (their prefix sum)
+    DevBuf arena, newLen, newStart;       // the arena; per query: length and absolute arena offset of the extended query
+};
+// nuclassembleresults / guidedassembleresults: what runNuclPasses allocates.  The caller's: it lives until the output DB is written.
+struct NuclWork { DevBuf heap, need, redo[2], cnt; };
 }
 
 // Sharded run (plasship_ctx_set_comm): every rank has extended the queries it owns.  The extended sequences (and, for the
 // guided variant, their protein twins) are packed, all-gathered and entered into flags / newLen / newStart of every rank as if
 // it had produced them itself, so that buildOutputDB writes the complete DB everywhere; the "consumed" bits only matter with
 // --keep-target 0 and are OR-ed over the ranks then.  gathered / gatheredAa replace the local arenas.
-static int mergeExtended(plasship_ctx *ctx, uint32_t N, bool guided, int keepTarget, uint32_t *dFlags, uint32_t *dNewLen, uint64_t *dNewStart, const char *dArena,
-                         uint32_t *dAaNewLen, uint64_t *dAaNewStart, const char *dAaArena, void *dTmp, size_t tmpBytes, DevBuf &gathered, DevBuf &gatheredAa) {
+static int mergeExtended(plasship_ctx *ctx, uint32_t N, bool guided, int keepTarget, uint32_t *dFlags, const ExtSide &side, const ExtSide &aaSide,
+                         void *dTmp, size_t tmpBytes, DevBuf &gathered, DevBuf &gatheredAa) {
     hipStream_t st = ctx->stream;
     const plasship_comm *cm = commOf(ctx);
     const int W = cm->world;
+    uint32_t *dNewLen = side.newLen.as<uint32_t>(), *dAaNewLen = aaSide.newLen.as<uint32_t>();
+    uint64_t *dNewStart = side.newStart.as<uint64_t>(), *dAaNewStart = aaSide.newStart.as<uint64_t>();
     DevBuf dKeep, dBytes, dAaBytes, dPos, dOff, dAaOff;
     if (dKeep.alloc(((size_t) N + 1) * 4) != hipSuccess || dBytes.alloc(((size_t) N + 1) * 8) != hipSuccess || dPos.alloc(((size_t) N + 2) * 8) != hipSuccess ||
         dOff.alloc(((size_t) N + 2) * 8) != hipSuccess || (guided && (dAaBytes.alloc(((size_t) N + 1) * 8) != hipSuccess || dAaOff.alloc(((size_t) N + 2) * 8) != hipSuccess))) {
@@ -1914,7 +1679,7 @@ static int mergeExtended(plasship_ctx *ctx, uint32_t N, bool guided, int keepTar
         setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE;
     }
     if (N) hipLaunchKernelGGL(extPackKernel, dim3(std::min<uint32_t>((N + 15) / 16, (uint32_t) ctx->numCU * 16)), dim3(256), 0, st, N, dKeep.as<uint32_t>(), dPos.as<uint64_t>(), dOff.as<uint64_t>(),
-                              guided ? dAaOff.as<uint64_t>() : (const uint64_t *) nullptr, dNewLen, dNewStart, dArena, dAaNewLen, dAaNewStart, dAaArena,
+                              guided ? dAaOff.as<uint64_t>() : (const uint64_t *) nullptr, dNewLen, dNewStart, side.arena.as<char>(), dAaNewLen, dAaNewStart, aaSide.arena.as<char>(),
                               dMeta.as<ExtMeta>(), dPacked.as<char>(), guided ? dAaPacked.as<char>() : (char *) nullptr);
     PH_TRACE(st, "assemble: packed the extended sequences");
     DevBuf gMeta; std::vector<uint64_t> rb(W), rbMeta(W), rbSeq(W), rbAa(W);
@@ -1990,170 +1755,75 @@ static int asmHistRecord(hipStream_t st, uint32_t N, const uint64_t *dQoff, cons
     return PLASSHIP_OK;
 }
 
-// aaDb == nullptr: assembleresults (protein DB) / nuclassembleresults (nucleotide DB); aaDb != nullptr: guidedassembleresults
-static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_seqdb *aaDb, const plasship_alns *al,
-                        const plasship_assemble_params *par, plasship_seqdb **out, plasship_seqdb **outAa, plasship_assemble_stats *stats) {
-    const bool guided = aaDb != nullptr;
-    // protein DB -> assembleresults; nucleotide DB -> nuclassembleresults (what the nuclassemble workflow runs on reads)
-    const bool nucl = db->dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES;
-    if (!nucl && db->dbtype != PLASSHIP_DBTYPE_AMINO_ACIDS) { setError("plasship_assemble: the sequence DB is neither amino acids nor nucleotides"); return PLASSHIP_ERR_ARG; }
-    if (par->rescore_mode != 3) { setError("plasship_assemble: only --rescore-mode 3"); return PLASSHIP_ERR_UNSUPPORTED; }
-    if (al->nQueries != db->n) { setError("plasship_assemble: alignment list does not belong to the DB"); return PLASSHIP_ERR_ARG; }
-    PH_ENTER(ctx);
+// nuclassembleresults / guidedassembleresults: the passes over the queries of a nucleotide DB
+static int runNuclPasses(plasship_ctx *ctx, AsmArgs &a, bool guided, uint32_t N, uint64_t nLines, const uint64_t *dBytes, NuclWork &nw) {
     hipStream_t st = ctx->stream;
-    const uint32_t N = (uint32_t) db->n;
-    // nuclassembleresults / guidedassembleresults rank a query's alignment with itself among the others (it enters the heap like any hit);
-    // assembleresults pops and discards it (assembleresult.cpp:203-209): only the former need the identity pairs scored (common.hpp: selfPending)
-    if (nucl) { const int rcS = finishSelfAlns(ctx, al); if (rcS) return rcS; }
-    const uint64_t nLines = al->nSlots;                     // record slots (a sparse list: holes included, common.hpp); al->nLines of them are alignments
-    DevBuf dLeftCap, dBytes, dArenaOff, dTmp, dItems, dFlags, dNewLen, dNewStart, dMat, dStats, dArena;
-    const size_t tmpBytes = exclusiveScanTmpBytes((size_t) N + 2);
-    if (dLeftCap.alloc(((size_t) N + 1) * 4) != hipSuccess || dBytes.alloc(((size_t) N + 1) * 8) != hipSuccess || dArenaOff.alloc(((size_t) N + 2) * 8) != hipSuccess ||
-        dTmp.alloc(tmpBytes) != hipSuccess || dItems.alloc(std::max<uint64_t>(nLines, 1) * sizeof(Item)) != hipSuccess || dFlags.alloc(((size_t) N + 1) * 4) != hipSuccess ||
-        dNewLen.alloc(((size_t) N + 1) * 4) != hipSuccess || dNewStart.alloc(((size_t) N + 1) * 8) != hipSuccess || dMat.alloc(123 * 123) != hipSuccess || dStats.alloc(128) != hipSuccess) {
-        setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE;
+    const uint32_t needCap = 1u << 16;
+    if (nw.heap.alloc(std::max<uint64_t>(nLines, 1) * 12) != hipSuccess || nw.need.alloc((size_t) needCap * 16) != hipSuccess || nw.redo[0].alloc(((size_t) N + 1) * 4) != hipSuccess ||
+        nw.redo[1].alloc(((size_t) N + 1) * 4) != hipSuccess || nw.cnt.alloc(8) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+    a.heap = nw.heap.as<uint32_t>();
+    if (!ctx->d_cmpCache.p) {
+        const size_t cb = (size_t) CMP_LEN * CMP_MM * CMP_LEN * CMP_MM;
+        if (ctx->d_cmpCache.alloc(cb) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+        PH_CHECK(hipMemsetAsync(ctx->d_cmpCache.p, 0, cb, st));
     }
-    PH_CHECK(hipMemsetAsync(dFlags.p, 0, ((size_t) N + 1) * 4, st));
-    PH_CHECK(hipMemsetAsync(dNewLen.p, 0, ((size_t) N + 1) * 4, st));
-    PH_CHECK(hipMemsetAsync(dStats.p, 0, 128, st));
-    PH_CHECK(hipMemcpyAsync(dMat.p, asciiSubMat(nucl), 123 * 123, hipMemcpyHostToDevice, st));
-    { const int rcOL = ensureOffLen(ctx, db); if (rcOL) return rcOL; }          // the extension kernels look up random targets
-    const SeqView sv = db->view();
-    PH_CHECK(hipEventRecord(ctx->ev[0], st));
-    // work lists by queue size: [0] 9..16 alignments, [1] <= 32, [2] <= 64, [3] more, [4] <= 8 (tiers: arenaSizeKernel; lists: tierListKernel)
-    const uint32_t nTiles = (uint32_t) (((size_t) N + SCAN_TILE - 1) / SCAN_TILE);
-    DevBuf dBigList, dMidList, dMid32List, dSmallList, dNarrowList, dTierOf, dTierPart, dAaLeftCap, dAaBytes, dAaArenaOff, dAaArena, dAaNewLen, dAaNewStart;
-    if (guided && (dAaLeftCap.alloc(((size_t) N + 1) * 4) != hipSuccess || dAaBytes.alloc(((size_t) N + 1) * 8) != hipSuccess || dAaArenaOff.alloc(((size_t) N + 2) * 8) != hipSuccess ||
-                   dAaNewLen.alloc(((size_t) N + 1) * 4) != hipSuccess || dAaNewStart.alloc(((size_t) N + 1) * 8) != hipSuccess)) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    if (guided) PH_CHECK(hipMemsetAsync(dAaNewLen.p, 0, ((size_t) N + 1) * 4, st));
-    if (dBigList.alloc(((size_t) N + 1) * 4) != hipSuccess || dMidList.alloc(((size_t) N + 1) * 4) != hipSuccess || dMid32List.alloc(((size_t) N + 1) * 4) != hipSuccess ||
-        dSmallList.alloc(((size_t) N + 1) * 4) != hipSuccess || (!nucl && dNarrowList.alloc(((size_t) N + 1) * 4) != hipSuccess) || dTierOf.alloc((size_t) N + 8) != hipSuccess ||
-        dTierPart.alloc(((size_t) N_TIERS * (nTiles + 1) + 1) * 8) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    DevBuf dQSum, dQSumAa, dQCan;
-    if (dQSum.alloc(((size_t) N + 1) * 8) != hipSuccess || dQCan.alloc(((size_t) N + 1) * 4) != hipSuccess || (guided && dQSumAa.alloc(((size_t) N + 1) * 8) != hipSuccess)) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-    PH_CHECK(hipMemsetAsync(dQSum.p, 0, ((size_t) N + 1) * 8, st));
-    PH_CHECK(hipMemsetAsync(dQCan.p, 0, ((size_t) N + 1) * 4, st));
-    if (guided) PH_CHECK(hipMemsetAsync(dQSumAa.p, 0, ((size_t) N + 1) * 8, st));
-    if (nLines) hipLaunchKernelGGL(arenaSumKernel, dim3((unsigned) std::min<uint64_t>((nLines + 255) / 256, (uint64_t) ctx->numCU * 32)), dim3(256), 0, st, al->d_recs.as<AlnRec>(), (uint64_t) nLines,
-                                       (uint64_t) par->max_seq_len, dQSum.as<unsigned long long>(), guided ? dQSumAa.as<unsigned long long>() : (unsigned long long *) nullptr, dQCan.as<uint32_t>(),
-                                       (nucl && !guided) ? 1 : 0);
-    if (N) hipLaunchKernelGGL(arenaSizeKernel, dim3(std::min<uint32_t>((N + 255) / 256, 8192)), dim3(256), 0, st, sv, al->d_qoff.as<uint64_t>(), (const unsigned long long *) dQSum.as<unsigned long long>(),
-                              (const unsigned long long *) dQSumAa.as<unsigned long long>(), (const uint32_t *) dQCan.as<uint32_t>(), dLeftCap.as<uint32_t>(), dBytes.as<uint64_t>(), nucl ? 1 : 0, (uint64_t) 1 << 30,
-                              dTierOf.as<uint8_t>(),
-                              guided ? aaDb->d_len.as<uint32_t>() : (const uint32_t *) nullptr, dAaLeftCap.as<uint32_t>(), guided ? dAaBytes.as<uint64_t>() : (uint64_t *) nullptr);
-    if (guided && exclusiveScanU64(st, dAaBytes.as<uint64_t>(), dAaArenaOff.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
-    PH_CHECK(hipMemsetAsync(dTierPart.p, 0, ((size_t) N_TIERS * (nTiles + 1) + 1) * 8, st));
-    if (nTiles) hipLaunchKernelGGL(tierCountKernel, dim3(nTiles), dim3(SCAN_BLOCK), 0, st, (const uint8_t *) dTierOf.as<uint8_t>(), N, dTierPart.as<uint64_t>(), nTiles);
-    // ONE scan over the five rows end to end, in place (entry [nTiles] of a row is 0): a row's entries minus its first one are the tiles' offsets in
-    // the tier's list, and the first entry of the next row minus its own is the tier's total
-    if (exclusiveScanU64(st, dTierPart.as<uint64_t>(), dTierPart.as<uint64_t>(), (size_t) N_TIERS * (nTiles + 1), dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
-    {
-        TierLists tl;
-        tl.list[0] = dSmallList.as<uint32_t>(); tl.list[1] = dMid32List.as<uint32_t>(); tl.list[2] = dMidList.as<uint32_t>(); tl.list[3] = dBigList.as<uint32_t>();
-        tl.list[TIER_NARROW] = dNarrowList.as<uint32_t>();              // (not allocated for a nucleotide DB, whose queries have tiers 0 and 1 only)
-        if (nTiles) hipLaunchKernelGGL(tierListKernel, dim3(nTiles), dim3(SCAN_BLOCK), 0, st, (const uint8_t *) dTierOf.as<uint8_t>(), N, (const uint64_t *) dTierPart.as<uint64_t>(), nTiles, tl);
+    a.cmpCache = ctx->d_cmpCache.as<uint8_t>();
+    a.needKeys = nw.need.as<uint32_t>(); a.needCount = nw.cnt.as<uint32_t>(); a.needCap = needCap; a.redoCount = nw.cnt.as<uint32_t>() + 1;
+    PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_T16_BEGIN], st));
+    // Pass 0 runs every query; a query that needs a comparator decision the table lacks leaves no trace and is
+    // run again once the host has evaluated the tuple (the set of such tuples is small and recurs, so the table
+    // kept in the context makes later calls single-pass).
+    // pass 0: queries with up to 256 hits one thread each, the rest one wavefront each; later passes (queries that met
+    // a comparator tuple the table lacked) one wavefront each
+    uint32_t nWork = a.nSmall + a.nMid32;
+    for (int pass = 0; nWork > 0; pass++) {
+        if (pass > 256) { setError("plasship_assemble: comparator table did not converge"); return PLASSHIP_ERR_DEVICE; }
+        a.ambKeys = ctx->d_ambKeys.as<uint32_t>(); a.ambVals = ctx->d_ambVals.as<uint8_t>(); a.ambMask = ctx->ambSlots ? ctx->ambSlots - 1 : 0;
+        a.redoList = nw.redo[pass & 1].as<uint32_t>();
+        PH_CHECK(hipMemsetAsync(nw.cnt.p, 0, 8, st));
+        auto launchWave = [&](const uint32_t *list, uint32_t n) {
+            if (!n) return;
+            a.queryList = list; a.nQueryList = n;
+            if (guided) hipLaunchKernelGGL(assembleNuclKernel<true>, dim3(std::min<uint32_t>(n, (uint32_t) ctx->numCU * 16)), dim3(64), 0, st, a);
+            else hipLaunchKernelGGL(assembleNuclKernel<false>, dim3(std::min<uint32_t>(n, (uint32_t) ctx->numCU * 16)), dim3(64), 0, st, a);
+        };
+        if (pass == 0) {
+            if (a.nSmall) {
+                // the list in work classes (nuclClassScatterKernel): the thread-per-query kernel reads the classed copy
+                DevBuf dCls;
+                if (dCls.alloc(2 * NW_CLASSES * 4) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+                PH_CHECK(hipMemsetAsync(dCls.p, 0, 2 * NW_CLASSES * 4, st));
+                const unsigned g = std::min<uint32_t>((a.nSmall + 255) / 256, (uint32_t) ctx->numCU * 8);
+                hipLaunchKernelGGL(nuclClassCountKernel, dim3(g), dim3(256), 0, st, (const uint32_t *) a.smallList, a.nSmall, dBytes, dCls.as<uint32_t>());
+                hipLaunchKernelGGL(nuclClassScatterKernel, dim3(g), dim3(256), 0, st, (const uint32_t *) a.smallList, a.nSmall, dBytes, dCls.as<uint32_t>(),
+                                   a.midList);          // (the 64-lane list is a protein tier: unused here)
+                a.queryList = a.midList; a.nQueryList = a.nSmall;
+                const uint32_t grid = std::min<uint32_t>((a.nSmall + NT_BLOCK - 1) / NT_BLOCK, (uint32_t) ctx->numCU * 8);
+                if (guided) hipLaunchKernelGGL(assembleNuclThreadKernel<true>, dim3(grid), dim3(NT_BLOCK), 0, st, a);
+                else hipLaunchKernelGGL(assembleNuclThreadKernel<false>, dim3(grid), dim3(NT_BLOCK), 0, st, a);
+            }
+            launchWave(a.mid32List, a.nMid32);
+        } else launchWave(nw.redo[(pass + 1) & 1].as<uint32_t>(), nWork);
+        uint32_t cnt[2] = {0, 0};
+        PH_CHECK(hipMemcpyAsync(cnt, nw.cnt.p, 8, hipMemcpyDeviceToHost, st));
+        PH_CHECK(plasship::streamSync(st));
+        PH_CHECK(hipGetLastError());
+        nWork = cnt[1];
+        if (nWork == 0) break;
+        const uint32_t nNeed = std::min(cnt[0], needCap);
+        if (nNeed == 0) { setError("plasship_assemble: queries aborted without a missing comparator tuple"); return PLASSHIP_ERR_DEVICE; }
+        std::vector<uint32_t> need((size_t) nNeed * 4);
+        PH_COPY_SYNC(ctx->stream, need.data(), nw.need.p, need.size() * 4, hipMemcpyDeviceToHost);
+        const int rc = ambTableInsert(ctx, need.data(), nNeed);
+        if (rc != PLASSHIP_OK) return rc;
     }
-    if (exclusiveScanU64(st, dBytes.as<uint64_t>(), dArenaOff.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
-    uint64_t arenaBytes = 0, aaArenaBytes = 0;
-    uint64_t rowStart[N_TIERS + 1] = {};
-    if (guided) PH_CHECK(hipMemcpyAsync(&aaArenaBytes, dAaArenaOff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    PH_CHECK(hipMemcpyAsync(&arenaBytes, dArenaOff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
-    PH_CHECK(hipMemcpy2DAsync(rowStart, 8, dTierPart.p, (size_t) (nTiles + 1) * 8, 8, N_TIERS + 1, hipMemcpyDeviceToHost, st));
-    PH_CHECK(plasship::streamSync(st));
-    uint32_t cnts[N_TIERS];
-    for (int t = 0; t < N_TIERS; t++) cnts[t] = (uint32_t) (rowStart[t + 1] - rowStart[t]);
-    if (dArena.alloc(arenaBytes + 64) != hipSuccess || (guided && dAaArena.alloc(aaArenaBytes + 64) != hipSuccess)) {
-        size_t fr = 0, tt = 0; (void) hipMemGetInfo(&fr, &tt);
-        setError("plasship_assemble: out of device memory for the extension arena (" + std::to_string(arenaBytes) + " bytes; device free " + std::to_string(fr) + " of " + std::to_string(tt) + ")"); return PLASSHIP_ERR_DEVICE;
-    }
-    HostEvaluer ev(nucl, db->residues);
-    AsmArgs a; memset(&a, 0, sizeof(a));
-    a.s = sv; a.qoff = al->d_qoff.as<uint64_t>(); a.recs = al->d_recs.as<AlnRec>(); a.items = dItems.as<Item>(); a.arenaOff = dArenaOff.as<uint64_t>();
-    a.leftCap = dLeftCap.as<uint32_t>(); a.arena = dArena.as<char>(); a.flags = dFlags.as<uint32_t>(); a.newLen = dNewLen.as<uint32_t>(); a.newStart = dNewStart.as<uint64_t>();
-    a.mat = dMat.as<signed char>(); a.lambda = ev.g[0]; a.logK = ev.logK; a.ln2 = ev.ln2; a.seqIdThr = par->seq_id_thr; a.maxSeqLen = par->max_seq_len; a.rescoreMode = par->rescore_mode;
-    a.ownLaneMin = 6;      // swept 1 / 3 / 6 / 12 / never: 30.4 / 28.4 / 27.9 / 29.9 / 40.3 ms for the two wide tiers (profiles/r05_ab_knobs.txt, call 11)
-    a.stats = dStats.as<unsigned long long>();
-    a.smallList = dSmallList.as<uint32_t>(); a.nSmall = cnts[0];
-    a.narrowList = dNarrowList.as<uint32_t>(); a.nNarrow = cnts[TIER_NARROW];
-    a.mid32List = dMid32List.as<uint32_t>(); a.nMid32 = cnts[1];
-    a.midList = dMidList.as<uint32_t>(); a.nMid = cnts[2];
-    a.bigList = dBigList.as<uint32_t>(); a.nBig = cnts[3];
-    // assembleBigKernel keeps the self hit in its HBM-resident queue (its rank decides what is left queued when the length cap ends the pop
-    // loop, assembleresult.cpp:259-263,285): the identity pairs of ITS queries are scored now (common.hpp: selfPending); the register-queue
-    // kernels never queue the self hit
-    if (!nucl && a.nBig) { const int rcS = finishSelfAlns(ctx, al, dBigList.as<uint32_t>(), a.nBig); if (rcS) return rcS; }
-    std::unique_ptr<plasship_seqdb> aaPacked;                // guided: the twins are read past their end like the reference does (buildOutputDBImpl, noAppend):
-    if (guided && !aaDb->contiguous) {                       // a twin DB that lives in a shared heap is laid out like its DB file first
-        const int rcP = packedCopyOf(ctx, aaDb, aaPacked); if (rcP) return rcP;
-    }
-    if (guided) {
-        a.aa = (aaPacked ? aaPacked.get() : aaDb)->view(); a.aaArena = dAaArena.as<char>(); a.aaArenaOff = dAaArenaOff.as<uint64_t>(); a.aaLeftCap = dAaLeftCap.as<uint32_t>();
-        a.aaNewLen = dAaNewLen.as<uint32_t>(); a.aaNewStart = dAaNewStart.as<uint64_t>();
-    }
-    DevBuf dHeap, dNeed, dRedo[2], dCnt;
-    if (nucl) {
-        const uint32_t needCap = 1u << 16;
-        if (dHeap.alloc(std::max<uint64_t>(nLines, 1) * 12) != hipSuccess || dNeed.alloc((size_t) needCap * 16) != hipSuccess || dRedo[0].alloc(((size_t) N + 1) * 4) != hipSuccess ||
-            dRedo[1].alloc(((size_t) N + 1) * 4) != hipSuccess || dCnt.alloc(8) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-        a.heap = dHeap.as<uint32_t>();
-        if (!ctx->d_cmpCache.p) {
-            const size_t cb = (size_t) CMP_LEN * CMP_MM * CMP_LEN * CMP_MM;
-            if (ctx->d_cmpCache.alloc(cb) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-            PH_CHECK(hipMemsetAsync(ctx->d_cmpCache.p, 0, cb, st));
-        }
-        a.cmpCache = ctx->d_cmpCache.as<uint8_t>();
-        a.needKeys = dNeed.as<uint32_t>(); a.needCount = dCnt.as<uint32_t>(); a.needCap = needCap; a.redoCount = dCnt.as<uint32_t>() + 1;
-        PH_CHECK(hipEventRecord(ctx->ev[2], st));
-        // Pass 0 runs every query; a query that needs a comparator decision the table lacks leaves no trace and is
-        // run again once the host has evaluated the tuple (the set of such tuples is small and recurs, so the table
-        // kept in the context makes later calls single-pass).
-        // pass 0: queries with up to 256 hits one thread each, the rest one wavefront each; later passes (queries that met
-        // a comparator tuple the table lacked) one wavefront each
-        uint32_t nWork = cnts[0] + cnts[1];
-        for (int pass = 0; nWork > 0; pass++) {
-            if (pass > 256) { setError("plasship_assemble: comparator table did not converge"); return PLASSHIP_ERR_DEVICE; }
-            a.ambKeys = ctx->d_ambKeys.as<uint32_t>(); a.ambVals = ctx->d_ambVals.as<uint8_t>(); a.ambMask = ctx->ambSlots ? ctx->ambSlots - 1 : 0;
-            a.redoList = dRedo[pass & 1].as<uint32_t>();
-            PH_CHECK(hipMemsetAsync(dCnt.p, 0, 8, st));
-            auto launchWave = [&](const uint32_t *list, uint32_t n) {
-                if (!n) return;
-                a.queryList = list; a.nQueryList = n;
-                if (guided) hipLaunchKernelGGL(assembleNuclKernel<true>, dim3(std::min<uint32_t>(n, (uint32_t) ctx->numCU * 16)), dim3(64), 0, st, a);
-                else hipLaunchKernelGGL(assembleNuclKernel<false>, dim3(std::min<uint32_t>(n, (uint32_t) ctx->numCU * 16)), dim3(64), 0, st, a);
-            };
-            if (pass == 0) {
-                if (cnts[0]) {
-                    // the list in work classes (nuclClassScatterKernel): the thread-per-query kernel reads the classed copy
-                    DevBuf dCls;
-                    if (dCls.alloc(2 * NW_CLASSES * 4) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
-                    PH_CHECK(hipMemsetAsync(dCls.p, 0, 2 * NW_CLASSES * 4, st));
-                    const unsigned g = std::min<uint32_t>((cnts[0] + 255) / 256, (uint32_t) ctx->numCU * 8);
-                    hipLaunchKernelGGL(nuclClassCountKernel, dim3(g), dim3(256), 0, st, (const uint32_t *) dSmallList.as<uint32_t>(), cnts[0], (const uint64_t *) dBytes.as<uint64_t>(), dCls.as<uint32_t>());
-                    hipLaunchKernelGGL(nuclClassScatterKernel, dim3(g), dim3(256), 0, st, (const uint32_t *) dSmallList.as<uint32_t>(), cnts[0], (const uint64_t *) dBytes.as<uint64_t>(), dCls.as<uint32_t>(),
-                                       dMidList.as<uint32_t>());          // (the 64-lane list is a protein tier: unused here)
-                    a.queryList = dMidList.as<uint32_t>(); a.nQueryList = cnts[0];
-                    const uint32_t grid = std::min<uint32_t>((cnts[0] + NT_BLOCK - 1) / NT_BLOCK, (uint32_t) ctx->numCU * 8);
-                    if (guided) hipLaunchKernelGGL(assembleNuclThreadKernel<true>, dim3(grid), dim3(NT_BLOCK), 0, st, a);
-                    else hipLaunchKernelGGL(assembleNuclThreadKernel<false>, dim3(grid), dim3(NT_BLOCK), 0, st, a);
-                }
-                launchWave(dMid32List.as<uint32_t>(), cnts[1]);
-            } else launchWave(dRedo[(pass + 1) & 1].as<uint32_t>(), nWork);
-            uint32_t cnt[2] = {0, 0};
-            PH_CHECK(hipMemcpyAsync(cnt, dCnt.p, 8, hipMemcpyDeviceToHost, st));
-            PH_CHECK(plasship::streamSync(st));
-            PH_CHECK(hipGetLastError());
-            nWork = cnt[1];
-            if (nWork == 0) break;
-            const uint32_t nNeed = std::min(cnt[0], needCap);
-            if (nNeed == 0) { setError("plasship_assemble: queries aborted without a missing comparator tuple"); return PLASSHIP_ERR_DEVICE; }
-            std::vector<uint32_t> need((size_t) nNeed * 4);
-            PH_COPY_SYNC(ctx->stream, need.data(), dNeed.p, need.size() * 4, hipMemcpyDeviceToHost);
-            const int rc = ambTableInsert(ctx, need.data(), nNeed);
-            if (rc != PLASSHIP_OK) return rc;
-        }
-        PH_CHECK(hipEventRecord(ctx->ev[3], st));
-        for (int e = 4; e <= 7; e++) PH_CHECK(hipEventRecord(ctx->ev[e], st));
-    } else {
+    for (int e = ASM_EV_T16_END; e <= ASM_EV_QUEUE_END; e++) PH_CHECK(hipEventRecord(ctx->ev[e], st));      // (the other two tiers: empty intervals)
+    return PLASSHIP_OK;
+}
+
+// assembleresults: the tiers of a protein DB, narrow queues first
+static int launchProteinTiers(plasship_ctx *ctx, AsmArgs &a, uint32_t N) {
+    hipStream_t st = ctx->stream;
     // (round 4: the protein tiers' lists in work classes like the nucleotide list changed nothing — 82.2 against 81.0 ms for the stage: the
     //  tiers already group the queries by queue size, and id order keeps a wavefront's alignment records adjacent; profiles/r04_ab_knobs.txt)
     // wavefronts per SIMD of the register-queue kernels: the grid is what the CUs hold at once
@@ -2161,16 +1831,16 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
     const dim3 g16(std::min<uint32_t>((a.nSmall + 15) / 16, (uint32_t) ctx->numCU * 5u)), g64(std::min<uint32_t>((a.nMid + 3) / 4, (uint32_t) ctx->numCU * 4u));
     // (round 5: the four tiers — disjoint queries — launched side by side on four streams, so that one tier's tail of long queues lies under
     //  the next tier: 88.8 against 82.7 ms for the stage; the tiers' wavefronts evict each other's lines.  profiles/r05_ab_knobs.txt)
-    PH_CHECK(hipEventRecord(ctx->ev[2], st));
+    PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_T16_BEGIN], st));
     // queues of at most 8 alignments, 8 lanes each: the same instruction serves twice the queries, and a wavefront keeps eight chains of round trips in flight
     if (a.nNarrow) hipLaunchKernelGGL((assembleGroupKernel<8, ASM8_WPE>), dim3(std::min<uint32_t>((a.nNarrow + 31) / 32, (uint32_t) ctx->numCU * ASM8_WPE)), dim3(256), 0, st, a);
     if (a.nSmall) hipLaunchKernelGGL((assembleGroupKernel<16, 5>), g16, dim3(256), 0, st, a);
-    PH_CHECK(hipEventRecord(ctx->ev[3], st));
-    PH_CHECK(hipEventRecord(ctx->ev[4], st));
+    PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_T16_END], st));
+    PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_T64_BEGIN], st));
     if (a.nMid32) hipLaunchKernelGGL((assembleGroupKernel<32, 5>), dim3(std::min<uint32_t>((a.nMid32 + 7) / 8, (uint32_t) ctx->numCU * 5u)), dim3(256), 0, st, a);      // (4 wavefronts per SIMD: 28.3 against 28.0 ms)
     if (a.nMid) hipLaunchKernelGGL((assembleGroupKernel<64, 4>), g64, dim3(256), 0, st, a);
-    PH_CHECK(hipEventRecord(ctx->ev[5], st));
-    PH_CHECK(hipEventRecord(ctx->ev[6], st));
+    PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_T64_END], st));
+    PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_QUEUE_BEGIN], st));
     DevBuf dDbgRounds, dDbgCycles;
     const bool hist = asmHistOn();
     const uint32_t tierQ[5] = {a.nNarrow, a.nSmall, a.nMid32, a.nMid, a.nBig};
@@ -2200,39 +1870,145 @@ static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plass
         AsmArgs o = a; o.bigList = dOverList[1].as<uint32_t>(); o.bigCount = dOverCount.as<uint32_t>() + 1;
         hipLaunchKernelGGL(assembleBigKernel, gBig, dim3(256), 0, st, o);
     } else if (a.nBig) hipLaunchKernelGGL(assembleBigKernel, gBig, dim3(256), 0, st, a);
-    PH_CHECK(hipEventRecord(ctx->ev[7], st));
+    PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_QUEUE_END], st));
     if (hist) { const int rcH = asmHistRecord(st, N, a.qoff, a.bigList, a.nBig, a.dbgRounds, a.dbgCycles, onChip ? qCap : 64, tierQ); if (rcH) return rcH; }
+    return PLASSHIP_OK;
+}
+
+// aaDb == nullptr: assembleresults (protein DB) / nuclassembleresults (nucleotide DB); aaDb != nullptr: guidedassembleresults
+static int assembleImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plasship_seqdb *aaDb, const plasship_alns *al,
+                        const plasship_assemble_params *par, plasship_seqdb **out, plasship_seqdb **outAa, plasship_assemble_stats *stats) {
+    const bool guided = aaDb != nullptr;
+    // protein DB -> assembleresults; nucleotide DB -> nuclassembleresults (what the nuclassemble workflow runs on reads)
+    const bool nucl = db->dbtype == PLASSHIP_DBTYPE_NUCLEOTIDES;
+    if (!nucl && db->dbtype != PLASSHIP_DBTYPE_AMINO_ACIDS) { setError("plasship_assemble: the sequence DB is neither amino acids nor nucleotides"); return PLASSHIP_ERR_ARG; }
+    if (par->rescore_mode != 3) { setError("plasship_assemble: only --rescore-mode 3"); return PLASSHIP_ERR_UNSUPPORTED; }
+    if (al->nQueries != db->n) { setError("plasship_assemble: alignment list does not belong to the DB"); return PLASSHIP_ERR_ARG; }
+    PH_ENTER(ctx);
+    hipStream_t st = ctx->stream;
+    const uint32_t N = (uint32_t) db->n;
+    // nuclassembleresults / guidedassembleresults rank a query's alignment with itself among the others (it enters the heap like any hit);
+    // assembleresults pops and discards it (assembleresult.cpp:203-209): only the former need the identity pairs scored (common.hpp: selfPending)
+    if (nucl) { const int rcS = finishSelfAlns(ctx, al); if (rcS) return rcS; }
+    const uint64_t nLines = al->nSlots;                     // record slots (a sparse list: holes included, common.hpp); al->nLines of them are alignments
+    ExtSide own, twin;                                      // twin: guided only
+    DevBuf dTmp, dItems, dFlags, dMat, dStats;
+    const size_t tmpBytes = exclusiveScanTmpBytes((size_t) N + 2);
+    if (own.leftCap.alloc(((size_t) N + 1) * 4) != hipSuccess || own.bytes.alloc(((size_t) N + 1) * 8) != hipSuccess || own.arenaOff.alloc(((size_t) N + 2) * 8) != hipSuccess ||
+        dTmp.alloc(tmpBytes) != hipSuccess || dItems.alloc(std::max<uint64_t>(nLines, 1) * sizeof(Item)) != hipSuccess || dFlags.alloc(((size_t) N + 1) * 4) != hipSuccess ||
+        own.newLen.alloc(((size_t) N + 1) * 4) != hipSuccess || own.newStart.alloc(((size_t) N + 1) * 8) != hipSuccess || dMat.alloc(123 * 123) != hipSuccess || dStats.alloc(128) != hipSuccess) {
+        setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE;
     }
+    PH_CHECK(hipMemsetAsync(dFlags.p, 0, ((size_t) N + 1) * 4, st));
+    PH_CHECK(hipMemsetAsync(own.newLen.p, 0, ((size_t) N + 1) * 4, st));
+    PH_CHECK(hipMemsetAsync(dStats.p, 0, 128, st));
+    PH_CHECK(hipMemcpyAsync(dMat.p, asciiSubMat(nucl), 123 * 123, hipMemcpyHostToDevice, st));
+    { const int rcOL = ensureOffLen(ctx, db); if (rcOL) return rcOL; }          // the extension kernels look up random targets
+    const SeqView sv = db->view();
+    PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_BEGIN], st));
+    // work lists by queue size: [0] 9..16 alignments, [1] <= 32, [2] <= 64, [3] more, [4] <= 8 (tiers: arenaSizeKernel; lists: tierListKernel)
+    const uint32_t nTiles = (uint32_t) (((size_t) N + SCAN_TILE - 1) / SCAN_TILE);
+    DevBuf dBigList, dMidList, dMid32List, dSmallList, dNarrowList, dTierOf, dTierPart;
+    if (guided && (twin.leftCap.alloc(((size_t) N + 1) * 4) != hipSuccess || twin.bytes.alloc(((size_t) N + 1) * 8) != hipSuccess || twin.arenaOff.alloc(((size_t) N + 2) * 8) != hipSuccess ||
+                   twin.newLen.alloc(((size_t) N + 1) * 4) != hipSuccess || twin.newStart.alloc(((size_t) N + 1) * 8) != hipSuccess)) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+    if (guided) PH_CHECK(hipMemsetAsync(twin.newLen.p, 0, ((size_t) N + 1) * 4, st));
+    if (dBigList.alloc(((size_t) N + 1) * 4) != hipSuccess || dMidList.alloc(((size_t) N + 1) * 4) != hipSuccess || dMid32List.alloc(((size_t) N + 1) * 4) != hipSuccess ||
+        dSmallList.alloc(((size_t) N + 1) * 4) != hipSuccess || (!nucl && dNarrowList.alloc(((size_t) N + 1) * 4) != hipSuccess) || dTierOf.alloc((size_t) N + 8) != hipSuccess ||
+        dTierPart.alloc(((size_t) N_TIERS * (nTiles + 1) + 1) * 8) != hipSuccess) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+    DevBuf dQSum, dQSumAa, dQCan;
+    if (dQSum.alloc(((size_t) N + 1) * 8) != hipSuccess || dQCan.alloc(((size_t) N + 1) * 4) != hipSuccess || (guided && dQSumAa.alloc(((size_t) N + 1) * 8) != hipSuccess)) { setError("plasship_assemble: out of device memory"); return PLASSHIP_ERR_DEVICE; }
+    PH_CHECK(hipMemsetAsync(dQSum.p, 0, ((size_t) N + 1) * 8, st));
+    PH_CHECK(hipMemsetAsync(dQCan.p, 0, ((size_t) N + 1) * 4, st));
+    if (guided) PH_CHECK(hipMemsetAsync(dQSumAa.p, 0, ((size_t) N + 1) * 8, st));
+    if (nLines) hipLaunchKernelGGL(arenaSumKernel, dim3((unsigned) std::min<uint64_t>((nLines + 255) / 256, (uint64_t) ctx->numCU * 32)), dim3(256), 0, st, al->d_recs.as<AlnRec>(), (uint64_t) nLines,
+                                       (uint64_t) par->max_seq_len, dQSum.as<unsigned long long>(), guided ? dQSumAa.as<unsigned long long>() : (unsigned long long *) nullptr, dQCan.as<uint32_t>(),
+                                       (nucl && !guided) ? 1 : 0);
+    if (N) hipLaunchKernelGGL(arenaSizeKernel, dim3(std::min<uint32_t>((N + 255) / 256, 8192)), dim3(256), 0, st, sv, al->d_qoff.as<uint64_t>(), (const unsigned long long *) dQSum.as<unsigned long long>(),
+                              (const unsigned long long *) dQSumAa.as<unsigned long long>(), (const uint32_t *) dQCan.as<uint32_t>(), own.leftCap.as<uint32_t>(), own.bytes.as<uint64_t>(), nucl ? 1 : 0, (uint64_t) 1 << 30,
+                              dTierOf.as<uint8_t>(),
+                              guided ? aaDb->d_len.as<uint32_t>() : (const uint32_t *) nullptr, twin.leftCap.as<uint32_t>(), guided ? twin.bytes.as<uint64_t>() : (uint64_t *) nullptr);
+    if (guided && exclusiveScanU64(st, twin.bytes.as<uint64_t>(), twin.arenaOff.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
+    PH_CHECK(hipMemsetAsync(dTierPart.p, 0, ((size_t) N_TIERS * (nTiles + 1) + 1) * 8, st));
+    if (nTiles) hipLaunchKernelGGL(tierCountKernel, dim3(nTiles), dim3(SCAN_BLOCK), 0, st, (const uint8_t *) dTierOf.as<uint8_t>(), N, dTierPart.as<uint64_t>(), nTiles);
+    // ONE scan over the five rows end to end, in place (entry [nTiles] of a row is 0): a row's entries minus its first one are the tiles' offsets in
+    // the tier's list, and the first entry of the next row minus its own is the tier's total
+    if (exclusiveScanU64(st, dTierPart.as<uint64_t>(), dTierPart.as<uint64_t>(), (size_t) N_TIERS * (nTiles + 1), dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
+    {
+        TierLists tl;
+        tl.list[0] = dSmallList.as<uint32_t>(); tl.list[1] = dMid32List.as<uint32_t>(); tl.list[2] = dMidList.as<uint32_t>(); tl.list[3] = dBigList.as<uint32_t>();
+        tl.list[TIER_NARROW] = dNarrowList.as<uint32_t>();              // (not allocated for a nucleotide DB, whose queries have tiers 0 and 1 only)
+        if (nTiles) hipLaunchKernelGGL(tierListKernel, dim3(nTiles), dim3(SCAN_BLOCK), 0, st, (const uint8_t *) dTierOf.as<uint8_t>(), N, (const uint64_t *) dTierPart.as<uint64_t>(), nTiles, tl);
+    }
+    if (exclusiveScanU64(st, own.bytes.as<uint64_t>(), own.arenaOff.as<uint64_t>(), N, dTmp.p, tmpBytes)) { setError("plasship_assemble: scan failed"); return PLASSHIP_ERR_DEVICE; }
+    uint64_t arenaBytes = 0, aaArenaBytes = 0;
+    uint64_t rowStart[N_TIERS + 1] = {};
+    if (guided) PH_CHECK(hipMemcpyAsync(&aaArenaBytes, twin.arenaOff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
+    PH_CHECK(hipMemcpyAsync(&arenaBytes, own.arenaOff.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, st));
+    PH_CHECK(hipMemcpy2DAsync(rowStart, 8, dTierPart.p, (size_t) (nTiles + 1) * 8, 8, N_TIERS + 1, hipMemcpyDeviceToHost, st));
+    PH_CHECK(plasship::streamSync(st));
+    uint32_t cnts[N_TIERS];
+    for (int t = 0; t < N_TIERS; t++) cnts[t] = (uint32_t) (rowStart[t + 1] - rowStart[t]);
+    if (own.arena.alloc(arenaBytes + 64) != hipSuccess || (guided && twin.arena.alloc(aaArenaBytes + 64) != hipSuccess)) {
+        size_t fr = 0, tt = 0; (void) hipMemGetInfo(&fr, &tt);
+        setError("plasship_assemble: out of device memory for the extension arena (" + std::to_string(arenaBytes) + " bytes; device free " + std::to_string(fr) + " of " + std::to_string(tt) + ")"); return PLASSHIP_ERR_DEVICE;
+    }
+    HostEvaluer ev(nucl, db->residues);
+    AsmArgs a; memset(&a, 0, sizeof(a));
+    a.s = sv; a.qoff = al->d_qoff.as<uint64_t>(); a.recs = al->d_recs.as<AlnRec>(); a.items = dItems.as<Item>(); a.arenaOff = own.arenaOff.as<uint64_t>();
+    a.leftCap = own.leftCap.as<uint32_t>(); a.arena = own.arena.as<char>(); a.flags = dFlags.as<uint32_t>(); a.newLen = own.newLen.as<uint32_t>(); a.newStart = own.newStart.as<uint64_t>();
+    a.mat = dMat.as<signed char>(); a.lambda = ev.g[0]; a.logK = ev.logK; a.ln2 = ev.ln2; a.seqIdThr = par->seq_id_thr; a.maxSeqLen = par->max_seq_len;
+    a.ownLaneMin = 6;      // swept 1 / 3 / 6 / 12 / never: 30.4 / 28.4 / 27.9 / 29.9 / 40.3 ms for the two wide tiers (profiles/r05_ab_knobs.txt, call 11)
+    a.stats = dStats.as<unsigned long long>();
+    a.smallList = dSmallList.as<uint32_t>(); a.nSmall = cnts[0];
+    a.narrowList = dNarrowList.as<uint32_t>(); a.nNarrow = cnts[TIER_NARROW];
+    a.mid32List = dMid32List.as<uint32_t>(); a.nMid32 = cnts[1];
+    a.midList = dMidList.as<uint32_t>(); a.nMid = cnts[2];
+    a.bigList = dBigList.as<uint32_t>(); a.nBig = cnts[3];
+    // assembleBigKernel keeps the self hit in its HBM-resident queue (its rank decides what is left queued when the length cap ends the pop
+    // loop, assembleresult.cpp:259-263,285): the identity pairs of ITS queries are scored now (common.hpp: selfPending); the register-queue
+    // kernels never queue the self hit
+    if (!nucl && a.nBig) { const int rcS = finishSelfAlns(ctx, al, dBigList.as<uint32_t>(), a.nBig); if (rcS) return rcS; }
+    std::unique_ptr<plasship_seqdb> aaPacked;                // guided: the twins are read past their end like the reference does (OutPlacement::Exact, common.hpp):
+    if (guided && !aaDb->contiguous) {                       // a twin DB that lives in a shared heap is laid out like its DB file first
+        const int rcP = packedCopyOf(ctx, aaDb, aaPacked); if (rcP) return rcP;
+    }
+    if (guided) {
+        a.aa = (aaPacked ? aaPacked.get() : aaDb)->view(); a.aaArena = twin.arena.as<char>(); a.aaArenaOff = twin.arenaOff.as<uint64_t>(); a.aaLeftCap = twin.leftCap.as<uint32_t>();
+        a.aaNewLen = twin.newLen.as<uint32_t>(); a.aaNewStart = twin.newStart.as<uint64_t>();
+    }
+    NuclWork nuclWork;
+    { const int rcX = nucl ? runNuclPasses(ctx, a, guided, N, nLines, own.bytes.as<uint64_t>(), nuclWork) : launchProteinTiers(ctx, a, N); if (rcX) return rcX; }
     PH_TRACE(st, "assemble: extension kernels");
     // ---- output DB(s): extended queries + carried-over sequences, in key order ----
     plasship_seqdb *o = nullptr, *oAa = nullptr;
     unsigned long long hs[16] = {0};
     DevBuf dGathered, dGatheredAa;
-    const char *arenaP = dArena.as<char>(), *aaArenaP = dAaArena.as<char>();
+    const char *arenaP = own.arena.as<char>(), *aaArenaP = twin.arena.as<char>();
     if (commOf(ctx)) {
-        const int rc = mergeExtended(ctx, N, guided, par->keep_target, dFlags.as<uint32_t>(), dNewLen.as<uint32_t>(), dNewStart.as<uint64_t>(), dArena.as<char>(),
-                                     dAaNewLen.as<uint32_t>(), dAaNewStart.as<uint64_t>(), dAaArena.as<char>(), dTmp.p, tmpBytes, dGathered, dGatheredAa);
+        const int rc = mergeExtended(ctx, N, guided, par->keep_target, dFlags.as<uint32_t>(), own, twin, dTmp.p, tmpBytes, dGathered, dGatheredAa);
         if (rc != PLASSHIP_OK) return rc;
         arenaP = dGathered.as<char>(); aaArenaP = dGatheredAa.as<char>();
     }
-    int rcOut = buildOutputDB(ctx, db, dFlags.as<uint32_t>(), dNewLen.as<uint32_t>(), dNewStart.as<uint64_t>(), arenaP, par->keep_target, dTmp.p, tmpBytes, &o,
-                              dStats.p, hs, 128, guided ? (hipEvent_t) nullptr : ctx->ev[1], guided);
+    // guided: both DBs back to back in exact buffers (OutPlacement::Exact), the call's end recorded behind the second one
+    const OutPlacement place = guided ? OutPlacement::Exact : OutPlacement::Chain;
+    int rcOut = buildOutputDB(ctx, db, {.flags = dFlags.as<uint32_t>(), .newLen = own.newLen.as<uint32_t>(), .newStart = own.newStart.as<uint64_t>(), .arena = arenaP, .keepTarget = par->keep_target},
+                              dTmp.p, tmpBytes, &o, {.placement = place, .doneEvent = guided ? (hipEvent_t) nullptr : ctx->ev[ASM_EV_END], .dExtra = dStats.p, .hExtra = hs, .extraBytes = 128});
     if (rcOut != PLASSHIP_OK) return rcOut;
     std::unique_ptr<plasship_seqdb> holdO(o), holdAa;              // released to the caller on success only
     if (guided) {
-        rcOut = buildOutputDB(ctx, aaDb, dFlags.as<uint32_t>(), dAaNewLen.as<uint32_t>(), dAaNewStart.as<uint64_t>(), aaArenaP, par->keep_target, dTmp.p, tmpBytes, &oAa,
-                              nullptr, nullptr, 0, nullptr, true);
+        rcOut = buildOutputDB(ctx, aaDb, {.flags = dFlags.as<uint32_t>(), .newLen = twin.newLen.as<uint32_t>(), .newStart = twin.newStart.as<uint64_t>(), .arena = aaArenaP, .keepTarget = par->keep_target},
+                              dTmp.p, tmpBytes, &oAa, {.placement = place});
         if (rcOut != PLASSHIP_OK) return rcOut;
         holdAa.reset(oAa);
     }
-    if (guided) { PH_CHECK(hipEventRecord(ctx->ev[1], st)); PH_CHECK(plasship::streamSync(st)); }
+    if (guided) { PH_CHECK(hipEventRecord(ctx->ev[ASM_EV_END], st)); PH_CHECK(plasship::streamSync(st)); }
     if (hs[12]) { setError("plasship_guided_assemble: an alignment asks for a protein fragment the twin does not have (coordinates are not codon aligned)"); return PLASSHIP_ERR_ARG; }
     if (stats) {
         stats->n_extended = hs[0]; stats->n_rescored = hs[1]; stats->out_residues = o->residues;
-        float ms = 0; (void) hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]); stats->ms_kernel = ms;
+        float ms = 0; (void) hipEventElapsedTime(&ms, ctx->ev[ASM_EV_BEGIN], ctx->ev[ASM_EV_END]); stats->ms_kernel = ms;
         float sum = 0;
         for (int t = 0; t < 3; t++) {
-            ms = 0; (void) hipEventElapsedTime(&ms, ctx->ev[2 + 2 * t], ctx->ev[3 + 2 * t]); stats->ms_tier_kernel[t] = ms; sum += ms;
+            ms = 0; (void) hipEventElapsedTime(&ms, ctx->ev[ASM_EV_T16_BEGIN + 2 * t], ctx->ev[ASM_EV_T16_END + 2 * t]); stats->ms_tier_kernel[t] = ms; sum += ms;
             stats->tier_alignments[t] = hs[3 + 3 * t]; stats->tier_query_residues[t] = hs[4 + 3 * t]; stats->tier_rescored_residues[t] = hs[5 + 3 * t];
         }
         stats->ms_assemble_kernel = sum;

@@ -186,7 +186,7 @@ struct plasship_ctx {
 
 namespace plasship {
 uint64_t newDbGeneration();
-// An append-only byte heap shared by a chain of sequence DBs (assemble.hip, buildOutputDB): an assembly iteration changes 10-20 % of
+// An append-only byte heap shared by a chain of sequence DBs (outdb.hip, buildOutputDB): an assembly iteration changes 10-20 % of
 // the sequences, so the DB it makes keeps the bytes of the unchanged entries where they are — its index points into the heap of the
 // DB it derives from — and only the extended entries are appended behind `used`.  Nothing is ever overwritten, so every DB of the
 // chain stays valid for as long as its handle lives; the buffer goes when the last of them does.
@@ -335,14 +335,35 @@ int commAlltoallvRecords(plasship_ctx *ctx, const void *dSend, const uint64_t *s
 int commAllgathervBytes(plasship_ctx *ctx, const void *dSend, uint64_t sendBytes, DevBuf &recv, std::vector<uint64_t> &recvBytes);
 // the same when every rank already knows everybody's size (recvBytes[world] given)
 int commAllgathervBytesKnown(plasship_ctx *ctx, const void *dSend, uint64_t sendBytes, DevBuf &recv, const std::vector<uint64_t> &recvBytes);
-// builds an output sequence DB in key order (assemble.hip): entries with flag 0x20 come from `dArena + dNewStart[id]` (dNewLen[id]
-// residues), the others are carried over from `db` (dropped when !keepTarget and flag 0x80 is set)
-// a copy of `db` with its entries back to back in key order in a buffer of its own (assemble.hip); callers that stream or copy the
+// ---- the output-DB writer (outdb.hip) ----
+// where buildOutputDB puts the entries of the DB it makes
+enum class OutPlacement {
+    // the DB shares `db`'s heap (SeqHeap) when it has one with room: only the rewritten entries move.  Otherwise it opens a new heap with
+    // slack for the iterations to come (PLASSHIP_TUNE_DBHEAP=2: no heaps, an exact buffer of its own).  Lineage and origin are recorded.
+    Chain,
+    // back to back in key order in an exact buffer — the layout of the DB file — with lineage and origin.  For the DBs of the protein-guided
+    // path: the reference's proteinaln2nucl and guidedassembleresults read PAST the end of an entry when a protein twin and its ORF / 3
+    // differ in length, i.e. into the entry that FOLLOWS in the data file; behind an entry appended to a shared heap
+    // lies whatever was appended next.  tests/test_gpu_deep.py::test_four_guided_iterations (round 5) found the difference in the third
+    // guided iteration, the first one whose input DB had appended entries: 3 bytes of one alignment DB in 382 MB.  Also for a DB nobody
+    // will ever append behind (cyclecheck's cycle DB): no slack.
+    Exact,
+    // a packed copy in an exact buffer, no lineage, no origin (packedCopyOf)
+    Packed
+};
+// what differs from `db`: entries with flag 0x20 come from `arena + newStart[id]` (newLen[id] residues), the others are carried over
+// from `db` (dropped when !keepTarget and flag 0x80 is set)
+struct OutEdits { const uint32_t *flags = nullptr; const uint32_t *newLen = nullptr; const uint64_t *newStart = nullptr; const char *arena = nullptr; int keepTarget = 0; };
+struct OutOptions {
+    OutPlacement placement = OutPlacement::Chain;
+    hipEvent_t doneEvent = nullptr;       // recorded behind the writer's last kernel
+    const void *dExtra = nullptr; void *hExtra = nullptr; size_t extraBytes = 0;       // the caller's counters ride along with the writer's last copy to the host
+};
+// builds an output sequence DB in key order (outdb.hip) from `db` and the edits
+int buildOutputDB(plasship_ctx *ctx, const plasship_seqdb *db, const OutEdits &edits, void *dTmp, size_t tmpBytes, plasship_seqdb **out, const OutOptions &opt = {});
+// a copy of `db` with its entries back to back in key order in a buffer of its own (outdb.hip); callers that stream or copy the
 // data of a DB as one block (DB files, downloads, concatdbs) take it when !db->contiguous
 int packedCopyOf(plasship_ctx *ctx, const plasship_seqdb *db, std::unique_ptr<plasship_seqdb> &out);
-int buildOutputDB(plasship_ctx *ctx, const plasship_seqdb *db, const uint32_t *dFlags, const uint32_t *dNewLen, const uint64_t *dNewStart,
-                  const char *dArena, int keepTarget, void *dTmp, size_t tmpBytes, plasship_seqdb **out,
-                  const void *dExtra = nullptr, void *hExtra = nullptr, size_t extraBytes = 0, hipEvent_t doneEvent = nullptr, bool noAppend = false);
 // ---- host boundary (core.hip): bulk copies through the context's pinned double buffer, on the context stream ----
 // H2D of `total` bytes the caller produces chunk by chunk: produce(dst, byteOffset, bytes) fills a pinned chunk (consecutive chunks,
 // in order; it may use the host threads) while the previous chunk is in flight.  Returns after the last copy has completed.

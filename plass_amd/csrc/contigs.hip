@@ -157,7 +157,7 @@ __global__ void fastaChunkKernel(const uint64_t *__restrict__ outOff, uint64_t n
     }
 }
 // entries [b, e) into `out` (byte 0 = the first byte of entry b).  Every lane formats its own entry's header; then the wavefront copies the
-// sequences of its 64 entries one after the other with all 64 lanes, 8 bytes per lane and step (the copy of appendOutKernel, assemble.hip)
+// sequences of its 64 entries one after the other with all 64 lanes, 8 bytes per lane and step (the copy of appendOutKernel, outdb.hip)
 __global__ __launch_bounds__(256) void fastaWriteKernel(const char *data, const uint64_t *__restrict__ off, const uint32_t *__restrict__ len,
                                                         const uint64_t *__restrict__ outOff, const unsigned char *__restrict__ cyc, int hasCycle,
                                                         uint64_t b, uint64_t e, char *__restrict__ out) {

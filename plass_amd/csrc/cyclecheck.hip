@@ -435,15 +435,16 @@ extern "C" int plasship_cyclecheck(plasship_ctx *ctx, const plasship_seqdb *db, 
     // the circular sequences (whole or cut) ...
     plasship_seqdb *oc = nullptr, *orest = nullptr;
     if (N) hipLaunchKernelGGL(cycleFlagsKernel, dim3(gridN), dim3(256), 0, st, sv, dSplit.as<uint32_t>(), par->chop_cycle ? 1 : 0, 0, dFlags.as<uint32_t>(), dNewLen.as<uint32_t>(), dNewStart.as<uint64_t>());
-    int rc = buildOutputDB(ctx, db, dFlags.as<uint32_t>(), dNewLen.as<uint32_t>(), dNewStart.as<uint64_t>(), sv.data, 0, dTmp.p, tmpBytes, &oc, nullptr, nullptr, 0, ctx->ev[1],
-                           true);      // (noAppend: the cycle DB is written out and freed at once — its entries do not belong in the chain's long-lived heap)
+    const OutEdits edits = {.flags = dFlags.as<uint32_t>(), .newLen = dNewLen.as<uint32_t>(), .newStart = dNewStart.as<uint64_t>(), .arena = sv.data, .keepTarget = 0};
+    // (Exact: the cycle DB is written out and freed at once — its entries do not belong in the chain's long-lived heap)
+    int rc = buildOutputDB(ctx, db, edits, dTmp.p, tmpBytes, &oc, {.placement = OutPlacement::Exact, .doneEvent = ctx->ev[1]});
     if (rc != PLASSHIP_OK) return rc;
     std::unique_ptr<plasship_seqdb> holdC(oc);
     oc->dbtype = PLASSHIP_DBTYPE_NUCLEOTIDES;
     // ... and, if asked for, everything else (what the workflow continues with: "<db>_noneCycle", data/nuclassemble.sh:27-35)
     if (out_rest) {
         if (N) hipLaunchKernelGGL(cycleFlagsKernel, dim3(gridN), dim3(256), 0, st, sv, dSplit.as<uint32_t>(), 0, 1, dFlags.as<uint32_t>(), dNewLen.as<uint32_t>(), dNewStart.as<uint64_t>());
-        rc = buildOutputDB(ctx, db, dFlags.as<uint32_t>(), dNewLen.as<uint32_t>(), dNewStart.as<uint64_t>(), sv.data, 0, dTmp.p, tmpBytes, &orest);
+        rc = buildOutputDB(ctx, db, edits, dTmp.p, tmpBytes, &orest);
         if (rc != PLASSHIP_OK) return rc;
         ctx->cycKnownGen = orest->gen; ctx->cycKnownMaxLen = (uint64_t) par->max_seq_len;      // every entry of it has split == 0
     }

@@ -123,8 +123,8 @@ static int findStartImpl(plasship_ctx *ctx, const plasship_seqdb *db, const plas
     if (dArena.alloc(arenaBytes + 64) != hipSuccess) { setError("plasship_find_assembly_start: out of device memory"); return PLASSHIP_ERR_DEVICE; }
     if (N) hipLaunchKernelGGL(findStartFillKernel, dim3(grid), dim3(256), 0, st, sv, dStop.as<int>(), dStart.as<uint64_t>(), dArena.as<char>());
     plasship_seqdb *o = nullptr;
-    const int rc = buildOutputDB(ctx, db, dFlags.as<uint32_t>(), dNewLen.as<uint32_t>(), dStart.as<uint64_t>(), dArena.as<char>(), 1, dTmp.p, tmpBytes, &o,
-                                 nullptr, nullptr, 0, ctx->ev[1]);
+    const int rc = buildOutputDB(ctx, db, {.flags = dFlags.as<uint32_t>(), .newLen = dNewLen.as<uint32_t>(), .newStart = dStart.as<uint64_t>(), .arena = dArena.as<char>(), .keepTarget = 1},
+                                 dTmp.p, tmpBytes, &o, {.doneEvent = ctx->ev[1]});
     if (rc != PLASSHIP_OK) return rc;
     o->dbtype = PLASSHIP_DBTYPE_AMINO_ACIDS;                                              // findassemblystart.cpp:47
     if (stats) {

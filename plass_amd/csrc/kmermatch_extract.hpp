@@ -1454,7 +1454,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void ex
 //     128-byte lines of section 2c do not fit; instead the extraction kernels leave, beside the record array, ONE WINDOW POSITION PER
 //     RECORD SLOT (u16, u32 in the long layout; the slot of the identity record holds the count) and the identity hash per id, and the
 //     DBs derived from the DB of that call carry, per entry, the id it had there (plasship_seqdb::d_origin, 0xFFFFFFFF = rewritten —
-//     buildOutputDB, assemble.hip).  The next call with the same selection parameters rebuilds the records of every such entry here:
+//     buildOutputDB, outdb.hip).  The next call with the same selection parameters rebuilds the records of every such entry here:
 //     canonical k-mer and strand from the bytes at the cached positions, nothing hashed, nothing selected.  Same records in the same
 //     slots as the full kernels write (the nucleotide chain tests pass through here from their third call on; PLASSHIP_TUNE_KMCACHE=2
 //     switches it off).
